@@ -5,6 +5,10 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...      (no launcher: starts that same torch.distributed.run command itself, as a child process)
 
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs is given, and prints the line.
+--full adds everything else the line can carry: HIP-event spans of the hot kernels with the per-kernel / roofline table, the launch
+census, host calibration, the bucket timeline, the `also` sub-records (fp32, D + G, graph replays) and the CPU baseline.
+
 One step = one generator training step of the `--model stylegan3` path on one batch of synthetic MR-like slices:
 mapping + encoder + co-modulated decoder forward (HIP filtered_lrelu / bias_act / MFMA convs), lambda_L1 * L1 loss,
 backward, gradient all-reduce across ranks (RCCL), NaN scrub, Adam step -- StyleGAN3GeneratorStep.optimize_parameters.
@@ -72,12 +76,21 @@ def parse():
                     help='time the FULL iteration (D update with R1, then G update with the GAN term; SURVEY.md row f1) instead of the '
                          'generator step that BASELINE.json\'s metric names')
     ap.add_argument('--lean', action='store_true',
-                    help='the timed steps and nothing else: --cpu-baseline off --also off --host-calibration off --no-launch-census (A/B tools and '
-                         'every rocprofv3 script: one tracer, no extra steps in the kernel statistics)')
+                    help='with --full: the timed steps and the kernel spans, nothing else: --cpu-baseline off --also off --host-calibration off '
+                         '--no-launch-census (A/B tools; a plain run is leaner still)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: kernel spans, per-kernel / roofline table, launch census, host calibration, bucket '
+                         'timeline, the `also` sub-records and the CPU baseline (each still subject to its own switch above)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the generated batch, the '
+                         'losses, and a fixed sample of every network\'s updated parameters and their gradients')
     a = ap.parse_args()
     if a.lean:
         a.cpu_baseline = a.also = a.host_calibration = 'off'
         a.no_launch_census = True
+    if not a.full:
+        a.cpu_baseline = a.also = a.host_calibration = 'off'
+        a.no_kernel_timing = True
     return a
 
 
@@ -289,7 +302,7 @@ def kernel_table(fams, dtype_name, fp32_conv, timed_with_events):
     return kernels
 
 
-def timed_steps(step, inputs, steps, warmup, world, use_dist, kernel_timing, every, dev):
+def timed_steps(step, inputs, steps, warmup, world, use_dist, kernel_timing, every, dev, bucket_trace=True):
     """`warmup` untimed steps, then EXACTLY `steps` timed ones between barrier + synchronize on both sides (max over ranks).
     Returns dict(elapsed, host_wall, host_cpu, timed_with_events, families, threads, one_step)."""
     import torch
@@ -317,7 +330,7 @@ def timed_steps(step, inputs, steps, warmup, world, use_dist, kernel_timing, eve
         if kernel_timing:
             profiling.enabled = (i % max(1, every) == 0)
             timed_with_events += int(profiling.enabled)
-        if use_dist and step.buckets is not None and i == steps - 1:
+        if bucket_trace and use_dist and step.buckets is not None and i == steps - 1:
             # the LAST timed step carries the bucket timeline: CUDA events at the phase boundaries and at every bucket's launch
             # (records only, nothing waits on them)
             step.buckets.trace, step.phase_events = [], {}
@@ -344,6 +357,43 @@ def timed_steps(step, inputs, steps, warmup, world, use_dist, kernel_timing, eve
                                               for ns, name, t in busy[:6] if ns > 0])
     return dict(elapsed=elapsed, host_wall=host_wall, host_cpu=host_cpu, timed_with_events=timed_with_events,
                 families=profiling.summary() if kernel_timing else {}, threads=threads, one_step=one_step)
+
+
+def _sample(t, n, seed):
+    """t as float32 on the host: whole if it has at most n elements, else flattened and taken at up to n sorted indices drawn with `seed`
+    (the same indices for the same shape in every run)."""
+    import numpy as np
+    import torch
+    t = t.detach()
+    if t.numel() > n:
+        idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), n))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(step, out_dir, max_image=1 << 23, max_params=1 << 20):
+    """What the timed path's last step hands its caller, as DIR/<name>.npy in float32: the generated batch `fake_B` (a fixed sample of
+    max_image elements beyond that size), every loss tensor of the step, and per network (G, and D with --with-discriminator) a fixed
+    sample of max_params elements of its parameters after the update and of the gradients that update used (zeros where a parameter
+    had none).  At most 32 + 4 * 4 MB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    out = {'fake_B': _sample(step.fake_B, max_image, 0)}
+    for k, v in sorted(vars(step).items()):
+        if k.startswith('loss_') and torch.is_tensor(v):
+            out[k] = v.detach().float().cpu().numpy()
+    for tag in ('G', 'D'):
+        net = getattr(step, 'net' + tag, None)
+        if net is None:
+            continue
+        params = list(net.parameters())
+        out[f'{tag}_params'] = _sample(torch.cat([p.detach().reshape(-1).float() for p in params]), max_params, 1)
+        out[f'{tag}_grads'] = _sample(torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in params]),
+                                      max_params, 1)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v.astype(np.float32))
+    return sorted(out)
 
 
 def launch_census(one_step, rank, world, skip):
@@ -501,9 +551,11 @@ def main():
         from afcm_amd.torch_utils.ops import fused_layer
         fused_layer.HOMOGENEOUS_DOT = False
     step, inputs = build_step(args, dev, args.dtype, args.with_discriminator, use_dist, args.fp32_conv)
-    r = timed_steps(step, inputs, args.steps, args.warmup, world, use_dist, not args.no_kernel_timing, args.kernel_timing_every, dev)
+    r = timed_steps(step, inputs, args.steps, args.warmup, world, use_dist, not args.no_kernel_timing, args.kernel_timing_every, dev,
+                    bucket_trace=args.full)
     elapsed, host_wall, host_cpu, timed_with_events = r['elapsed'], r['host_wall'], r['host_cpu'], r['timed_with_events']
     r_threads, families = r['threads'], r['families']
+    dumped = dump_outputs(step, args.dump_outputs) if (args.dump_outputs and rank == 0) else None     # before any further step
 
     bucket_timeline = None
     if use_dist and step.buckets is not None and getattr(step, 'phase_events', None):
@@ -516,7 +568,7 @@ def main():
                                buckets=[dict(bucket=i, mbytes=round(nb / 1e6, 1), issued_at_ms=round(pe['backward'].elapsed_time(e), 2),
                                              backward_left_ms=round(bwd_ms - pe['backward'].elapsed_time(e), 2)) for i, nb, e in step.buckets.trace])
         step.buckets.trace = step.phase_events = None
-    launches = launch_census(r['one_step'], rank, world, args.no_launch_census)
+    launches = launch_census(r['one_step'], rank, world, args.no_launch_census) if args.full else None
     if rank == 0:
         kernels = kernel_table(families, args.dtype, args.fp32_conv, timed_with_events)
         dominant = max(kernels, key=lambda k: kernels[k]['total_ms']) if kernels else None
@@ -525,7 +577,7 @@ def main():
         # (tools/pmc_traffic.sh -> profiles/pmc_traffic.json, which names the build it was taken on); said so in `traffic_source`
         tpath = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
         default_workload = args.dtype == 'bf16' and args.batch == 16 and args.res == 256 and not args.with_discriminator
-        if os.path.exists(tpath) and default_workload:        # the PMC passes were taken on the default command only
+        if kernels and os.path.exists(tpath) and default_workload:        # the PMC passes were taken on the default command only
             try:
                 t = json.load(open(tpath))
                 src = f'profiles/pmc_traffic.json ({t.get("_source", "rocprofv3 --pmc passes of bench.py")}), not measured in this run'
@@ -603,6 +655,8 @@ def main():
             out['also'] = also
         if bucket_timeline is not None:
             out['bucket_timeline'] = bucket_timeline
+        if dumped is not None:
+            out['dumped_outputs'] = dict(dir=args.dump_outputs, arrays=dumped)
         print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()

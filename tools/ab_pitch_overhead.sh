@@ -6,7 +6,7 @@ for v in "$@"; do
 import runpy, sys
 import afcm_amd.torch_utils.ops._rows as r
 r.MAX_OVERHEAD = float(sys.argv[1])
-sys.argv = ['bench.py', '--lean', '--steps', '12', '--warmup', '3']
+sys.argv = ['bench.py', '--full', '--lean', '--steps', '12', '--warmup', '3']
 runpy.run_path('bench.py', run_name='__main__')
 PY
   python - "$v" <<'PY'

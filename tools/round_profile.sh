@@ -6,9 +6,10 @@
 set -e
 tag=$1
 export TMPDIR=/tmp
+res=${RESULTS_DIR:-results}; mkdir -p "$res"
 python -m pytest tests -m gpu -x -q > gpurun_out/${tag}_tests.log 2>&1 < /dev/null
 echo tests done
-python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err < /dev/null
+python bench.py --full > "$res/${tag}_bench.json" 2> "$res/${tag}_bench.err" < /dev/null
 echo bench done
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${tag}_smoke.log 2>&1 < /dev/null
 bash tools/r03_step_profile.sh ${tag} < /dev/null > /dev/null 2>&1 || true
