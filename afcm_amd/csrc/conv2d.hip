@@ -17,10 +17,6 @@
 
 #include "common.h"
 
-#ifndef AFCM_CONV_BM96_PERSIST
-#define AFCM_CONV_BM96_PERSIST 1   // the 96-row block as persistent workgroups (two per CU) like the 64-row one: 228 registers, no spills; 3-7 % on the 91-row launches (profiles/r05_conv_bm96_ab.txt)
-#endif
-
 namespace afcm {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -49,25 +45,11 @@ template <> struct ConvCfg<bf16_t> { static constexpr int BK = 16, PITCH = 24; }
 template <> struct ConvCfg<f16_t>  { static constexpr int BK = 16, PITCH = 24; };
 template <> struct ConvCfg<float>  { static constexpr int BK = 8,  PITCH = 9;  };   // 36-byte rows: conflict-free b32
 
-// MFMA shape of the 16-bit 3x3 stride-1 kernel: 1 = v_mfma_f32_16x16x32 (conv2d_fwd16x_kernel, K-chunks of 32 channels), 0 = 32x32x16
-// (conv2d_fwd16_kernel, chunks of 16).  -DAFCM_CONV_AB builds both and a debug switch (tools/ab_conv_shape.py): the A/B of r05.
-#ifndef AFCM_CONV_X16
-#define AFCM_CONV_X16 1
-#endif
-#ifdef AFCM_CONV_AB
-static int g_conv_x16 = AFCM_CONV_X16;
-#define AFCM_X16_ON (g_conv_x16 != 0)
-#else
-#define AFCM_X16_ON (AFCM_CONV_X16 != 0)
-#endif
 // K-chunk (channels) of the packed weight image for (dtype, kernel size)
 static inline int conv_bk(int dtype, int ks);
 // conv2d_direct.hip: 16-bit 3x3 convs with at most four input channels (the generator's first layer)
 int conv2d_direct_small_cin(const void* x, void* y, const void* wp, const float* oscale, const float* obias, int dtype, int n, int cin, int cout,
                             int h, int w, int pad, int rows_pad, int bk, int ldx, int ldy, hipStream_t st);
-#ifndef AFCM_CONV_DIRECT4
-#define AFCM_CONV_DIRECT4 1        // 0: the implicit-GEMM kernels for every layer (A/B builds)
-#endif
 
 constexpr int kPatchMax = 416;   // LDS patch capacity in pixels
 constexpr int kPlaneX16 = 416;    // pixels per channel-group plane of conv2d_fwd16x_kernel (a multiple of 16: planes 256 bytes apart) ...
@@ -82,7 +64,7 @@ struct ConvParams {
     const float* oscale;  // [N * Cout] or null
     const float* obias;   // [Cout] or null: y = acc * oscale + obias
     int N, Cin, Cout, H, W, P, Q;
-    int ldx, ldy;         // row pitch (elements) of x / y; = W / Q for dense tensors.  conv2d_fwd16_kernel only.
+    int ldx, ldy;         // row pitch (elements) of x / y; = W / Q for dense tensors
     int pad;
     int TH, TW, PWL, tilesX, tilesY;
     int Opad, nkc;
@@ -90,7 +72,7 @@ struct ConvParams {
     int o_base;           // conv2d_fwd16x_kernel: first output row of this launch (a layer may be split between the 128- and the 64-row kernel)
     unsigned magicTW;     // ceil(2^32 / TW): j / TW = umulhi(j, magicTW) for the tile-local pixel indices (j < 2^16)
     unsigned magicTX, magicTY, magicN, magicPC;   // ... / tilesX, tilesY, N (block index decode: dividend x divisor < 2^32), / (PWL / 4)
-    // split-precision form (conv2d_fwd16_kernel<bf16, BM, true>): x holds `parts` bf16 tensors [N, Cin, H, ldx] part_bytes apart,
+    // split-precision form (conv2d_fwd16x_kernel<bf16, BM, true>): x holds `parts` bf16 tensors [N, Cin, H, ldx] part_bytes apart,
     // the K loop runs over terms x nkc_real chunks, term t reads part (term_parts >> 4 t) & 15; y is fp32
     int nkc_real; unsigned magicNK, term_parts; int part_bytes, last_part_bytes;   // last_part_bytes: offset of the highest part any term reads
     const unsigned* bound_a; const unsigned* bound_b;   // magnitude-bound words of the two operands (or null): their power-of-two factors are undone in the epilogue
@@ -364,466 +346,23 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 1 : 2)) void conv2d_fwd_kern
 }
 
 // ---------------------------------------------------------------------------------------------
-// 16-bit 3x3 forward / data-gradient kernel, r02 structure.  Same tile (BM_O channels x 256 pixels, 4 waves as 2(o) x
-// 2(pixel halves), 2 workgroups per CU), different operand paths:
-//   * weights never touch LDS: the packed layout [kc][tap][Opad][16] already IS the A-fragment image (lane (r32, h) ->
-//     16 bytes at row r32, half h; a wave reads one contiguous 1 KB), so every wave loads its fragments straight from
-//     L2 into a 3-tap-deep register ring, three taps ahead of their MFMAs.  That removes 9 of the 13 staging pieces per
-//     thread and K-chunk, the 36 staging VGPRs, a third of the LDS reads and 55 KB of LDS per workgroup;
-//   * the activation patch (transposed NCHW -> [pixel][channel] while staging) is double-buffered in the freed LDS:
-//     ONE barrier per K-chunk instead of two, and the transposing ds_writes sit among the MFMAs of the running chunk;
-//   * the patch writes are conflict-free: a thread owns 4 consecutive pixels (192 bytes apart from its neighbour's, a
-//     4-way conflict when every lane writes its pixel e at step e), so lane i writes pixel (e + (i >> 2)) & 3 at step e;
+// 16-bit 3x3 forward / data-gradient kernel.  Tile: BM_O channels x 256 pixels, 4 waves as 2(o) x 2(pixel halves), wave tile
+// (BM_O / 2) x 128 = MO x 8 accumulator tiles of v_mfma_f32_16x16x32, 2 workgroups per CU.  Kept from the r02 structure (a 32x32x16
+// kernel on K-chunks of 16 channels; DESIGN.md, "Retired build switches"):
+//   * weights never touch LDS: the packed layout already IS the A-fragment image, so every wave loads its fragments straight from
+//     L2 into a register ring, taps ahead of their MFMAs;
+//   * the activation patch (transposed NCHW -> [pixel][channel] while staging) is double-buffered in LDS: ONE barrier per K-chunk,
+//     and the transposing ds_writes sit among the MFMAs of the running chunk;
 //   * XCD-aware tile order: neighbouring tiles of one image (shared halos, same weights) stay on one XCD's L2.
-// Measured bounds (ablation builds, whole-generator conv bench, baseline 0.92 / 0.96 PF/s fwd / dgrad): weight fragments served
-// from L1 +2 %; no barrier +0 %; B fragments read once per chunk +5 %; patch written later in the chunk +0 %; the four
-// transposing ds_write_b128 removed (loads and permutes kept) +19 %; the whole activation path removed +38 %.  So the
-// register -> LDS transpose that NCHW forces is the limiter; LDS-DMA + ds_read_b64_tr_b16 cannot replace it because the
-// transposing read ignores the low three address bits (tools/ubench/tr_align_probe.hip) and the tap columns shift by
-// 1 and 2 pixels.
-#ifdef AFCM_CONV_STAMPS        // diagnostic build only: shader-clock stamps per workgroup (entry, K loop start, K loop end, exit)
-__device__ unsigned long long afcm_conv_stamps_buf[4 * 65536];
-__device__ unsigned long long afcm_conv_bar_buf[4 * 65536];    // per wave: cycles spent at the K loop's barriers
-__device__ unsigned long long afcm_conv_rt_buf[4 * 65536];     // the 100 MHz constant clock at the same four points: shader clock = d cycles / d ticks x 100 MHz
-#define AFCM_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 65536) { afcm_conv_stamps_buf[4 * blockIdx.x + (k)] = __builtin_readcyclecounter(); \
-                                                                          afcm_conv_rt_buf[4 * blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-// inside the prologue of conv2d_fwd16x_kernel (wave 0): 0 = requests issued, 1 = all of them returned (an explicit vmcnt(0)), 2 = patch written
-__device__ unsigned long long afcm_conv_pro_buf[4 * 65536];
-#define AFCM_STAMP_P(k) do { if ((k) == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
-                             if (threadIdx.x == 0 && blockIdx.x < 65536) afcm_conv_pro_buf[4 * blockIdx.x + (k)] = __builtin_readcyclecounter(); } while (0)
-// (the persistent kernel stamps per TILE: slot = the work item; a workgroup's first tile carries the prologue)
-#define AFCM_STAMP_I(k, it) do { if (threadIdx.x == 0 && (it) < 65536) { afcm_conv_stamps_buf[4 * (it) + (k)] = __builtin_readcyclecounter(); \
-                                                                          afcm_conv_rt_buf[4 * (it) + (k)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#else
-#define AFCM_STAMP(k) do { } while (0)
-#define AFCM_STAMP_P(k) do { } while (0)
-#define AFCM_STAMP_I(k, it) do { } while (0)
-#endif
-template <typename T, int BM_O, bool SPLIT = false>
-__global__ __launch_bounds__(256, 2) void conv2d_fwd16_kernel(ConvParams p) {
-    static_assert(sizeof(T) == 2, "16-bit types only");
-    typedef ConvCfg<T> C;
-    typedef typename std::conditional<SPLIT, float, T>::type TO;      // output element
-    constexpr int KS = 3, KK = 9, BK = C::BK, PITCH = C::PITCH, MI = BM_O / 64;
-    // RING: taps the weight fragments run ahead; NP: patch register sets (2 = the patch of chunk k + 2 requested at the top of chunk
-    // k); BD: taps the B fragments run ahead.  r04 built and measured the deeper forms on the 64-row blocks (RING 9 at two waves per
-    // SIMD or with 9-11 spilled registers at three, NP 2, BD 2, the transposing write at tap 7 / 8): 0-8 % slower on every layer
-    // (profiles/r04_conv_ring_depth.txt) -- the chunk does not wait for any ONE of these round trips.
-    constexpr int RING = 3, NP = 1, BD = 1;
-    typedef typename std::conditional<std::is_same<T, bf16_t>::value, bf16x8, f16x8>::type frag_t;
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-    __shared__ __attribute__((aligned(16))) T lds[2 * kPatchMax * PITCH + 4 * PITCH];      // + a sink for lanes outside the patch
-
-    AFCM_STAMP(0);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wo = wave & 1, wpx = wave >> 1;
-    const int r32 = lane & 31, h = lane >> 5;
-
-    int bid = blockIdx.x;
-    {
-        const int total = gridDim.x;
-        bid = xcd_order(bid, total);
-    }
-    // block index -> (tile x, tile y, image, row block): multiplications by host-made reciprocals on the scalar unit (an integer division,
-    // even of uniform operands, is ~30 vector instructions, and everything derived from a VGPR result -- image base, buffer
-    // descriptor -- would sit in VGPRs with a waterfall loop around every buffer load)
-    unsigned q0 = udiv_magic((unsigned)bid, p.magicTX);
-    const int tx = __builtin_amdgcn_readfirstlane(bid - (int)q0 * p.tilesX);
-    unsigned q1 = udiv_magic(q0, p.magicTY);
-    const int ty = __builtin_amdgcn_readfirstlane((int)q0 - (int)q1 * p.tilesY);
-    unsigned q2 = udiv_magic(q1, p.magicN);
-    const int n = __builtin_amdgcn_readfirstlane((int)q1 - (int)q2 * p.N);
-    const int ob = __builtin_amdgcn_readfirstlane((int)q2);
-    const int y0 = ty * p.TH, x0 = tx * p.TW;
-    const int o0 = ob * BM_O;
-    const int PH = p.TH + KS - 1, PWL = p.PWL;
-    const int xorg = (x0 - p.pad) & ~1;
-    const int xoff = (x0 - p.pad) - xorg;
-
-    f32x16 acc[MI][4];
-#pragma unroll
-    for (int mi = 0; mi < MI; mi++)
-#pragma unroll
-        for (int ti = 0; ti < 4; ti++)
-#pragma unroll
-            for (int e = 0; e < 16; e++) acc[mi][ti][e] = 0.f;
-
-    // ---- A fragments: straight from the packed weights
-    const T* wlane = (const T*)p.wp + (size_t)(o0 + wo * (BM_O / 2) + r32) * BK + h * 8;
-    const size_t wtap = (size_t)p.Opad * BK;                       // elements per tap
-    auto load_a = [&](int kc, int tap, int mi) __attribute__((always_inline)) {
-        return *(const frag_t*)(wlane + ((size_t)kc * KK + tap) * wtap + mi * 32 * BK);
-    };
-
-    // ---- patch staging (one item = 4 pixels x 8 channels), as in conv2d_fwd_kernel
-    const int cg = (tid >> 5) & 1, pg = (tid & 31) + 32 * (tid >> 6);
-    const int pcols = PWL >> 2;
-    const int prow = (int)udiv_magic((unsigned)pg, p.magicPC), pcol4 = pg - prow * pcols;
-    const bool pvalid = prow < PH;
-    const int iy = y0 - p.pad + prow, ix = xorg + 4 * pcol4;
-    const bool rowok = pvalid && (unsigned)iy < (unsigned)p.H;
-    const T* xn = (const T*)p.x + (size_t)n * p.Cin * p.H * p.ldx;
-    const long long pix_off = (long long)(rowok ? iy : 0) * p.ldx + ix;
-    const int pdst = (prow * PWL + 4 * pcol4) * PITCH + cg * 8;
-    constexpr unsigned kOob = 0x80000000u;
-    const bool d0ok = rowok && (unsigned)ix < (unsigned)p.W, d1ok = rowok && (unsigned)(ix + 2) < (unsigned)p.W;
-    const unsigned pmask0 = d0ok ? ~0u : 0u, pmask1 = d1ok ? ~0u : 0u;
-    const bool lshift = !d0ok && d1ok;                                                // never touch bytes before a row 0
-    const unsigned pvoff = (d0ok || d1ok) ? (unsigned)(((long long)cg * 8 * p.H * p.ldx + pix_off + (lshift ? 2 : 0)) * 2ll) : kOob;
-    // (split form: one descriptor from this image in part 0 to its end in the highest part read -- the part offset rides in the scalar
-    // offset, and the range check covers vector + scalar offset (tools/ubench/buffer_range_probe.hip).  It has to end exactly there: the
-    // 8-byte loads of a row's last columns run up to 4 bytes past the row, which for the last row of the last image of the last part is
-    // past the allocation; host: that end lies below 2^31 bytes)
-    const long long img_bytes = (long long)p.Cin * p.H * p.ldx * 2ll + (SPLIT ? (long long)p.last_part_bytes : 0ll);
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)xn, 0, (int)(img_bytes > 0x7fffffffll ? 0x7fffffffll : img_bytes), 0x00020000);
-    const int hw2 = p.H * p.ldx * 2;
-
-    unsigned preg[NP][8][2];
-    // Channels past Cin exist only in the last chunk of a layer whose Cin is not a multiple of 16.  In the plain form the descriptor
-    // ends with the image and the range check (vector + scalar offset) zeroes them; in the split form the descriptor runs on into the
-    // next part, so those lanes get the out-of-range vector offset.  Decided here, at the chunk boundary, to keep the tap loop free of
-    // branches.
-    // Branch-free, and issued on EVERY chunk (past the last one with the out-of-range offset: zeros, no memory traffic): a
-    // conditional issue makes the compiler's s_waitcnt for the weight ring assume the path without these eight loads, and on
-    // the path with them that count waits for all eight -- a full memory round trip exposed at the top of every chunk.
-    auto issue_patch = [&](int kc, bool live, auto set_c) __attribute__((always_inline)) {
-        constexpr int SET = decltype(set_c)::value;
-        int kcr = kc, sbase = 0;                           // chunk inside its term, byte offset of the term's part (scalar unit)
-        if constexpr (SPLIT) {
-            const int term = (int)udiv_magic((unsigned)kc, p.magicNK);
-            kcr = kc - term * p.nkc_real;
-            sbase = (int)((p.term_parts >> (4 * term)) & 15u) * p.part_bytes;
-        }
-        const int cbase = kcr * BK + cg * 8;
-        const int climit = live ? p.Cin : 0;              // one scalar select; `live && ...` per load comes back as branches
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            const unsigned off = (cbase + c < climit) ? pvoff : kOob;
-            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(xrs, off, sbase + (kcr * BK + c) * hw2, 0);
-            preg[SET][c][0] = v.x; preg[SET][c][1] = v.y;
-        }
-    };
-    // Branch-free on purpose: any branch here (even a wave-uniform one) cuts the tap loop into basic blocks, the ~60
-    // transpose instructions then run as one serial block with no MFMA in flight (measured: the register -> LDS transpose
-    // cost 38 % of the kernel that way).  Channels past Cin are zeroed by issue_patch; lanes outside the patch
-    // write to a sink; edge masks are applied unconditionally.
-    auto write_patch = [&](int kc, T* dstbuf, int bufbase, auto set_c) __attribute__((always_inline)) {
-        constexpr int SET = decltype(set_c)::value;
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            const unsigned lo = lshift ? 0u : (preg[SET][c][0] & pmask0);
-            const unsigned hi = (lshift ? preg[SET][c][0] : preg[SET][c][1]) & pmask1;
-            preg[SET][c][0] = lo; preg[SET][c][1] = hi;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const unsigned sel = (e & 1) ? 0x07060302u : 0x05040100u;
-            uint4 v;
-            v.x = __builtin_amdgcn_perm(preg[SET][1][e >> 1], preg[SET][0][e >> 1], sel);
-            v.y = __builtin_amdgcn_perm(preg[SET][3][e >> 1], preg[SET][2][e >> 1], sel);
-            v.z = __builtin_amdgcn_perm(preg[SET][5][e >> 1], preg[SET][4][e >> 1], sel);
-            v.w = __builtin_amdgcn_perm(preg[SET][7][e >> 1], preg[SET][6][e >> 1], sel);
-            *(uint4*)(lds + (pvalid ? bufbase + pdst + e * PITCH : 2 * kPatchMax * PITCH)) = v;
-        }
-    };
-
-    // Ring depth and patch sets.  vmcnt is ONE in-order counter: a wait for a weight fragment also waits for every load issued
-    // before it, so a patch request (an HBM round trip) stalls the first tap whose fragments were requested behind it -- with
-    // RING = 3 that is three taps after the request, whatever the distance to the transposing writes.  <RING = 9, NP = 2> (the
-    // 64-row blocks: 32 accumulator registers leave room): a chunk's fragments are all requested one chunk ahead and the patch of
-    // chunk k + 2 is requested at the top of chunk k into the second register set, so the fragments waited for during chunk k
-    // are all OLDER than that request and the patch has a whole chunk to arrive.
-    frag_t ar[RING][MI];
-    typedef std::integral_constant<int, 0> set0_t;
-    typedef std::integral_constant<int, NP - 1> set1_t;
-    issue_patch(0, true, set0_t{});
-#pragma unroll
-    for (int t = 0; t < RING; t++)
-#pragma unroll
-        for (int mi = 0; mi < MI; mi++) ar[t][mi] = load_a(0, t, mi);
-    if (NP == 2) issue_patch(p.nkc > 1 ? 1 : 0, p.nkc > 1, set1_t{});
-    // (tile-local pixel coordinates of this lane's four B fragments: computed under the first requests' round trip)
-    int bbase[4], pyv[4], pxv[4];
-#pragma unroll
-    for (int ti = 0; ti < 4; ti++) {
-        const int j = wpx * 128 + ti * 32 + r32;
-        int py = (int)__umulhi((unsigned)j, p.magicTW), px = j - py * p.TW;
-        const bool valid = j < p.TH * p.TW;
-        if (!valid) { py = 0; px = 0; }
-        pyv[ti] = valid ? y0 + py : p.P;             // invalid slots fall outside the image -> never stored
-        pxv[ti] = x0 + px;
-        bbase[ti] = (py * PWL + px + xoff) * PITCH + h * 8;
-    }
-
-    write_patch(0, lds, 0, set0_t{});
-    __syncthreads();
-    AFCM_STAMP(1);
-
-    const int last = p.nkc - 1;
-#ifdef AFCM_CONV_STAMPS
-    unsigned long long bar_cycles = 0;
-#endif
-    // one K-chunk; PAR = kc & 1 (NP = 2: the register set that takes the request of chunk kc + 2; the other one holds chunk kc + 1)
-    auto chunk = [&](int kc, auto par_c) __attribute__((always_inline)) {
-        constexpr int PAR = decltype(par_c)::value;
-        typedef std::integral_constant<int, NP == 2 ? PAR : 0> req_t;
-        typedef std::integral_constant<int, NP == 2 ? 1 - PAR : 0> wr_t;
-        const T* cur = lds + (kc & 1) * (kPatchMax * PITCH);
-        T* nxt = lds + ((kc + 1) & 1) * (kPatchMax * PITCH);
-        const bool more = kc < last;
-        // B fragments run one tap ahead of their MFMAs in the SAME registers: a tap's MFMAs go pixel-block by pixel-block, and
-        // as soon as block ti's fragment has been consumed the next tap's fragment for that block is read into it.  (Read, wait,
-        // multiply per tap left ~one LDS round trip exposed per 8 MFMAs with only the other workgroup's wave to cover it.)
-        frag_t b[BD][4];
-#pragma unroll
-        for (int d = 0; d < BD; d++)
-#pragma unroll
-            for (int ti = 0; ti < 4; ti++) b[d][ti] = *(const frag_t*)(cur + bbase[ti] + ((d / KS) * PWL + (d % KS)) * PITCH);
-        if (NP == 2) {
-            const bool more2 = kc + 2 <= last;
-            issue_patch(more2 ? kc + 2 : kc, more2, req_t{});
-        } else {
-            issue_patch(kc + (int)more, more, req_t{});
-        }
-        __builtin_amdgcn_sched_group_barrier(0x100, 4 * BD, 0);          // the first fragments first, all in flight together
-        __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);
-#pragma unroll
-        for (int tap = 0; tap < KK; tap++) {
-            const int nr = (tap + BD) / KS, ns = (tap + BD) - nr * KS;
-            const int tapoff_n = (nr * PWL + ns) * PITCH;                 // offset of the tap BD ahead (unused on the last BD taps)
-            frag_t a[MI];
-#pragma unroll
-            for (int mi = 0; mi < MI; mi++) a[mi] = ar[tap % RING][mi];
-            // refill this ring slot with the fragments RING taps ahead (clamped at the end: no branch around a load)
-            {
-                const int nt = (tap + RING) % KK;
-                const int nk = (tap + RING < KK) ? kc : (more ? kc + 1 : kc);
-#pragma unroll
-                for (int mi = 0; mi < MI; mi++) ar[tap % RING][mi] = load_a(nk, nt, mi);
-            }
-#pragma unroll
-            for (int ti = 0; ti < 4; ti++) {
-#pragma unroll
-                for (int mi = 0; mi < MI; mi++) {
-                    if constexpr (std::is_same<T, bf16_t>::value)
-                        acc[mi][ti] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi], b[tap % BD][ti], acc[mi][ti], 0, 0, 0);
-                    else
-                        acc[mi][ti] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi], b[tap % BD][ti], acc[mi][ti], 0, 0, 0);
-                }
-#ifdef AFCM_CONV_EXPERIMENT_HALFB      // timing experiment only (wrong results): every other tap keeps the previous tap's B fragments
-                if (tap + BD < KK && (tap & 1) == 0) b[tap % BD][ti] = *(const frag_t*)(cur + bbase[ti] + tapoff_n);
-#else
-                if (tap + BD < KK) b[tap % BD][ti] = *(const frag_t*)(cur + bbase[ti] + tapoff_n);
-#endif
-            }
-            if (tap == 5) {
-                // the other buffer (last read one chunk ago); on the last chunk this rewrites stale registers into a buffer
-                // nobody reads.  Interleave: one MFMA, then a handful of the transpose's vector instructions.
-                write_patch(kc + 1, nxt, ((kc + 1) & 1) * (kPatchMax * PITCH), wr_t{});
-                __builtin_amdgcn_sched_group_barrier(0x020, MI, 0);
-#pragma unroll
-                for (int ti = 0; ti < 4; ti++) {
-#pragma unroll
-                    for (int mi = 0; mi < MI; mi++) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
-            } else {
-                // pin the issue order of the tap: the ring refill first (left alone, the scheduler sinks the loads next to
-                // their uses and the prefetch distance collapses), then per pixel block its MFMAs and the read ahead
-                __builtin_amdgcn_sched_group_barrier(0x020, MI, 0);
-#pragma unroll
-                for (int ti = 0; ti < 4; ti++) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, MI, 0);
-                    if (tap + BD < KK) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-            }
-        }
-#ifdef AFCM_CONV_STAMPS
-        const unsigned long long tb0 = __builtin_readcyclecounter();
-        __syncthreads();
-        bar_cycles += __builtin_readcyclecounter() - tb0;
-#else
-        __syncthreads();
-#endif
-    };
-    if constexpr (NP == 2) {
-        for (int kc = 0; kc < p.nkc; kc += 2) {
-            chunk(kc, std::integral_constant<int, 0>{});
-            if (kc + 1 >= p.nkc) break;
-            chunk(kc + 1, std::integral_constant<int, 1>{});
-        }
-    } else {
-        for (int kc = 0; kc < p.nkc; kc++) chunk(kc, std::integral_constant<int, 0>{});
-    }
-
-    AFCM_STAMP(2);
-#ifdef AFCM_CONV_STAMPS
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 65536) afcm_conv_bar_buf[4 * blockIdx.x + (threadIdx.x >> 6)] = bar_cycles;
-#endif
-    // ---- epilogue: D[row = channel][col = pixel]; row = (reg&3) + 8*(reg>>2) + 4*h within the 32x32 tile.
-    if (!SPLIT && (p.TW & 7) == 0) {
-        // Tile rows that are multiples of 8 pixels: transpose through LDS (the patch buffers are free after the last barrier)
-        // and store 8 pixels = 16 bytes per lane.  A lane holds 16 channels of ONE pixel (4 runs of 4 consecutive channels), so
-        // it stages [pixel][32 channels] rows with four 8-byte writes per 32x32 tile, and the transposing read
-        // (ds_read_b64_tr_b16: a 16-lane group takes a 4-pixel x 16-channel block, lane i receives channel i of the 4 pixels)
-        // hands every lane 4 pixels of one channel.
-        // Row = 64 bytes = eight 8-byte chunks; chunk c of pixel p lives at c ^ ((p >> 1) & 7): conflict-free for the writes
-        // (16 consecutive pixels x one chunk) and for the reads (a 32-lane half = both channel halves of 4 pixels).
-        // r04: this block retired ~650 vector instructions per 32-row pass (PMC: 1324 per wave on a 64 -> 64 layer whose K loop
-        // needs 436) -- a min + sign-extend + 64-bit add in front of EVERY per-row scale / bias load (32 of them), the swizzled
-        // LDS address of every write, a 64-bit pointer and two predicates per store -- and the SIMD issues those at ~4.6 cycles
-        // each whatever the number of waves (tools/ubench/issue_mix.hip): on the 64-row layers the vector issue port, not the matrix
-        // pipe, was the limit.  Now everything position-dependent is an immediate offset or one of a few registers computed once:
-        // scales / biases come as 16-byte buffer loads (range-checked: rows past Cout read 0), the writes use four per-lane
-        // addresses + immediates, the stores are buffer stores whose byte offset is one add of two precomputed registers (an
-        // out-of-image granule or an out-of-range channel carries a marker that pushes the sum past the descriptor's range).
-        typedef __attribute__((ext_vector_type(4))) short s16x4;
-        typedef __attribute__((ext_vector_type(4))) float ef32x4;
-        typedef __attribute__((ext_vector_type(4))) unsigned eu32x4;
-        constexpr int EROW = 64;
-        unsigned char* const ebuf = (unsigned char*)lds + wave * (128 * EROW);
-        const int pq = p.P * p.ldy;
-        // output image n as one buffer (host: Cout * P * ldy * 2 bytes < 2^30, so the markers below cannot wrap back into range)
-        const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void*)((T*)p.y + (size_t)n * p.Cout * pq), 0, p.Cout * pq * 2, 0x00020000);
-        const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.oscale ? p.oscale + (size_t)n * p.Cout : (const float*)p.y), 0, p.oscale ? p.Cout * 4 : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.obias ? p.obias : (const float*)p.y), 0, p.obias ? p.Cout * 4 : 0, 0x00020000);
-        constexpr unsigned kGOut = 0x80000000u, kOOut = 0xc0000000u;
-        // per-row scales and biases of BOTH row passes first (rows of a lane's 16 accumulator registers: rowbase + 4 h + (reg & 3) +
-        // 8 (reg >> 2): four 16-byte loads each), so that the address arithmetic below runs under their round trip
-        const bool has_sc = p.oscale != nullptr, has_ob = p.obias != nullptr;
-        ef32x4 sc[MI][4], ob[MI][4];
-#pragma unroll
-        for (int mi = 0; mi < MI; mi++) {
-            const unsigned sboff = (unsigned)((o0 + wo * (BM_O / 2) + mi * 32 + 4 * h) * 4);
-#pragma unroll
-            for (int k4 = 0; k4 < 4; k4++) {
-                sc[mi][k4] = (ef32x4){1.f, 1.f, 1.f, 1.f};
-                ob[mi][k4] = (ef32x4){0.f, 0.f, 0.f, 0.f};
-            }
-            if (has_sc) {
-#pragma unroll
-                for (int k4 = 0; k4 < 4; k4++) sc[mi][k4] = __builtin_bit_cast(ef32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, sboff + 32u * k4, 0, 0));
-            }
-            if (has_ob) {
-#pragma unroll
-                for (int k4 = 0; k4 < 4; k4++) ob[mi][k4] = __builtin_bit_cast(ef32x4, __builtin_amdgcn_raw_buffer_load_b128(brs, sboff + 32u * k4, 0, 0));
-            }
-        }
-        // read side: lane = (half hh: granule parity, chalf: channel half, i16: channel / address role inside the 16-lane group)
-        const int i16 = lane & 15, chalf = (lane >> 4) & 1, hh = lane >> 5;
-        const int q4 = i16 >> 2, p4 = i16 & 3;
-        unsigned rd_off[2];
-#pragma unroll
-        for (int r = 0; r < 2; r++) {
-            const int prow = 8 * hh + 4 * r + q4;                 // + 16 pixels per iteration: (prow >> 1) & 7 does not change
-            rd_off[r] = prow * EROW + (((chalf * 4 + p4) ^ ((prow >> 1) & 7)) << 3);
-        }
-        // write side: pixel 32 ti + r32 (its swizzle (pix >> 1) & 7 does not depend on ti), chunks h + 2 k4
-        unsigned wr_off[4];
-#pragma unroll
-        for (int k4 = 0; k4 < 4; k4++) wr_off[k4] = (unsigned)(r32 * EROW + (((h + 2 * k4) ^ ((r32 >> 1) & 7)) << 3));
-        // this lane's 8 granules (8 pixels each, one tile row): byte offset inside a channel plane, or the marker; bit `it` of gfullm =
-        // the whole granule fits the row (a pitched row: up to the pitch, columns >= Q are padding)
-        unsigned gbyte[8], gfullm = 0;
-        int gxv[8];
-#pragma unroll
-        for (int it = 0; it < 8; it++) {
-            const int j0 = wpx * 128 + (2 * it + hh) * 8;
-            const int gpy = (int)__umulhi((unsigned)j0, p.magicTW), gpx = j0 - gpy * p.TW;
-            const int gy = y0 + gpy, gx = x0 + gpx;
-            gbyte[it] = (j0 < p.TH * p.TW && gy < p.P && gx < p.Q) ? (unsigned)((gy * p.ldy + gx) * 2) : kGOut;
-            gxv[it] = gx;
-            if (gx + 8 <= p.ldy) gfullm |= 1u << it;
-        }
-#pragma unroll
-        for (int mi = 0; mi < MI; mi++) {
-            const int rowbase = o0 + wo * (BM_O / 2) + mi * 32;
-#pragma unroll
-            for (int ti = 0; ti < 4; ti++) {
-#pragma unroll
-                for (int k4 = 0; k4 < 4; k4++) {                   // registers 4 k4 .. 4 k4 + 3 = channels 4 h + 8 k4 + 0..3
-                    uint2 w;
-                    w.x = pack2<T>(acc[mi][ti][4 * k4 + 0] * sc[mi][k4][0] + ob[mi][k4][0], acc[mi][ti][4 * k4 + 1] * sc[mi][k4][1] + ob[mi][k4][1]);
-                    w.y = pack2<T>(acc[mi][ti][4 * k4 + 2] * sc[mi][k4][2] + ob[mi][k4][2], acc[mi][ti][4 * k4 + 3] * sc[mi][k4][3] + ob[mi][k4][3]);
-                    *(uint2*)(ebuf + wr_off[k4] + ti * (32 * EROW)) = w;
-                }
-            }
-            // same wave wrote and reads: LDS operations of a wave complete in order, no barrier needed
-            const int o = rowbase + chalf * 16 + i16;
-            const unsigned obyte = o < p.Cout ? (unsigned)(o * pq * 2) : kOOut;
-#pragma unroll
-            for (int it = 0; it < 8; it++) {
-                union { s16x4 v[2]; eu32x4 q; } u;
-#pragma unroll
-                for (int r = 0; r < 2; r++)
-                    u.v[r] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ebuf + it * (16 * EROW) + rd_off[r]));
-                const unsigned off = obyte + gbyte[it];
-                if ((gfullm >> it) & 1) {
-                    __builtin_amdgcn_raw_buffer_store_b128(u.q, yrs, off, 0, 0);
-                } else {                                          // the granule straddles the right edge (even width: whole pairs)
-#pragma unroll
-                    for (int w2 = 0; w2 < 4; w2++)
-                        __builtin_amdgcn_raw_buffer_store_b32(u.q[w2], yrs, (gxv[it] + 2 * w2 < p.Q) ? off + 4u * w2 : kGOut, 0, 0);
-                }
-            }
-        }
-        AFCM_STAMP(3);
-        return;
-    }
-    TO* yn = (TO*)p.y + (size_t)n * p.Cout * p.P * p.ldy;
-    // per output-row block: all per-channel scales and biases first (clamped index, no branch around the loads: one wait
-    // instead of a round trip per row), then the stores
-    int poff[4];                                     // pixel offset inside a plane, -1: not stored
-#pragma unroll
-    for (int ti = 0; ti < 4; ti++) poff[ti] = (pyv[ti] < p.P && pxv[ti] < p.Q) ? pyv[ti] * p.ldy + pxv[ti] : -1;
-    const float* osn = p.oscale ? p.oscale + (size_t)n * p.Cout : nullptr;
-    const int pq = p.P * p.ldy;
-#pragma unroll
-    for (int mi = 0; mi < MI; mi++) {
-        float sc[16], ob[16];
-        const int obase = o0 + wo * (BM_O / 2) + mi * 32 + 4 * h;
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) { sc[reg] = 1.f; ob[reg] = 0.f; }
-        if (osn != nullptr) {
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) sc[reg] = osn[min(obase + (reg & 3) + 8 * (reg >> 2), p.Cout - 1)];
-        }
-        if (p.obias != nullptr) {
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) ob[reg] = p.obias[min(obase + (reg & 3) + 8 * (reg >> 2), p.Cout - 1)];
-        }
-        if constexpr (SPLIT) {
-            float ia = 1.f, ib = 1.f;
-            if (p.bound_a) pow2_factor(p.bound_a[0], &ia);
-            if (p.bound_b) pow2_factor(p.bound_b[0], &ib);
-            const float inv = ia * ib;
-#pragma unroll
-            for (int reg = 0; reg < 16; reg++) sc[reg] *= inv;
-        }
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const int o = obase + (reg & 3) + 8 * (reg >> 2);
-            if (o < p.Cout) {
-                TO* yo = yn + (size_t)o * pq;
-#pragma unroll
-                for (int ti = 0; ti < 4; ti++)
-                    if (poff[ti] >= 0) yo[poff[ti]] = from_f32<TO>(acc[mi][ti][reg] * sc[reg] + ob[reg]);
-            }
-        }
-    }
-    AFCM_STAMP(3);
-}
-
-// ---- r05: the same tile on v_mfma_f32_16x16x32 -------------------------------------------------------------------------------------
-// conv2d_fwd16_kernel's >= 256-channel layers hold ~1.5 GHz under their MFMA load (all-zero operands: +23 %, profiles/r04_power_probe.txt),
-// and on a clock-limited loop the chip holds a higher clock on the 16x16x32 shape than on 32x32x16 at equal cycles per flop
-// (MI355X_MICROARCH.md, DVFS give-back item 7).  Same workgroup tile (BM_O channels x 256 pixels), same wave tile ((BM_O / 2) x 128:
-// MO x 8 accumulator tiles of 16 x 16 = the same accumulator registers), same operand bytes per MFMA cycle; what changes:
+// Measured bounds of the r02 kernel (ablation builds, whole-generator conv bench, baseline 0.92 / 0.96 PF/s fwd / dgrad): weight
+// fragments served from L1 +2 %; no barrier +0 %; B fragments read once per chunk +5 %; patch written later in the chunk +0 %; the
+// four transposing ds_write_b128 removed (loads and permutes kept) +19 %; the whole activation path removed +38 %.  So the register
+// -> LDS transpose that NCHW forces is the limiter; LDS-DMA + ds_read_b64_tr_b16 cannot replace it because the transposing read
+// ignores the low three address bits (tools/ubench/tr_align_probe.hip) and the tap columns shift by 1 and 2 pixels.
+// r05 moved the tile to v_mfma_f32_16x16x32: the 32x32x16 kernel's >= 256-channel layers held ~1.5 GHz under their MFMA load (all-zero
+// operands: +23 %, profiles/r04_power_probe.txt), and on a clock-limited loop the chip holds a higher clock on the 16x16x32 shape than
+// on 32x32x16 at equal cycles per flop (MI355X_MICROARCH.md, DVFS give-back item 7).  Same accumulator registers, same operand bytes
+// per MFMA cycle; what changed:
 //   * a K step is 32 channels of one tap: K-chunks of 32 channels (packed weights [kc][tap][Opad][32], a lane's fragment = 16 bytes at
 //     row (lane & 15), channel group (lane >> 4); a wave still reads one contiguous 1 KB per fragment), half as many barriers;
 //   * the LDS patch is PLANAR: four planes [channel group of 8][pixel][8 channels], a pixel = 16 bytes, planes a multiple of 256 bytes
@@ -840,8 +379,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16_kernel(ConvParams p) {
 //     under tap 4, item 1 requested under tap 5 and written under tap 8.  Lanes 2, 3 (mod 4) of a group write their pixel pairs in
 //     swapped order (the permute's selector is a register): 2-way instead of 4-way conflicts on the transposing 16-byte writes;
 //   * the issue order is the source order: the loop is written as 72 steps (MO MFMAs, the read four steps ahead, a slice of the
-//     staging work) with a scheduling barrier after each.  Left to the scheduler (sched_group_barrier pipelines as in
-//     conv2d_fwd16_kernel) the MFMAs of different taps were reordered around the reads and every read was waited for at once.
+//     staging work) with a scheduling barrier after each.  Left to the scheduler (sched_group_barrier pipelines, as
+//     in the r02 kernel) the MFMAs of different taps were reordered around the reads and every read was waited for at once.
 // FASTEPI (r06): tiles whose width is a multiple of 16 pixels on rows whose pitch is a multiple of 8 elements (the 276^2 / 278^2 and 256^2
 // planes of the generator: 8 x 32 and 4 x 64 tiles on 288- and 256-element rows).  A 16-pixel block of the tile then lies in ONE tile row,
 // so the row and column base of its two 8-pixel granules are wave-uniform: they are computed on the scalar unit and ride in the store's
@@ -891,11 +430,12 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
     // hides: a new workgroup needed 7-15k cycles from its first instruction to its first barrier (its address set-up is issued
     // in the slots two MFMA-dense older waves leave, then a memory round trip: profiles/r05_conv_prologue_stamps.txt), a quarter of a
     // workgroup's life on the <= 128-channel layers.
-    // Only the 64-row kernel is persistent: carrying a second tile's staging state across the K loop costs the 128-row kernel, which
-    // sits at 250 of its 256 registers, 19-52 spilled registers in every form tried (its workgroups live 150-200k cycles, the prologue
-    // is 3 % of that); the 64-row kernel -- the <= 64-channel and the 181-channel layers, where the prologue is a quarter -- fits in the
-    // 168 registers of three waves per SIMD.  A non-persistent launch has one item per workgroup (the host sizes the grid accordingly).
-    constexpr bool PERSIST = BM_O == 64 || (BM_O == 96 && AFCM_CONV_BM96_PERSIST);
+    // The 128-row kernel is not persistent: carrying a second tile's staging state across the K loop costs it, at 250 of its 256
+    // registers, 19-52 spilled registers in every form tried (its workgroups live 150-200k cycles, the prologue is 3 % of that); the
+    // 64-row kernel -- the <= 64-channel and the 181-channel layers, where the prologue is a quarter -- fits in the 168 registers of
+    // three waves per SIMD; the 96-row kernel, at two per CU, in 228 registers without spills (3-7 % on the 91-row
+    // launches, profiles/r05_conv_bm96_ab.txt).  A non-persistent launch has one item per workgroup (the host sizes the grid accordingly).
+    constexpr bool PERSIST = BM_O == 64 || BM_O == 96;
     struct Tile { int y0, x0, n, o0; };
     auto decode = [&](int it) __attribute__((always_inline)) -> Tile {
         const int bid = xcd_order(it, p.total_blocks);
@@ -965,7 +505,9 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
         xrs = __builtin_amdgcn_make_buffer_rsrc((void*)((const T*)p.x + (size_t)t.n * p.Cin * p.H * p.ldx), 0, img_records, 0x00020000);
     };
 
-    // (branch-free, issued on every chunk -- past the last one of the last tile with the out-of-range offset: see conv2d_fwd16_kernel)
+    // Branch-free, and issued on EVERY chunk (past the last one of the last tile with the out-of-range offset: zeros, no memory
+    // traffic): a conditional issue makes the compiler's s_waitcnt for the weight ring assume the path without these loads, and on
+    // the path with them that count waits for all of them -- a full memory round trip exposed at the top of every chunk.
     auto issue_patch = [&](unsigned (&pr)[8][2], int kc, bool live, int item) __attribute__((always_inline)) {
         int kcr = kc, sbase = 0;                           // chunk inside its term, byte offset of the term's part (scalar unit)
         if constexpr (SPLIT) {
@@ -984,7 +526,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
             pr[c][0] = v.x; pr[c][1] = v.y;
         }
     };
-    // edge masks of one channel's two dwords (pixels 0, 1 | 2, 3): unconditional, as in conv2d_fwd16_kernel
+    // edge masks of one channel's two dwords (pixels 0, 1 | 2, 3): unconditional -- any branch here (even a wave-uniform one) cuts
+    // the tap loop into basic blocks, and the transpose then runs as one serial block with no MFMA in flight
     auto mask_ch = [&](unsigned (&pr)[8][2], int c) __attribute__((always_inline)) {
         const unsigned lo = pr[c][0] & pm_lo;
         const unsigned hi = (lshift ? pr[c][0] : pr[c][1]) & pm_hi;
@@ -1033,7 +576,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
     // ---- the first tile of this workgroup: the one exposed prologue
     int item = blockIdx.x;
     Tile S = decode(item);
-    AFCM_STAMP_I(0, item);
     stage_tile(S);
     frag_t ar[ARING];
     unsigned preg[8][2];
@@ -1043,18 +585,14 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
         issue_patch(preg1, 0, true, 1);
 #pragma unroll
         for (int q = 0; q < ARING; q++) ar[q] = load_a(S.o0, 0, q / MO, q % MO);
-        AFCM_STAMP_P(0);
-        AFCM_STAMP_P(1);
 #pragma unroll
         for (int c = 0; c < 8; c++) { mask_ch(preg, c); mask_ch(preg1, c); }
 #pragma unroll
         for (int e = 0; e < 4; e++) { write_px(preg, e, 0); write_px(preg1, e, 2 * PLANE_B); }
-        AFCM_STAMP_P(2);
     }
     int cb = 0;                                              // buffer of the chunk under way
     set_bbyte(S, cb);
     __syncthreads();
-    AFCM_STAMP_I(1, item);
 
     const int last = p.nkc - 1;
     const unsigned rowstep = (unsigned)(PWL * 16);
@@ -1123,7 +661,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
             cb ^= 1;
             __syncthreads();
         }
-        AFCM_STAMP_I(2, item);
         // ---- epilogue of tile S: a 16 x 16 tile has its pixel on the lane (col = lane & 15) and channels 4 g .. 4 g + 3 in the 4 registers
         // (the lane id goes through an empty asm: otherwise pixel coordinates computed for the K loop are kept -- spilled -- for the stores
         // below instead of being recomputed)
@@ -1133,7 +670,7 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
         const int c16e = lane_e & 15, ge = lane_e >> 4;
         const int y0 = S.y0, x0 = S.x0, n = S.n, o0 = S.o0;
         if constexpr (!SPLIT) {
-            // as conv2d_fwd16_kernel: per 32-channel pass stage [pixel][32 channels] rows (64 bytes, 8-byte chunk c of pixel p at
+            // per 32-channel pass stage [pixel][32 channels] rows (64 bytes, 8-byte chunk c of pixel p at
             // c ^ ((p >> 1) & 7)) and read them back transposed; here a lane stages ONE 8-byte chunk per tile (channels 16 (mo & 1) + 4 g ..),
             // 64 pixels at a time: the staging area (4 KB per wave) lies in the patch buffer the last chunk read -- the other one already
             // holds the next tile's first chunk.
@@ -1286,20 +823,17 @@ __global__ __launch_bounds__(256, 2) void conv2d_fwd16x_kernel(ConvParams p) {
                 }
             }
         }
-        AFCM_STAMP_I(3, item);
         if (!has_next) break;
         // the staging area of the epilogue (the buffer the last chunk read) is the one the next tile's first chunk stages INTO
         if (!SPLIT) __syncthreads();
         S = decode(item_n);
         item = item_n;
         set_bbyte(S, cb);
-        AFCM_STAMP_I(0, item);
-        AFCM_STAMP_I(1, item);
     }
 }
 
-// Stride-2 form of conv2d_fwd16_kernel for the discriminator's down-sampling convs (CoModGAN/generator.py:613-692: blur, then a 3x3
-// conv at stride 2): the r01/r02 route computed the stride-1 result and decimated it -- four times the MFMAs, a full-resolution
+// Stride-2 3x3 kernel (the r02 structure: 32x32x16 MFMAs, K-chunks of 16 channels) for the discriminator's down-sampling convs
+// (CoModGAN/generator.py:613-692: blur, then a 3x3 conv at stride 2): the r01/r02 route computed the stride-1 result and decimated it -- four times the MFMAs, a full-resolution
 // write and a decimation copy.  Here an output pixel (py, px) reads the patch at (2 py + r, 2 px + s): same packed weights, same
 // tap loop, B fragment addresses twice as far apart.  The patch of a tile is ~4x its outputs, so a workgroup takes 128 output
 // pixels (two 32-pixel blocks per wave) under a (2 TH + 1) x (2 TW + 2) patch of up to kPatchMaxS2 pixels (two staging items per
@@ -2803,21 +2337,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_wgrad16_kernel(WgradParams p) {
 // rebuilds a 128-bit descriptor per piece -- 64-bit base, exact record count, validity select, three v_readfirstlane --
 // ~45 scalar instructions per piece, 310 per K step of 36 MFMAs: the wave's own instruction stream, not the matrix pipe, set
 // the step time (PMC r01e: MFMA pipe 49 % busy, 8.7 SALU per MFMA).
-#ifndef AFCM_CONV_BM96
-#define AFCM_CONV_BM96 1           // 65 .. 96 output rows on one 96-row block of conv2d_fwd16x_kernel (0: a 128-row block; A/B builds)
-#endif
-#ifndef AFCM_CONV_BM96_192
-#define AFCM_CONV_BM96_192 0       // experiment: 129 .. 192 rows as two 96-row blocks instead of 128 + 64 (measured: the same, profiles/r05_conv_bm96_ab.txt)
-#endif
-#ifndef AFCM_CONV_MIXED
-#define AFCM_CONV_MIXED 1          // 128 k + (1 .. 64) output rows: 128-row kernel + one 64-row block (0: 64-row blocks only; A/B builds)
-#endif
-#ifndef AFCM_WGRAD_LATE
-#define AFCM_WGRAD_LATE 1          // begin_loads behind the first iteration's MFMAs: 8.55 -> 8.28 ms in the step (profiles/r05_wgrad_late_ab.txt); 0: at the step's top
-#endif
-#ifndef AFCM_WGRAD_NBUF
-#define AFCM_WGRAD_NBUF 3          // LDS ring depth of conv2d_wgrad16g_kernel (2: measured in profiles/r04_wgrad_ring.txt)
-#endif
+constexpr int kWgradRing = 3;      // LDS ring depth of conv2d_wgrad16g_kernel (2: measured in profiles/r04_wgrad_ring.txt)
 // X16 (r05): the same tile on v_mfma_f32_16x16x32 -- a wave's 32 (o) x 32 (i) tile is 2 x 2 tiles of 16 x 16 per tap (the same 144
 // accumulator registers), a K step is 32 pixels = FOUR granules, one per 16-lane group: wave th takes pixels 32 th .. 32 th + 31 of the
 // chunk.  ds_read_b128 serves the lanes in groups that hold all 16 rows with TWO neighbouring granules (G, G + 1), so the swizzle is
@@ -2961,12 +2481,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_wgrad16g_kernel(WgradParams p) 
                 constexpr int xr = I - R;
                 const int row = c_prow0 - p.pad + xr;
                 const unsigned soff = c_x32 + (unsigned)(row * Ws + c_q0 - XLEAD) * 2u;
-#ifdef AFCM_WGRAD_EXPERIMENT_HALFX      // timing experiment only (wrong results): the two x rows shared with the previous row pair are not requested.
-                                        // CAUTION: its -8 % is the clock, not the bytes -- the rows then multiply zeros (profiles/r04_wgrad_ring.txt)
-                const unsigned sinv = ((unsigned)row < (unsigned)p.H && c_live && xr >= 2) ? 0u : kOob;
-#else
                 const unsigned sinv = ((unsigned)row < (unsigned)p.H && c_live) ? 0u : kOob;
-#endif
                 lds_dma_b128(rs_x, ((v_x & ~kOob) + soff) | (v_x & kOob) | sinv, lds0 + c_bufa + DY_BYTES + xr * (64 * ROWB) + wave * 1024);
             } else {
                 const int row = c_prow0 - p.pad;                                 // lanes add their xr
@@ -3033,9 +2548,6 @@ __global__ __launch_bounds__(512, 1) void conv2d_wgrad16g_kernel(WgradParams p) 
                                          : DY_BYTES + XMAIN + (rb >> 3) * (XR * 128) + xr * 128 + (rb & 7) * 16;
     }
 
-#ifdef AFCM_WGRAD_PRIO           // A/B builds: static priority for one half of the workgroup's waves (MI355X_MICROARCH.md, two waves per SIMD, item 4): 1 = waves 4-7, 2 = waves 0-3
-    if ((AFCM_WGRAD_PRIO == 1) == (wave >= 4)) __builtin_amdgcn_s_setprio(1);
-#endif
     // ---- pipeline: NBUF-1 steps of loads in flight; a step's loads are waited for (counted vmcnt) before the barrier that
     // precedes its use.
 #pragma unroll
@@ -3055,8 +2567,9 @@ __global__ __launch_bounds__(512, 1) void conv2d_wgrad16g_kernel(WgradParams p) 
     int cbuf = 0;
     for (int step = s0; step < s1; step++) {
         // LATE (16x16x32, 3x3): the live waves run begin_loads' ~50 scalar / vector instructions after their first iteration's MFMAs
-        // instead of between the barrier and the first MFMA of all eight waves at once (their pieces then go out in iterations 1 .. 7)
-        constexpr bool LATE = X16 && TAIL && AFCM_WGRAD_LATE;
+        // instead of between the barrier and the first MFMA of all eight waves at once (their pieces then go out in iterations 1 .. 7):
+        // 8.55 -> 8.28 ms in the step (profiles/r05_wgrad_late_ab.txt)
+        constexpr bool LATE = X16 && TAIL;
         if constexpr (!LATE) begin_loads(step + NBUF - 1 < s1);                 // into the buffer everyone left at the last barrier
         const char* buf = lds + cbuf * BUF;
         typedef typename std::conditional<std::is_same<T, bf16_t>::value, bf16x8, f16x8>::type frag_t;
@@ -3146,11 +2659,7 @@ __global__ __launch_bounds__(512, 1) void conv2d_wgrad16g_kernel(WgradParams p) 
                         union { unsigned u[4]; frag_t f; } bw;
 #pragma unroll
                         for (int w = 0; w < 4; w++)
-#ifdef AFCM_WGRAD_EXPERIMENT_NOSHIFT    // timing experiment only (wrong results): 1 = no funnel shifts for the middle tap column, 2 = no register copies for the first either
-                            bw.u[w] = (sft == 0 && AFCM_WGRAD_EXPERIMENT_NOSHIFT < 2) ? d[w] : d[w + 1];
-#else
                             bw.u[w] = (sft == 0) ? d[w] : (sft == 1) ? __builtin_amdgcn_alignbyte(d[w + 1], d[w], 2) : d[w + 1];
-#endif
 #pragma unroll
                         for (int rr = 0; rr < R; rr++) {
                             const int r = xr - rr;
@@ -3462,19 +2971,13 @@ static int conv_persistent_grid(long long items, int per_cu) {
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         if (dev >= 0 && dev < 16) cus[dev] = n;
     }
-#ifdef AFCM_CONV_AB
-    if (g_conv_x16 >> 4) per_cu = g_conv_x16 >> 4;         // experiment: workgroups per CU of the persistent grid from the debug switch
-#endif
     const long long slots = (long long)round_up(n * per_cu, 8);
     return (int)(items < slots ? items : slots);
 }
 
 // conv2d_fwd16x_kernel<.., FASTEPI>: tile widths that are multiples of 16 on output rows whose pitch is a multiple of 8 elements
-#ifndef AFCM_CONV_FASTEPI
-#define AFCM_CONV_FASTEPI 1          // (0: the general epilogue everywhere; A/B builds)
-#endif
 static bool conv_fast_epilogue(const ConvParams& p) {
-    return AFCM_CONV_FASTEPI && (p.TW & 15) == 0 && (p.ldy & 7) == 0 && (p.Q & 1) == 0;
+    return (p.TW & 15) == 0 && (p.ldy & 7) == 0 && (p.Q & 1) == 0;
 }
 
 // o_base / row_blocks: the launch covers output rows [o_base, o_base + row_blocks * BM_O) (16-bit 3x3 16x16x32 kernel only; 0: all rows)
@@ -3487,18 +2990,10 @@ static int launch_conv(ConvParams p, int ks, hipStream_t st, int o_base = 0, int
     p.total_blocks = (int)blocks;
     if constexpr (sizeof(T) == 2) {
         if (ks == 3) {
-#if defined(AFCM_CONV_AB) || AFCM_CONV_X16
-            if (AFCM_X16_ON) {
-                // (the 64-row kernel is persistent: one round of three workgroups per CU; the 128-row kernel takes one item per workgroup)
-                const dim3 g16 = BM_O == 64 ? dim3((unsigned)conv_persistent_grid(blocks, 3)) : grid;
-                if (conv_fast_epilogue(p)) hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, false, true>), g16, block, 0, st, p);
-                else hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O>), g16, block, 0, st, p);
-                return hip_status(hipGetLastError());
-            }
-#endif
-#if defined(AFCM_CONV_AB) || !AFCM_CONV_X16
-            hipLaunchKernelGGL((conv2d_fwd16_kernel<T, BM_O>), grid, block, 0, st, p);
-#endif
+            // (the 64-row kernel is persistent: one round of three workgroups per CU; the 128-row kernel takes one item per workgroup)
+            const dim3 g16 = BM_O == 64 ? dim3((unsigned)conv_persistent_grid(blocks, 3)) : grid;
+            if (conv_fast_epilogue(p)) hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, false, true>), g16, block, 0, st, p);
+            else hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O>), g16, block, 0, st, p);
             return hip_status(hipGetLastError());
         }
     }
@@ -3511,34 +3006,9 @@ static int launch_conv(ConvParams p, int ks, hipStream_t st, int o_base = 0, int
 
 using namespace afcm;
 
-#ifdef AFCM_CONV_STAMPS
-extern "C" int afcm_debug_conv_stamps(void* dst, int n_blocks) {
-    return hip_status(hipMemcpyFromSymbol(dst, HIP_SYMBOL(afcm_conv_stamps_buf), (size_t)n_blocks * 32, 0, hipMemcpyDeviceToHost));
-}
-extern "C" int afcm_debug_conv_realtime(void* dst, int n_blocks) {
-    return hip_status(hipMemcpyFromSymbol(dst, HIP_SYMBOL(afcm_conv_rt_buf), (size_t)n_blocks * 32, 0, hipMemcpyDeviceToHost));
-}
-extern "C" int afcm_debug_conv_prologue(void* dst, int n_blocks) {
-    return hip_status(hipMemcpyFromSymbol(dst, HIP_SYMBOL(afcm_conv_pro_buf), (size_t)n_blocks * 32, 0, hipMemcpyDeviceToHost));
-}
-extern "C" int afcm_debug_conv_barrier_cycles(void* dst, int n_blocks) {
-    return hip_status(hipMemcpyFromSymbol(dst, HIP_SYMBOL(afcm_conv_bar_buf), (size_t)n_blocks * 32, 0, hipMemcpyDeviceToHost));
-}
-extern "C" int afcm_debug_conv_stamps_clear() {
-    void* a; void* b;
-    if (hipGetSymbolAddress(&a, HIP_SYMBOL(afcm_conv_stamps_buf)) != hipSuccess || hipGetSymbolAddress(&b, HIP_SYMBOL(afcm_conv_bar_buf)) != hipSuccess) return AFCM_E_INVALID;
-    (void)hipMemset(a, 0, sizeof(afcm_conv_stamps_buf));
-    void* c;
-    if (hipGetSymbolAddress(&c, HIP_SYMBOL(afcm_conv_pro_buf)) == hipSuccess) (void)hipMemset(c, 0, sizeof(afcm_conv_pro_buf));
-    return hip_status(hipMemset(b, 0, sizeof(afcm_conv_bar_buf)));
-}
-#endif
 extern "C" int afcm_conv2d_block_k(int32_t dtype) { return dtype == AFCM_F32 ? ConvCfg<float>::BK : ConvCfg<bf16_t>::BK; }
-static inline int afcm::conv_bk(int dtype, int ks) { return (dtype != AFCM_F32 && ks == 3 && AFCM_X16_ON) ? 32 : afcm_conv2d_block_k(dtype); }
+static inline int afcm::conv_bk(int dtype, int ks) { return (dtype != AFCM_F32 && ks == 3) ? 32 : afcm_conv2d_block_k(dtype); }
 extern "C" int afcm_conv2d_block_k_ks(int32_t dtype, int32_t ks) { return conv_bk(dtype, ks); }
-#ifdef AFCM_CONV_AB
-extern "C" int afcm_debug_conv_variant(int x16) { g_conv_x16 = x16; return AFCM_OK; }
-#endif
 
 template <typename T>
 static void launch_pack8(void* dst0, void* dst1, const float* w, int cout, int cin, int ks, int rows_pad0, int rows_pad1, int BK, hipStream_t st) {
@@ -3701,11 +3171,11 @@ extern "C" int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const
         AFCM_REQUIRE((long long)cout * p.P * p.ldy < (1ll << 30), "conv2d: pitched output image is out of range");
     }
     AFCM_REQUIRE(dtype == AFCM_F32 || ks != 3 || (long long)cout * p.P * p.ldy * 2 < (1ll << 30), "conv2d: 16-bit output image of %lld bytes is out of range (< 2^30)", (long long)cout * p.P * p.ldy * 2);
-    if (AFCM_CONV_DIRECT4 && dtype != AFCM_F32 && ks == 3 && cin <= 4 && cout <= 64 && conv_bk(dtype, ks) == 32) {
+    if (dtype != AFCM_F32 && ks == 3 && cin <= 4 && cout <= 64) {
         // a handful of input channels: the contraction index is (tap column, channel), no channel padding (conv2d_direct.hip; r06)
         return conv2d_direct_small_cin(x, y, wpacked, oscale, obias, dtype, n, cin, cout, h, w, pad, rows_pad, 32, p.ldx, p.ldy, (hipStream_t)stream);
     }
-    choose_tile(p.P, p.Q, ks, &p.TH, &p.TW, &p.PWL, (dtype != AFCM_F32 && ks == 3 && AFCM_X16_ON) ? kPatchMaxX16 : kPatchMax);
+    choose_tile(p.P, p.Q, ks, &p.TH, &p.TW, &p.PWL, (dtype != AFCM_F32 && ks == 3) ? kPatchMaxX16 : kPatchMax);
     p.tilesX = cdiv(p.Q, p.TW); p.tilesY = cdiv(p.P, p.TH);
     p.magicTW = (unsigned)((0x100000000ull + (unsigned)p.TW - 1) / (unsigned)p.TW);
     p.magicTX = magic_u32((unsigned)p.tilesX); p.magicTY = magic_u32((unsigned)p.tilesY); p.magicN = magic_u32((unsigned)p.N); p.magicPC = magic_u32((unsigned)(p.PWL >> 2));
@@ -3718,12 +3188,13 @@ extern "C" int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const
     // ... and both when the rows are 128 k + (1 .. 64) (the 181-channel layers: 192 padded rows): the 128-row kernel moves half the
     // pixel-fragment bytes per flop of the 64-row one, so rows [0, 128 k) go to it and only the last 64 to the 64-row kernel -- two
     // launches, disjoint output rows, the same number of passes over x as three 64-row blocks had
-    if (AFCM_CONV_BM96 && AFCM_X16_ON && dtype != AFCM_F32 && ks == 3 && ((cout > 64 && cout <= 96) || (AFCM_CONV_BM96_192 && cout > 128 && cout <= 192 && rows_pad >= 192))) {
-        // 65 .. 96 output rows (the 91-channel layers): one 96-row block instead of 128 rows of MFMAs for them
+    if (dtype != AFCM_F32 && ks == 3 && cout > 64 && cout <= 96) {
+        // 65 .. 96 output rows (the 91-channel layers): one 96-row block instead of 128 rows of MFMAs for them.  (129 .. 192 rows as two
+        // 96-row blocks instead of 128 + 64 measured the same: profiles/r05_conv_bm96_ab.txt)
         const long long blocks = (long long)p.tilesX * p.tilesY * p.N * cdiv(cout, 96);
         AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d: grid of %lld blocks is out of range", blocks);
         p.total_blocks = (int)blocks; p.o_base = 0;
-        const dim3 g96((unsigned)(AFCM_CONV_BM96_PERSIST ? conv_persistent_grid(blocks, 2) : blocks));
+        const dim3 g96((unsigned)conv_persistent_grid(blocks, 2));
         if (conv_fast_epilogue(p)) {
             if (dtype == AFCM_F16) hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 96, false, true>), g96, dim3(256), 0, st, p);
             else hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 96, false, true>), g96, dim3(256), 0, st, p);
@@ -3731,7 +3202,7 @@ extern "C" int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const
         else hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 96>), g96, dim3(256), 0, st, p);
         return hip_status(hipGetLastError());
     }
-    if (AFCM_CONV_MIXED && AFCM_X16_ON && dtype != AFCM_F32 && ks == 3 && rows_pad % 128 == 64 && rows_pad > 128) {
+    if (dtype != AFCM_F32 && ks == 3 && rows_pad % 128 == 64 && rows_pad > 128) {
         const int big = rows_pad / 128;
         const int rc = dtype == AFCM_F16 ? launch_conv<f16_t, 128>(p, ks, st, 0, big) : launch_conv<bf16_t, 128>(p, ks, st, 0, big);
         if (rc != AFCM_OK) return rc;
@@ -3836,7 +3307,7 @@ extern "C" int afcm_conv2d_split(float* y, const void* x_parts, const void* wpac
     AFCM_REQUIRE(p.P >= 1 && p.Q >= 1, "output must be at least 1x1");
     p.pad = pad;
     p.ldx = w; p.ldy = p.Q;
-    choose_tile(p.P, p.Q, ks, &p.TH, &p.TW, &p.PWL, AFCM_X16_ON ? kPatchMaxX16 : kPatchMax);
+    choose_tile(p.P, p.Q, ks, &p.TH, &p.TW, &p.PWL, kPatchMaxX16);
     p.tilesX = cdiv(p.Q, p.TW); p.tilesY = cdiv(p.P, p.TH);
     p.magicTW = (unsigned)((0x100000000ull + (unsigned)p.TW - 1) / (unsigned)p.TW);
     p.magicTX = magic_u32((unsigned)p.tilesX); p.magicTY = magic_u32((unsigned)p.tilesY); p.magicN = magic_u32((unsigned)p.N); p.magicPC = magic_u32((unsigned)(p.PWL >> 2));
@@ -3851,31 +3322,17 @@ extern "C" int afcm_conv2d_split(float* y, const void* x_parts, const void* wpac
     const bool small = (rows_pad % 128 != 0) || cout <= 64;
     const long long blocks = (long long)p.tilesX * p.tilesY * p.N * cdiv(p.Cout, small ? 64 : 128);
     AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d_split: grid of %lld blocks is out of range", blocks);
-    dim3 grid((unsigned)blocks), block(256);
+    const dim3 block(256);
     hipStream_t st = (hipStream_t)stream;
-#if defined(AFCM_CONV_AB) || AFCM_CONV_X16
-    if (AFCM_X16_ON) {
-        p.total_blocks = (int)blocks; p.o_base = 0;
-        const dim3 pgrid(small ? (unsigned)conv_persistent_grid(blocks, 3) : (unsigned)blocks);
-        if (dtype == AFCM_BF16) {
-            if (small) hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 64, true>), pgrid, block, 0, st, p);
-            else hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 128, true>), pgrid, block, 0, st, p);
-        } else {
-            if (small) hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 64, true>), pgrid, block, 0, st, p);
-            else hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 128, true>), pgrid, block, 0, st, p);
-        }
-        return hip_status(hipGetLastError());
-    }
-#endif
-#if defined(AFCM_CONV_AB) || !AFCM_CONV_X16
+    p.total_blocks = (int)blocks; p.o_base = 0;
+    const dim3 pgrid(small ? (unsigned)conv_persistent_grid(blocks, 3) : (unsigned)blocks);
     if (dtype == AFCM_BF16) {
-        if (small) hipLaunchKernelGGL((conv2d_fwd16_kernel<bf16_t, 64, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv2d_fwd16_kernel<bf16_t, 128, true>), grid, block, 0, st, p);
+        if (small) hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 64, true>), pgrid, block, 0, st, p);
+        else hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 128, true>), pgrid, block, 0, st, p);
     } else {
-        if (small) hipLaunchKernelGGL((conv2d_fwd16_kernel<f16_t, 64, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv2d_fwd16_kernel<f16_t, 128, true>), grid, block, 0, st, p);
+        if (small) hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 64, true>), pgrid, block, 0, st, p);
+        else hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 128, true>), pgrid, block, 0, st, p);
     }
-#endif
     return hip_status(hipGetLastError());
 }
 
@@ -3885,38 +3342,21 @@ static int wgrad_rows_per_step(int dtype) { return dtype == AFCM_F32 ? 1 : 2; }
 // Workgroups per 64 x 64 tile.  One workgroup per CU is resident (LDS ring), so aim for ONE full round of the 256 CUs and never one
 // workgroup more: rounding up (258 workgroups = two rounds) halves the throughput, and every extra split costs a 36 x 64 x 64 x 4 B
 // partial tile written and read back (at 768 workgroups the partials of a 64 -> 64 layer were 2/3 of its time).
-// two_class (conv2d_wgrad16g_kernel): tiles whose last 32 rows or columns lie outside the matrix (WgradParams::fo / fi) run their steps
-// at ~0.6 of a full tile's cost (one live wave per SIMD: 1152 MFMA cycles + the ~600 of barrier and bookkeeping, against 2304 + 600),
-// so they get 0.6 of a full tile's workgroups -- the round stays one round and every workgroup ends at about the same time.
-// MEASURED (profiles/r05_wgrad_partial_tiles.txt): the skipped quadrants alone are worth 3-6 % on the 91-channel layers (L11 0.33 -> 0.31 ms)
-// with the same number of workgroups per tile; the two-class plan on top made them SLOWER (L11 0.31 -> 0.36): a lone wave per SIMD cannot
-// hide its own LDS latency, a step costs a partial tile nearer 0.8 than 0.6 of a full one.  Off; the plan and the reduce kernels keep the
-// machinery (tests/test_gpu_conv.py ran green with it on).
-#ifndef AFCM_WGRAD_TWO_CLASS
-#define AFCM_WGRAD_TWO_CLASS 0
-#endif
-static void wgrad_plan(int n, int cout, int cin, int p_rows, bool two_class, int* fo, int* fi, int* splits, int* splits_p) {
-    const int to = cdiv(cout, 64), ti = cdiv(cin, 64), tiles = to * ti;
+// Every tile gets the same count.  (Tiles whose last 32 rows or columns lie outside the matrix skip those quadrants: 3-6 % on the
+// 91-channel layers, L11 0.33 -> 0.31 ms.  A two-class plan that gave them 0.6 of a full tile's workgroups on top made those layers
+// SLOWER, L11 0.31 -> 0.36: a lone wave per SIMD cannot hide its own LDS latency, a step costs a partial tile nearer 0.8 than 0.6 of a
+// full one -- profiles/r05_wgrad_partial_tiles.txt.  The kernel and the reduce kernels keep the two-class machinery, WgradParams::fo /
+// fi / splits_p.)
+static int wgrad_splits(int n, int cout, int cin, int p_rows) {
+    const int tiles = cdiv(cout, 64) * cdiv(cin, 64);
     const long long ksteps = (long long)n * p_rows;   // upper bound on the macro-steps of any dtype
-    auto clampk = [&](int v) { if (v > ksteps) v = (int)ksteps; return v < 1 ? 1 : v; };
-    *fo = to; *fi = ti;
-    *splits = *splits_p = clampk(256 / tiles);
-    if (!two_class || !AFCM_WGRAD_TWO_CLASS) return;
-    const int f_o = cout - (to - 1) * 64 <= 32 ? to - 1 : to, f_i = cin - (ti - 1) * 64 <= 32 ? ti - 1 : ti;
-    const int nf = f_o * f_i, np = tiles - nf;
-    if (nf == 0 || np == 0) return;                   // one class only
-    int sf = (int)(256 / (nf + 0.6 * np)), sp = (256 - nf * sf) / np;
-    if (sp < 1) { sp = 1; sf = (256 - np) / nf; }
-    if (sf < 1) return;
-    *fo = f_o; *fi = f_i; *splits = clampk(sf); *splits_p = clampk(sp);
+    int s = 256 / tiles;
+    if (s > ksteps) s = (int)ksteps;
+    return s < 1 ? 1 : s;
 }
 
 extern "C" int afcm_conv2d_wgrad_splits(int32_t n, int32_t cout, int32_t cin, int32_t p_rows) {
-    // slabs of the workspace: the most any tile of any kernel writes
-    int fo, fi, s0, s0p, s1, s1p;
-    wgrad_plan(n, cout, cin, p_rows, false, &fo, &fi, &s0, &s0p);
-    wgrad_plan(n, cout, cin, p_rows, true, &fo, &fi, &s1, &s1p);
-    return s0 > s1 ? s0 : s1;
+    return wgrad_splits(n, cout, cin, p_rows);   // slabs of the workspace: the most any tile writes
 }
 
 extern "C" int afcm_conv2d_wgrad(float* dw, float* workspace, const void* dy, const void* x, int32_t dtype, int32_t n, int32_t cin,
@@ -3944,17 +3384,18 @@ static int wgrad_impl(float* dw, float* workspace, const void* dy, const void* x
     p.rowgroups = cdiv(p.P, R);
     const long long ksteps = (long long)n * p.rowgroups * p.qchunks;
     const bool granule = (ks == 3 && pad == 2) || (ks == 1 && pad == 0);     // 16-byte LDS-DMA pieces; other paddings: 4-byte pieces
-    wgrad_plan(n, cout, cin, p.P, dtype != AFCM_F32 && granule, &p.fo, &p.fi, &p.splits, &p.splits_p);
+    p.fo = cdiv(cout, 64); p.fi = cdiv(cin, 64);                             // one tile class: every tile is full
+    p.splits = p.splits_p = wgrad_splits(n, cout, cin, p.P);
     if (p.splits > ksteps) p.splits = (int)ksteps;
     if (p.splits_p > ksteps) p.splits_p = (int)ksteps;
     p.steps_per_split = (int)((ksteps + p.splits - 1) / p.splits);
     p.steps_per_split_p = (int)((ksteps + p.splits_p - 1) / p.splits_p);
     p.splits_img = 0;
     if (dots != nullptr) {
-        // image-aligned shares: the same number of workgroups, each inside one image (the granule kernel, one tile class, a split count that
-        // is a multiple of the batch, at most 64 images: what wgrad_reduce_dots_kernel covers) -- else the caller takes its dot products
+        // image-aligned shares: the same number of workgroups, each inside one image (the granule kernel, a split count that is a
+        // multiple of the batch, at most 64 images: what wgrad_reduce_dots_kernel covers) -- else the caller takes its dot products
         // from the tensors themselves
-        if (!(dtype != AFCM_F32 && granule) || p.splits != p.splits_p || n > 64 || p.splits % n != 0 || p.splits / n < 1) return AFCM_E_NOKERNEL;
+        if (!(dtype != AFCM_F32 && granule) || n > 64 || p.splits % n != 0 || p.splits / n < 1) return AFCM_E_NOKERNEL;
         AFCM_REQUIRE(wref != nullptr, "conv2d_wgrad_dots: the weight tensor the dot products are taken with is missing");
         p.splits_img = p.splits / n;
         const long long per_img = (long long)p.rowgroups * p.qchunks;
@@ -3971,7 +3412,7 @@ static int wgrad_impl(float* dw, float* workspace, const void* dy, const void* x
                            if (ks == 3 && (pad & 1) == 0) hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 3, 0, NB>), grid, block, 0, st, p); \
                            else if (ks == 3) hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 3, 1, NB>), grid, block, 0, st, p); \
                            else hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 1, 0, NB>), grid, block, 0, st, p); } while (0)
-#define AFCM_WG16G_(T, X) do { constexpr int NB = AFCM_WGRAD_NBUF; \
+#define AFCM_WG16G_(T, X) do { constexpr int NB = kWgradRing; \
                             if (small && ks == 3) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 3, NB, true, X>), grid, block, 0, st, p); \
                             else if (small) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 1, NB, true, X>), grid, block, 0, st, p); \
                             else if (ks == 3) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 3, NB, false, X>), grid, block, 0, st, p); \
@@ -3980,7 +3421,7 @@ static int wgrad_impl(float* dw, float* workspace, const void* dy, const void* x
     // step is 32 pixels where the 32x32x16 form skips dead 16-pixel groups: rows whose last 64-pixel chunk holds 33 .. 48 pixels (the 38-wide
     // planes of the 36^2 layers) cost it a whole extra step (-12 % there) -- those keep the 32x32x16 form.
     const int q_last = p.Q % 64;
-    const bool wg_x16 = AFCM_X16_ON && !(q_last > 32 && q_last <= 48);
+    const bool wg_x16 = !(q_last > 32 && q_last <= 48);
 #define AFCM_WG16G(T) do { if (wg_x16) AFCM_WG16G_(T, true); else AFCM_WG16G_(T, false); } while (0)
     // tensors below 2 GB: one descriptor per tensor; larger ones: a descriptor per LDS-DMA piece (the general form)
     const bool small = (long long)n * cout * p.P * p.lddy * 2 < (1ll << 31) - 65536 &&

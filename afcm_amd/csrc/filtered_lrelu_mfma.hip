@@ -188,13 +188,10 @@ __global__ __launch_bounds__((64 * MfmaGeom<UP, DOWN, TOW, TOH>::NG), (mfma_tile
     // exposed round trip per tile for the up/down-y set, one per column block for UH, one for DH).
     const frag* wsf = (const frag*)p.ws;
     auto cfrag = [&](int f) __attribute__((always_inline)) { return wsf[f * 64 + lane]; };
-#ifndef AFCM_FL_PF_TOP
-#define AFCM_FL_PF_TOP (SIGN != AFCM_SIGNS_NONE)
-#endif
     // (the sign-writing forward kernel is register-bound: at 6 waves per SIMD / 80 VGPRs holding these across the staging phase
     // costs more than the round trip saves, 1630 vs 1710 GB/s; bounded to 5 waves / 96 VGPRs it gains, 1750.  The backward
     // kernel gains at 6 waves, 1712 vs 1602, and loses at 5.)
-    constexpr bool PF_TOP = AFCM_FL_PF_TOP;
+    constexpr bool PF_TOP = SIGN != AFCM_SIGNS_NONE;
     frag uv[UP], dvs[G::NDVK], dvr[G::NDVK];
     auto load_const = [&]() __attribute__((always_inline)) {
 #pragma unroll

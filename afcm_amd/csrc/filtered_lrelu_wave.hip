@@ -23,43 +23,16 @@
 // Per 64x32-output tile: ~600 vector + 142 matrix instructions on one wave instead of 3 x (~490 + 53).
 #include "flrelu_mfma_common.h"
 
-// waves per SIMD the register allocation targets (tuning aids).  Down 2: three (168 registers), except the sign-writing 48-row strips
-// (the 36^2 planes): at 168 registers they spill ~70-100 registers to scratch -- encoder_12 forward 0.075 ms, 0.034 ms with two
-// waves' budget; the sign-reading 48-row kernel spills 20 and is still 10 % faster at three.
-#ifndef AFCM_WAVE_OCC_D2
-#define AFCM_WAVE_OCC_D2 3
-#endif
-#ifndef AFCM_WAVE_OCC_D4
-#define AFCM_WAVE_OCC_D4 2
-#endif
+// waves per SIMD the register allocation targets.  Down 2: three (168 registers), except the sign-writing 48-row strips (the 36^2
+// planes): at 168 registers they spill ~70-100 registers to scratch -- encoder_12 forward 0.075 ms, 0.034 ms with two waves' budget;
+// the sign-reading 48-row kernel spills 20 and is still 10 % faster at three.
+constexpr int kOccDown2 = 3, kOccDown4 = 2;
 // cache-policy bits of the output / sign stores (buffer aux: 1 = sc0, 2 = nt, 16 = sc1).  nt: the outputs and codes are written
 // once and read by a later kernel; as plain (write-back allocating) stores they slowed the loads queued behind them --
 // encoder_1 forward 0.190 -> 0.145 ms with nt
-#ifndef AFCM_WAVE_STORE_AUX
-#define AFCM_WAVE_STORE_AUX 2
-#endif
-// ... of the input loads
-#ifndef AFCM_WAVE_LOAD_AUX
-#define AFCM_WAVE_LOAD_AUX 0
-#endif
-// ... of the sign-code loads of the transposed op (read once)
-#ifndef AFCM_WAVE_SIGNLOAD_AUX
-#define AFCM_WAVE_SIGNLOAD_AUX 0
-#endif
-
-#if defined(AFCM_WAVE_STAMPS) && !defined(AFCM_WAVE_F16)     // (the bf16 translation unit only: one definition of the symbols)
-#define AFCM_WAVE_STAMPS_ON 1
-// diagnostic build only (VERDICT r05 #2d): shader-clock and real-time stamps around every strip, summed per kernel variant
-// slot = (UP == 4) | (DOWN == 4) << 1 | (sign mode 0..3) << 2 | (TOH == 48) << 4; per slot: {sum of s_memtime deltas (shader cycles), sum of
-// s_memrealtime deltas (100 MHz ticks), strips}.  In-loop clock of a variant = cycles / ticks x 100 MHz (MI355X_MICROARCH.md, DVFS item 6).
-// The stamps go to a buffer of their own that nothing else reads; no output depends on them.
-__device__ unsigned long long afcm_wave_stamp_acc[32][4];
-extern "C" int afcm_debug_wave_stamps(void* dst) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(afcm_wave_stamp_acc), sizeof(unsigned long long) * 32 * 4); }
-extern "C" int afcm_debug_wave_stamps_clear() {
-    static unsigned long long zero[32][4] = {};
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(afcm_wave_stamp_acc), zero, sizeof(zero));
-}
-#endif
+constexpr int kStoreAux = 2;
+constexpr int kLoadAux = 0;           // ... of the input loads
+constexpr int kSignLoadAux = 0;       // ... of the sign-code loads of the transposed op (read once)
 
 namespace afcm {
 
@@ -190,7 +163,7 @@ __global__ void flrelu_wave_prepare_kernel(char* __restrict__ wsb, const float* 
 constexpr int kSignsReadAligned = 3;
 // LDS of one workgroup (4 waves) of flrelu_wave_kernel: keep-mask table, output staging, skip staging, input ring (the arrays declared
 // at the top of the kernel), and the workgroups per CU = waves per SIMD that the 160 KB allow.  The register target of a variant
-// (__launch_bounds__) is the tuning aid's (AFCM_WAVE_OCC_*) capped by that: asking for more than the LDS admits only made the compiler
+// (__launch_bounds__) is kOccDown2 / kOccDown4 capped by that: asking for more than the LDS admits only made the compiler
 // report a missed occupancy target on 14 variants (r04 build log) -- the 48-row strips (66 KB) and the skip variants (56 KB) run two
 // workgroups per CU, the down-4 strips (74 KB) two, their skip variants (84 KB) one, whatever the register count.
 template <int UP, int DOWN, int TOW, int TOH, int SIGN, int EPI>
@@ -201,7 +174,7 @@ constexpr int wave_lds_bytes() {
 }
 template <int UP, int DOWN, int TOW, int TOH, int SIGN, int EPI>
 constexpr int wave_occupancy() {
-    constexpr int want = (DOWN == 2 && (TOH <= 32 || SIGN == AFCM_SIGNS_READ || SIGN == kSignsReadAligned)) ? AFCM_WAVE_OCC_D2 : AFCM_WAVE_OCC_D4;
+    constexpr int want = (DOWN == 2 && (TOH <= 32 || SIGN == AFCM_SIGNS_READ || SIGN == kSignsReadAligned)) ? kOccDown2 : kOccDown4;
     constexpr int fit = (160 * 1024) / wave_lds_bytes<UP, DOWN, TOW, TOH, SIGN, EPI>();
     return fit < 1 ? 1 : (fit < want ? fit : want);
 }
@@ -238,10 +211,6 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
-#ifdef AFCM_WAVE_EXPERIMENT_LDS         // timing experiment only: LDS nobody uses, to run the same code at fewer waves per SIMD
-    __shared__ unsigned char lds_pad[AFCM_WAVE_EXPERIMENT_LDS];
-    if (p.total_tiles < 0) lds_pad[tid] = 1;
-#endif
     if (RD) {
         if (tid < 128) ((uint4*)lds_tab)[tid] = ((const uint4*)((const char*)p.ws + kWsTable))[tid];
         __syncthreads();
@@ -294,11 +263,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
 
     // ---- input: rows [I0y, +16 NMB) x columns [S0x + IWSTEP gi, +32) per group, straight into A fragments
     const T* xp = (const T*)p.x + (size_t)plane * p.xh * p.xld;
-#ifdef AFCM_WAVE_EXPERIMENT_NOLOAD    // timing experiment only: every input load falls outside the descriptor
-    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)xp, 0, 0, 0x00020000);
-#else
     const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)xp, 0, p.xh * p.xld * 2, 0x00020000);
-#endif
     // Lane map of the global accesses: an MFMA fragment puts 16 different ROWS on consecutive lanes (lane = 16 g + l15), which the
     // memory pipeline sees as 64 separate 16-byte requests per instruction (measured: the two output stores of a group cost more
     // than all of its arithmetic).  So loads and stores use lane = 4 row + chunk -- 4 consecutive lanes cover 64 (stores: 32)
@@ -321,11 +286,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
         if (__builtin_expect(c0 >= 0 && c0 + 32 <= p.xw, 1)) {
 #pragma unroll
             for (int mb = 0; mb < G::NMB; mb++)
-#ifdef AFCM_WAVE_EXPERIMENT_CACHED_LOADS   // timing experiment only (wrong results): every piece is the strip's piece 0 or 1 -- real data, served by the L1 / L2
-                raw[mb] = __builtin_amdgcn_raw_buffer_load_b128(rsx, (unsigned)(xoff0 + 64 * (k & 1) + mb * xrow16), 0, AFCM_WAVE_LOAD_AUX);
-#else
-                raw[mb] = __builtin_amdgcn_raw_buffer_load_b128(rsx, (unsigned)(xoff0 + 64 * k + mb * xrow16), 0, AFCM_WAVE_LOAD_AUX);
-#endif
+                raw[mb] = __builtin_amdgcn_raw_buffer_load_b128(rsx, (unsigned)(xoff0 + 64 * k + mb * xrow16), 0, kLoadAux);
         } else {
             // the piece crosses the left or right edge of the plane: dword by dword, columns outside it read as zero
             // (even plane widths: the two elements of a dword are in or out together; rows outside: as above, except that a
@@ -387,9 +348,6 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
     // READ: the sign dwords of a group's two column blocks, fetched one group ahead like the input window (consumed right after
     // the up-y products: fetched in place, every column block exposed a full memory round trip)
     auto load_signs = [&](int nb, unsigned (&sg)[RA ? 1 : 2][NL]) __attribute__((always_inline)) {
-#ifdef AFCM_WAVE_EXPERIMENT_CACHED_LOADS   // timing experiment only (wrong results): the codes of the strip's first two column blocks, again and again
-        nb &= 1;
-#endif
         const int blo = sgr_lo + nb * blkbytes, bhi = sgr_hi + nb * blkbytes;
 #pragma unroll
         for (int i = 0; i < NL; i++) {
@@ -398,25 +356,14 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
                 ol = ((unsigned)(sgr_dl + i) < (unsigned)nV4) ? ol : 0x80000000u;
                 oh = ((unsigned)(sgr_dh + i) < (unsigned)nV4) ? oh : 0x80000000u;
             }
-#ifdef AFCM_WAVE_EXPERIMENT_NOSIGNLOAD  // timing experiment only (wrong results): every code load falls outside the descriptor
-            ol |= 0x80000000u;
-#endif
-            sg[0][i] = __builtin_amdgcn_raw_buffer_load_b32(rss, ol, 0, AFCM_WAVE_SIGNLOAD_AUX);
-            if constexpr (!RA) sg[1][i] = (yy != 0) ? __builtin_amdgcn_raw_buffer_load_b32(rss, oh, 0, AFCM_WAVE_SIGNLOAD_AUX) : 0u;
+            sg[0][i] = __builtin_amdgcn_raw_buffer_load_b32(rss, ol, 0, kSignLoadAux);
+            if constexpr (!RA) sg[1][i] = (yy != 0) ? __builtin_amdgcn_raw_buffer_load_b32(rss, oh, 0, kSignLoadAux) : 0u;
         }
     };
 
     // ---- output
     T* const yp = (T*)p.y + (size_t)plane * p.yh * p.yld;
-#ifdef AFCM_WAVE_EXPERIMENT_NOSTORE   // timing experiment only: every output store falls outside the descriptor
-    const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)yp, 0, 0, 0x00020000);
-#else
-#ifdef AFCM_WAVE_EXPERIMENT_STORE_ALIAS   // timing experiment only (wrong results): every plane's stores land in plane 0's first 64 KB
-    const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, p.yh * p.yld * 2, 0x00020000);
-#else
     const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)yp, 0, p.yh * p.yld * 2, 0x00020000);
-#endif
-#endif
     const bool has_skip = (EPI & 2) && p.skip != nullptr;
     const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(has_skip ? (const T*)p.skip + (size_t)plane * p.yh * p.kld : (const T*)p.x), 0, has_skip ? p.yh * p.kld * 2 : 0, 0x00020000);
@@ -514,9 +461,6 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
             for (int j = 0; j < TOH / 8; j++) {
                 const u32x4 v = *(const u32x4*)(stage + st_r + (unsigned)(j * 8 * OPITCH));
                 unsigned off = gofs + (unsigned)(j * 16 * p.yld);
-#ifdef AFCM_WAVE_EXPERIMENT_STORE_ALIAS  // timing experiment only: all output stores land in one 64 KB window (no HBM write traffic)
-                off &= 0xfff0u;
-#endif
                 if (p.st_plain) {
                     // dense rows wider than one 64-column group (the 84- / 86-wide planes: 168- / 172-byte rows): a row leaves as a 128-byte
                     // piece plus a 40-byte tail of pair stores, neither on a line boundary -- as write-back stores L2 merges them into whole
@@ -529,16 +473,16 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
                             __builtin_amdgcn_raw_buffer_store_b32(v[w2], rsy, (c0 + 2 * w2 + 2 <= p.yw && 8 * fl_chk + 2 * w2 < 16 * (slot + 1)) ? off + 4u * w2 : kOut, 0, 0);
                     }
                 } else if (full) {
-                    __builtin_amdgcn_raw_buffer_store_b128(v, rsy, off, 0, AFCM_WAVE_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(v, rsy, off, 0, kStoreAux);
                 } else if (p.yld != p.yw) {
                     // pitched rows end on a 16-byte boundary: the lanes whose 8 columns lie inside the pitch store, the others fall
                     // outside the descriptor
-                    __builtin_amdgcn_raw_buffer_store_b128(v, rsy, (c0 + 8 <= p.yld) ? off : kOut, 0, AFCM_WAVE_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b128(v, rsy, (c0 + 8 <= p.yld) ? off : kOut, 0, kStoreAux);
                 } else {
                     // the group crosses the right edge (or is only partly produced): pair by pair (even plane widths)
 #pragma unroll
                     for (int w2 = 0; w2 < 4; w2++)
-                        __builtin_amdgcn_raw_buffer_store_b32(v[w2], rsy, (c0 + 2 * w2 + 2 <= p.yw && 8 * fl_chk + 2 * w2 < 16 * (slot + 1)) ? off + 4u * w2 : kOut, 0, AFCM_WAVE_STORE_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b32(v[w2], rsy, (c0 + 2 * w2 + 2 <= p.yw && 8 * fl_chk + 2 * w2 < 16 * (slot + 1)) ? off + 4u * w2 : kOut, 0, kStoreAux);
                 }
             }
         }
@@ -569,7 +513,6 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
                 for (int k = 0; k < NA; k++)
                     four[nbl][k] = __builtin_amdgcn_alignbyte(k + 1 < NL ? sg[nbl][0][k + 1] : 0u, sg[nbl][0][k], sgr_sl);
             }
-#ifndef AFCM_WAVE_NO_PIN_SIGNS
             // ... and pinned here: left to the scheduler the funnel shifts sank below the flush, so the wait for the codes (vmcnt is in
             // order and the count must hold on the path without a flush: 0) also drained the four output stores issued a moment
             // before, every fourth group, and the next request left half a group late.  (An empty asm with a memory clobber: the
@@ -579,7 +522,6 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
 #pragma unroll
                 for (int k = 0; k < NA; k++) asm volatile("" : "+v"(four[nbl][k]) : : "memory");
             __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         // the window of group PGRP (k - 1) + 1 is the first to reach into piece k: park it (requested PGRP groups ago, or before
         // the loop) and request piece k + 1 into the same registers; then this group's fragments; then the stores of the 64-column
@@ -611,9 +553,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
             // register copies that wait for the window just requested)
             load_signs((gi + 1) * G::NBG, sg[0]);
             load_signs((gi + 1) * G::NBG + 1, sg[1]);
-#ifndef AFCM_WAVE_NO_PIN_SIGNS
             __builtin_amdgcn_sched_barrier(0);
-#endif
         }
 #pragma unroll
         for (int nbl = 0; nbl < G::NBG; nbl++) {
@@ -675,11 +615,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
             __amdgpu_buffer_rsrc_t rsw = rsx;
             if (SIGN == AFCM_SIGNS_WRITE) {
                 const int blk = (U0x >> 4) + nb;
-#ifdef AFCM_WAVE_EXPERIMENT_STORE_ALIAS   // (... and every block's codes in the tensor's first block)
-                rsw = __builtin_amdgcn_make_buffer_rsrc((void*)p.s, 0, blk < nblk ? v4_end * 256 : 0, 0x00020000);
-#else
                 rsw = __builtin_amdgcn_make_buffer_rsrc((void*)(splane + (size_t)blk * blkbytes), 0, blk < nblk ? v4_end * 256 : 0, 0x00020000);
-#endif
             }
 
             // up-y + activation.  Fast path: relu(X2) (forward) / keep-mask & X2 (backward) is the only operand kept; the linear
@@ -702,11 +638,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
                     f32x4 x2 = M::mma(uv[vb % UP], q[vb / UP], zero4);
                     if (RD) {
                         if (!EXACT) {
-#ifdef AFCM_WAVE_EXPERIMENT_NOTABLE     // timing experiment only (wrong results): no keep-mask lookup
-                            const uint2 keep = make_uint2(0xffffffffu ^ codes[vb], 0xffffffffu);
-#else
                             const uint2 keep = lds_tab[codes[vb]];
-#endif
                             r0 = pack2<T>(x2[0], x2[1]) & keep.x;
                             r1 = pack2<T>(x2[2], x2[3]) & keep.y;
                         } else {
@@ -775,7 +707,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
                         const unsigned p23 = __builtin_amdgcn_perm(wc[4 * d + 3], wc[4 * d + 2], 0x0c0c0400u);
                         dw = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
                     }
-                    __builtin_amdgcn_raw_buffer_store_b32(dw, rsw, sgw_off + 256u * d, 0, AFCM_WAVE_STORE_AUX);
+                    __builtin_amdgcn_raw_buffer_store_b32(dw, rsw, sgw_off + 256u * d, 0, kStoreAux);
                 }
             }
 
@@ -863,7 +795,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
             // counted like any other) make the two states equal.
             constexpr int NVW = decltype(lasty_c)::value ? G::NVB : G::OWN_VB;
 #pragma unroll
-            for (int i = 0; i < G::NBG * cdiv(NVW, 4); i++) __builtin_amdgcn_raw_buffer_store_b32(0u, rsx, kOut + 256u * i, 0, AFCM_WAVE_STORE_AUX);   // (distinct, non-adjacent offsets: identical or adjacent stores are merged)
+            for (int i = 0; i < G::NBG * cdiv(NVW, 4); i++) __builtin_amdgcn_raw_buffer_store_b32(0u, rsx, kOut + 256u * i, 0, kStoreAux);   // (distinct, non-adjacent offsets: identical or adjacent stores are merged)
         }
         if (RD) {
             load_signs(0, sg[0]);
@@ -915,9 +847,6 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
         if (RD) return __builtin_amdgcn_ballot_w64((anyc & 0xaaaaaaaau) != 0) != 0;   // a clamped element in reach
         return __builtin_amdgcn_ballot_w64(!(amax <= cthr1)) != 0;                                        // NaN takes the exact path
     };
-#ifdef AFCM_WAVE_STAMPS_ON
-    const unsigned long long st_c0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // (READ never writes codes: one LASTY variant suffices)
     bool exact;
     if (SIGN == AFCM_SIGNS_WRITE && lastY) {
@@ -927,18 +856,6 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
         exact = run_strip(std::false_type{}, std::false_type{});
         if (__builtin_expect(exact, 0)) run_strip(std::true_type{}, std::false_type{});
     }
-#ifdef AFCM_WAVE_STAMPS_ON
-    {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        const unsigned long long st_c1 = __builtin_amdgcn_s_memtime(), st_r1 = __builtin_amdgcn_s_memrealtime();
-        constexpr int slot = (UP == 4 ? 1 : 0) | (DOWN == 4 ? 2 : 0) | ((SIGN & 3) << 2) | (TOH == 48 ? 16 : 0);
-        if (lane == 0) {
-            atomicAdd(&afcm_wave_stamp_acc[slot][0], st_c1 - st_c0);
-            atomicAdd(&afcm_wave_stamp_acc[slot][1], st_r1 - st_r0);
-            atomicAdd(&afcm_wave_stamp_acc[slot][2], 1ull);
-        }
-    }
-#endif
     // optional per-strip flag: the strip's activations could reach the clamp (a plane with no flagged strip is positively homogeneous
     // of degree 1 in its input: the caller derives <dL/dy, y> from <g, z>, afcm_plane_dot_gated_ld).  Every slot is written.
     if (!RD && p.clamp_flags != nullptr && lane == 0) p.clamp_flags[(size_t)plane * (p.tilesX * p.tilesY) + ty * p.tilesX + tx] = exact ? 1 : 0;

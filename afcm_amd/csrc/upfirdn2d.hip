@@ -21,12 +21,7 @@ struct UpfirdnParams {
 };
 
 constexpr int kMaxTaps = 4096;
-#ifndef AFCM_UPF_RPT11
-#define AFCM_UPF_RPT11 8           // output rows per thread of the (up 1, down 1) row kernel (tuning aid)
-#endif
-#ifndef AFCM_UPFIRDN_ROWS
-#define AFCM_UPFIRDN_ROWS 1        // 16-bit small filters on upfirdn2d_rows_kernel (0: the LDS tile kernel; A/B builds)
-#endif
+constexpr int kRowsPerThread11 = 8;   // output rows per thread of the (up 1, down 1) row kernel
 
 template <typename T>
 __global__ __launch_bounds__(256) void upfirdn2d_kernel(UpfirdnParams p, const float* __restrict__ f) {
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(256) void upfirdn2d_tile_kernel(UpfirdnParams p, co
 //   XODD: the first input column of a group is odd (UP 1: padx0 odd; UP 2: the zero-inserted origin x0 - padx0 is odd);  YODD (UP 2): the
 //   zero-inserted origin row is odd.  Both are uniform over the launch (x0 is a multiple of 8, the first row of a strip a multiple of RPT).
 template <int UP, int DOWN> struct UpfRows {
-    static constexpr int RPT = (UP == 1 && DOWN == 2) ? 4 : (UP == 1 ? AFCM_UPF_RPT11 : 8);   // output rows per thread
+    static constexpr int RPT = (UP == 1 && DOWN == 2) ? 4 : (UP == 1 ? kRowsPerThread11 : 8);   // output rows per thread
     static constexpr int NIN = UP == 1 ? (RPT - 1) * DOWN + 4 : 6;                      // input rows a thread reads
     static constexpr int NEED = UP == 1 ? 7 * DOWN + 4 : 6;                             // input columns per row (from the group's first)
     static constexpr int NL = (NEED + 1 + 7) / 8;                                       // 16-byte loads per row (+ 1: the odd start)
@@ -411,7 +406,7 @@ extern "C" int afcm_upfirdn2d(void* y, const void* x, const float* f, int32_t dt
     if (nblk > 256 * 64) nblk = 256 * 64;
     dim3 grid((unsigned)nblk), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (AFCM_UPFIRDN_ROWS && dtype != AFCM_F32) {
+    if (dtype != AFCM_F32) {                   // 16-bit small filters: upfirdn2d_rows_kernel
         const bool done = dtype == AFCM_F16 ? launch_rows<f16_t>(p, f, st) : launch_rows<bf16_t>(p, f, st);
         if (done) return hip_status(hipGetLastError());
     }

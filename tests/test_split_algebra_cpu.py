@@ -1,5 +1,5 @@
 """CPU checks of the split-operand algebra behind the fp32 convs on the 16-bit matrix pipe (afcm_amd/torch_utils/ops/conv2d.py:
-_SPLIT_TERMS, FP32_SPLIT; kernels: csrc/conv2d.hip split16_kernel / conv2d_fwd16_kernel<.., SPLIT>): the term tables and the
+_SPLIT_TERMS, FP32_SPLIT; kernels: csrc/conv2d.hip split16_kernel / conv2d_fwd16x_kernel<.., SPLIT>): the term tables and the
 power-of-two scaling are emulated with torch's CPU float16 / bfloat16 rounding (round to nearest even, as the kernels' conversions)
 and float64 accumulation, so that what remains is exactly the error of the splitting itself."""
 import pytest

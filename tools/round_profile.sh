@@ -12,7 +12,7 @@ echo tests done
 python bench.py --full > "$res/${tag}_bench.json" 2> "$res/${tag}_bench.err" < /dev/null
 echo bench done
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${tag}_smoke.log 2>&1 < /dev/null
-bash tools/r03_step_profile.sh ${tag} < /dev/null > /dev/null 2>&1 || true
+bash tools/step_profile.sh ${tag} < /dev/null > /dev/null 2>&1 || true
 cp gpurun_out/${tag}_traf/trace/*/*kernel_stats.csv gpurun_out/${tag}_bench_kernel_stats.csv 2>/dev/null || true
 echo traffic done
 bash tools/pmc_wave.sh ${tag}_pmcw bench.py --steps 2 --warmup 1 --lean --no-kernel-timing < /dev/null > /dev/null 2>&1 || true

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/r03_step_profile.sh <tag> [env assignments...]   (GPU box, repo root)
+# usage: tools/step_profile.sh <tag> [env assignments...]   (GPU box, repo root)
 # kernel trace + FETCH_SIZE + WRITE_SIZE passes of the bench command (each in its own run), then the per-launch in-step table of
 # the filtered_lrelu kernels (tools/flrelu_step_table.py) -> gpurun_out/<tag>_flrelu_step.txt
 tag=$1; shift
