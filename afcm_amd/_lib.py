@@ -185,3 +185,11 @@ def check(rc, what):
     if rc == E_INVALID:
         raise RuntimeError(f'{what}: {load().afcm_last_error().decode()}')
     raise RuntimeError(f'{what}: HIP error {rc - 1000} at kernel launch')
+
+
+def launched(rc, what):
+    """``check`` for a call site with no fallback: an entry point that declined the shape (E_NOKERNEL) left its outputs unwritten, so
+    that is an error here too, never an uninitialised result."""
+    if check(rc, what) == E_NOKERNEL:
+        raise RuntimeError(f'{what}: no kernel for this shape (the Python gate and the C entry point disagree)')
+    return rc

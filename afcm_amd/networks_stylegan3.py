@@ -98,7 +98,7 @@ class _PoolBlocks(torch.autograd.Function):
         x = x.contiguous()
         n, c, h, w = x.shape
         y = torch.empty([n, c, 4, 4], dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().afcm_pool_blocks_fwd(y.data_ptr(), x.data_ptr(), _lib.dtype_code(x), n * c, h, w, _lib.stream_ptr(x)), 'pool_blocks_fwd')
+        _lib.launched(_lib.load().afcm_pool_blocks_fwd(y.data_ptr(), x.data_ptr(), _lib.dtype_code(x), n * c, h, w, _lib.stream_ptr(x)), 'pool_blocks_fwd')
         ctx.cfg = (tuple(x.shape), x.dtype)
         return y
 
@@ -110,7 +110,7 @@ class _PoolBlocks(torch.autograd.Function):
         n, c, h, w = shape
         dx = torch.empty(shape, dtype=dtype, device=gy.device)
         gy = gy.to(torch.float32).contiguous()
-        _lib.check(_lib.load().afcm_pool_blocks_bwd(dx.data_ptr(), gy.data_ptr(), _lib._DTYPES[dtype], n * c, h, w, _lib.stream_ptr(gy)), 'pool_blocks_bwd')
+        _lib.launched(_lib.load().afcm_pool_blocks_bwd(dx.data_ptr(), gy.data_ptr(), _lib._DTYPES[dtype], n * c, h, w, _lib.stream_ptr(gy)), 'pool_blocks_bwd')
         return dx
 
 

@@ -107,17 +107,17 @@ class FusedScrubAdam(torch.optim.Optimizer):
                 sd = self._step_dev.get(key)
                 if sd is None:
                     sd = self._step_dev[key] = torch.full([1], float(step_t - 1), dtype=torch.float32, device=dev)
-                _lib.check(lib.afcm_adam_multi_capturable(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, ctypes.c_void_p(sd.data_ptr()), group['lr'],
-                                                          beta1, beta2, group['eps'], float(grad_scale), int(self.scrub), self.posinf, self.neginf,
-                                                          int(self.write_grad), _lib.stream_ptr(table)), 'adam_multi_capturable')
+                _lib.launched(lib.afcm_adam_multi_capturable(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, ctypes.c_void_p(sd.data_ptr()), group['lr'],
+                                                             beta1, beta2, group['eps'], float(grad_scale), int(self.scrub), self.posinf, self.neginf,
+                                                             int(self.write_grad), _lib.stream_ptr(table)), 'adam_multi_capturable')
                 torch.autograd.graph.increment_version(touched)
                 continue
             # bias corrections in double on the host, as torch.optim.Adam does for non-capturable steps
             bc1 = 1.0 - beta1 ** step_t
             bc2 = 1.0 - beta2 ** step_t
-            _lib.check(lib.afcm_adam_multi(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, group['lr'] / bc1, beta1, beta2,
-                                           1.0 - beta1, 1.0 - beta2, math.sqrt(bc2), group['eps'], float(grad_scale), int(self.scrub), self.posinf, self.neginf,
-                                           int(self.write_grad), _lib.stream_ptr(table)), 'adam_multi')
+            _lib.launched(lib.afcm_adam_multi(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, group['lr'] / bc1, beta1, beta2,
+                                              1.0 - beta1, 1.0 - beta2, math.sqrt(bc2), group['eps'], float(grad_scale), int(self.scrub), self.posinf, self.neginf,
+                                              int(self.write_grad), _lib.stream_ptr(table)), 'adam_multi')
             # the kernel wrote through raw pointers: tell autograd (version counters), so that anything keyed on a parameter's version --
             # saved-tensor checks, caches of derived tensors such as packed weight images -- sees the update
             torch.autograd.graph.increment_version(touched)
@@ -144,7 +144,7 @@ class _WeightedL1(torch.autograd.Function):
         numel = a.numel()
         blocks = max(1, min(256, (numel + 4095) // 4096))
         partials = torch.empty([blocks], dtype=torch.float32, device=a.device)
-        _lib.check(lib.afcm_l1_partials(partials.data_ptr(), a.data_ptr(), b.data_ptr(), numel, blocks, float(weight), _lib.stream_ptr(a)), 'l1_partials')
+        _lib.launched(lib.afcm_l1_partials(partials.data_ptr(), a.data_ptr(), b.data_ptr(), numel, blocks, float(weight), _lib.stream_ptr(a)), 'l1_partials')
         ctx.save_for_backward(a, b)
         ctx.weight = float(weight)
         return partials.sum()
@@ -155,7 +155,7 @@ class _WeightedL1(torch.autograd.Function):
         a, b = ctx.saved_tensors
         ga = torch.empty_like(a)
         gout = gout.to(torch.float32).contiguous()
-        _lib.check(_lib.load().afcm_l1_grad(ga.data_ptr(), a.data_ptr(), b.data_ptr(), gout.data_ptr(), a.numel(), ctx.weight, _lib.stream_ptr(a)), 'l1_grad')
+        _lib.launched(_lib.load().afcm_l1_grad(ga.data_ptr(), a.data_ptr(), b.data_ptr(), gout.data_ptr(), a.numel(), ctx.weight, _lib.stream_ptr(a)), 'l1_grad')
         return ga, None, None
 
 

@@ -58,9 +58,10 @@ def supported(ws, global_w, specs):
             return False
         if b is None or b.dtype != torch.float32 or not b.is_contiguous():
             return False
-        if not 0 <= sp.w_index < ws.shape[1]:
+        if not 0 <= sp.w_index < ws.shape[1] or w.data_ptr() % 16 != 0:
             return False
-    return (k <= 1536 and ws.shape[2] % 4 == 0 and kg % 4 == 0 and ws.stride(0) % 4 == 0 and ws.stride(1) % 4 == 0
+    # (csrc/affine_bank.hip bank_supported: the matrix kernels walk K in chunks of 16, so K % 16 as well as kw % 4 and kg % 4)
+    return (k <= 1536 and k % 16 == 0 and ws.shape[2] % 4 == 0 and kg % 4 == 0 and ws.stride(0) % 4 == 0 and ws.stride(1) % 4 == 0
             and ws.data_ptr() % 16 == 0 and (global_w is None or global_w.data_ptr() % 16 == 0))
 
 
@@ -101,8 +102,8 @@ class _AffineBank(torch.autograd.Function):
             d_g = torch.empty_like(global_w) if global_w is not None else None
             wsp = torch.empty([int(lib.afcm_affine_bank_workspace_bytes(a))], dtype=torch.uint8, device=ws.device)
         any_w = any(need_w) or any(need_b)
-        _lib.check(lib.afcm_affine_bank_bwd(a, _table(gs), _table(dws) if any_w else None, _table(dbs) if any_w else None, _lib.ptr(d_ws_l), _lib.ptr(d_g),
-                                            _lib.ptr(wsp), _lib.stream_ptr(ws)), 'affine_bank')
+        _lib.launched(lib.afcm_affine_bank_bwd(a, _table(gs), _table(dws) if any_w else None, _table(dbs) if any_w else None, _lib.ptr(d_ws_l), _lib.ptr(d_g),
+                                               _lib.ptr(wsp), _lib.stream_ptr(ws)), 'affine_bank')
         d_ws = None
         if ctx.needs_input_grad[0]:
             # the per-layer latent gradients back onto ws's latent axis (several layers may share a latent)

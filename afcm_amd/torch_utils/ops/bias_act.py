@@ -49,7 +49,7 @@ def _launch(x, b, xref, yref, dy, grad, dim, spec, alpha, gain, clamp):
             raise RuntimeError('xref, yref and dy must have the same shape and dtype as x')
     rc = lib.afcm_bias_act(_lib.ptr(y), _lib.ptr(x), _lib.ptr(b), _lib.ptr(xref), _lib.ptr(yref), _lib.ptr(dy),
                            _lib.dtype_code(x), x.numel(), inner, nb, grad, spec.cuda_idx, alpha, gain, clamp, _lib.stream_ptr(x))
-    _lib.check(rc, 'bias_act')
+    _lib.launched(rc, 'bias_act')
     return y
 
 

@@ -32,8 +32,8 @@ def pack_weights(w, dtype, mode):
     rows_pad = _pad64(rows)
     nkc = (cols + bk - 1) // bk
     dst = torch.empty([nkc, kh * kw, rows_pad, bk], dtype=dtype, device=w.device)
-    _lib.check(lib.afcm_conv2d_pack_weights(dst.data_ptr(), w.data_ptr(), code, o, i, kh, mode, rows_pad, _lib.stream_ptr(w)),
-               'conv2d_pack_weights')
+    _lib.launched(lib.afcm_conv2d_pack_weights(dst.data_ptr(), w.data_ptr(), code, o, i, kh, mode, rows_pad, _lib.stream_ptr(w)),
+                  'conv2d_pack_weights')
     return dst, rows_pad
 
 
@@ -49,8 +49,8 @@ def pack_weights_both(w, dtype):
     rp0, rp1 = _pad64(o), _pad64(i)
     d0 = torch.empty([(i + bk - 1) // bk, kh * kw, rp0, bk], dtype=dtype, device=w.device)
     d1 = torch.empty([(o + bk - 1) // bk, kh * kw, rp1, bk], dtype=dtype, device=w.device)
-    _lib.check(lib.afcm_conv2d_pack_weights2(d0.data_ptr(), d1.data_ptr(), w.data_ptr(), code, o, i, kh, rp0, rp1, _lib.stream_ptr(w)),
-               'conv2d_pack_weights2')
+    _lib.launched(lib.afcm_conv2d_pack_weights2(d0.data_ptr(), d1.data_ptr(), w.data_ptr(), code, o, i, kh, rp0, rp1, _lib.stream_ptr(w)),
+                  'conv2d_pack_weights2')
     return (d0, rp0), (d1, rp1)
 
 
@@ -79,7 +79,7 @@ def pack_weights_bank(ws, dtype, need_dgrad=True):
         e.dst_fwd, e.dst_dgrad, e.w = d0.data_ptr(), (d1.data_ptr() if need_dgrad else 0), w32.data_ptr()
         e.cout, e.cin, e.rows_pad_fwd, e.rows_pad_dgrad = o, i, rp0, rp1
         out.append(((d0, rp0), ((d1, rp1) if need_dgrad else None)))
-    _lib.check(lib.afcm_conv2d_pack_bank(table, len(ws), code, ks, _lib.stream_ptr(ws[0])), 'conv2d_pack_bank')
+    _lib.launched(lib.afcm_conv2d_pack_bank(table, len(ws), code, ks, _lib.stream_ptr(ws[0])), 'conv2d_pack_bank')
     return out
 
 
@@ -98,8 +98,8 @@ def scale_planes(x, scale, out_dtype=None):
     if scale is not None:
         scale = scale.to(torch.float32).contiguous()
         assert scale.numel() == n * c
-    _lib.check(lib.afcm_scale_planes(y.data_ptr(), x.data_ptr(), _lib.ptr(scale), _lib.dtype_code(x), _lib._DTYPES[out_dtype],
-                                     n * c, h * w, _lib.stream_ptr(x)), 'scale_planes')
+    _lib.launched(lib.afcm_scale_planes(y.data_ptr(), x.data_ptr(), _lib.ptr(scale), _lib.dtype_code(x), _lib._DTYPES[out_dtype],
+                                        n * c, h * w, _lib.stream_ptr(x)), 'scale_planes')
     return y
 
 
@@ -118,8 +118,8 @@ def plane_dot(a, b=None):
             and a.data_ptr() % 4 == 0 and (b is None or b.data_ptr() % 4 == 0)):      # (pitch_of takes a dense tensor at any offset)
         n, c, h, w = a.shape
         out = torch.empty([n, c], dtype=torch.float32, device=a.device)
-        _lib.check(lib.afcm_plane_dot_ld(out.data_ptr(), a.data_ptr(), _lib.ptr(b), _lib.dtype_code(a), n * c, h, w, lda, ldb, _lib.stream_ptr(a)),
-                   'plane_dot')
+        _lib.launched(lib.afcm_plane_dot_ld(out.data_ptr(), a.data_ptr(), _lib.ptr(b), _lib.dtype_code(a), n * c, h, w, lda, ldb, _lib.stream_ptr(a)),
+                      'plane_dot')
         return out
     a = a.contiguous()
     if a.data_ptr() % 16:                 # a view at an odd storage offset: the kernel wants 16-byte aligned bases
@@ -131,8 +131,8 @@ def plane_dot(a, b=None):
         if b.data_ptr() % 16:
             b = b.clone()
     out = torch.empty([n, c], dtype=torch.float32, device=a.device)
-    _lib.check(lib.afcm_plane_dot(out.data_ptr(), a.data_ptr(), _lib.ptr(b), _lib.dtype_code(a), n * c, h * w, _lib.stream_ptr(a)),
-               'plane_dot')
+    _lib.launched(lib.afcm_plane_dot(out.data_ptr(), a.data_ptr(), _lib.ptr(b), _lib.dtype_code(a), n * c, h * w, _lib.stream_ptr(a)),
+                  'plane_dot')
     return out
 
 
@@ -153,9 +153,9 @@ def plane_dot_gated(a, b, flags, out_scale, gz, next_scale=None, gskip=None):
     for t in (out_scale, gz, next_scale, gskip):
         assert t is None or (t.dtype == f32 and t.is_contiguous() and t.numel() == n * c)
     out = torch.empty([n, c], dtype=f32, device=a.device)
-    _lib.check(lib.afcm_plane_dot_gated_ld(out.data_ptr(), a.data_ptr(), b.data_ptr(), _lib.dtype_code(a), n * c, h, w, lda, ldb,
-                                           flags.data_ptr(), int(flags.shape[2]), out_scale.data_ptr(), gz.data_ptr(), _lib.ptr(next_scale),
-                                           _lib.ptr(gskip), _lib.stream_ptr(a)), 'plane_dot_gated')
+    _lib.launched(lib.afcm_plane_dot_gated_ld(out.data_ptr(), a.data_ptr(), b.data_ptr(), _lib.dtype_code(a), n * c, h, w, lda, ldb,
+                                              flags.data_ptr(), int(flags.shape[2]), out_scale.data_ptr(), gz.data_ptr(), _lib.ptr(next_scale),
+                                              _lib.ptr(gskip), _lib.stream_ptr(a)), 'plane_dot_gated')
     return out
 
 
@@ -232,7 +232,7 @@ def amax_bits(x, scale=None, out=None):
     if scale is not None:
         scale = scale.detach().to(torch.float32).contiguous()
         assert scale.numel() == planes
-    _lib.check(lib.afcm_amax_bits(word.data_ptr(), x.data_ptr(), planes, hw, _lib.ptr(scale), _lib.stream_ptr(x)), 'amax_bits')
+    _lib.launched(lib.afcm_amax_bits(word.data_ptr(), x.data_ptr(), planes, hw, _lib.ptr(scale), _lib.stream_ptr(x)), 'amax_bits')
     return word
 
 
@@ -259,8 +259,8 @@ def split16(x, scale=None, nparts=2, dtype=torch.float16, bound=None):
         assert scale.numel() == n * c
     if bound is not None:
         assert bound.dtype == torch.int32 and bound.numel() == 1 and bound.device == x.device
-    _lib.check(lib.afcm_split16(buf.data_ptr(), x.data_ptr(), _lib.ptr(scale), _lib.ptr(bound), _lib._DTYPES[dtype], n * c, h * w, nparts, stride,
-                                _lib.stream_ptr(x)), 'split16')
+    _lib.launched(lib.afcm_split16(buf.data_ptr(), x.data_ptr(), _lib.ptr(scale), _lib.ptr(bound), _lib._DTYPES[dtype], n * c, h * w, nparts, stride,
+                                   _lib.stream_ptr(x)), 'split16')
     return buf[:, :total].view(nparts, n, c, h, w)
 
 
@@ -272,8 +272,8 @@ def plane_dot_parts(parts, b, bound=None):
     b = b.contiguous()
     assert b.dtype == torch.float32 and tuple(b.shape) == (n, c, h, w) and parts.stride(1) == c * h * w
     out = torch.empty([n, c], dtype=torch.float32, device=b.device)
-    _lib.check(lib.afcm_plane_dot_parts(out.data_ptr(), parts.data_ptr(), parts.stride(0), nparts, b.data_ptr(), _lib._DTYPES[parts.dtype], n * c, h * w,
-                                        _lib.ptr(bound), _lib.stream_ptr(b)), 'plane_dot_parts')
+    _lib.launched(lib.afcm_plane_dot_parts(out.data_ptr(), parts.data_ptr(), parts.stride(0), nparts, b.data_ptr(), _lib._DTYPES[parts.dtype], n * c, h * w,
+                                           _lib.ptr(bound), _lib.stream_ptr(b)), 'plane_dot_parts')
     return out
 
 
@@ -305,8 +305,8 @@ def pack_weights_split(w, terms, dtype, transposed=False):
     bk = lib.afcm_conv2d_block_k_ks(_lib._DTYPES[dtype], 3)
     dst = torch.empty([terms * ((cols + bk - 1) // bk), 9, rows_pad, bk], dtype=dtype, device=w.device)
     code = sum(b << (4 * t) for t, (_, b) in enumerate(table))
-    _lib.check(lib.afcm_conv2d_pack_split(dst.data_ptr(), w.data_ptr(), _lib.ptr(bound), _lib._DTYPES[dtype], o, i, 1 if transposed else 0, rows_pad,
-                                          terms, code, _lib.stream_ptr(w)), 'conv2d_pack_split')
+    _lib.launched(lib.afcm_conv2d_pack_split(dst.data_ptr(), w.data_ptr(), _lib.ptr(bound), _lib._DTYPES[dtype], o, i, 1 if transposed else 0, rows_pad,
+                                             terms, code, _lib.stream_ptr(w)), 'conv2d_pack_split')
     return dst, rows_pad, bound
 
 
@@ -329,9 +329,9 @@ def _conv_split(parts, wp, rows_pad, terms, oscale, cout, pad, obias=None, bound
         assert obias.numel() == cout
     code = sum(a << (4 * t) for t, (a, _) in enumerate(table))
     span = profiling.span('conv2d', 2.0 * n * cout * cin * 9 * p * q)
-    _lib.check(lib.afcm_conv2d_split(y.data_ptr(), parts.data_ptr(), wp.data_ptr(), _lib.ptr(oscale), _lib.ptr(obias), _lib._DTYPES[parts.dtype], n, cin,
-                                     cout, h, w, pad, rows_pad, terms, code, parts.stride(0), _lib.ptr(bounds[0]), _lib.ptr(bounds[1]),
-                                     _lib.stream_ptr(parts)), 'conv2d_split')
+    _lib.launched(lib.afcm_conv2d_split(y.data_ptr(), parts.data_ptr(), wp.data_ptr(), _lib.ptr(oscale), _lib.ptr(obias), _lib._DTYPES[parts.dtype], n, cin,
+                                        cout, h, w, pad, rows_pad, terms, code, parts.stride(0), _lib.ptr(bounds[0]), _lib.ptr(bounds[1]),
+                                        _lib.stream_ptr(parts)), 'conv2d_split')
     if span is not None:
         span.end()
     return y
@@ -348,7 +348,7 @@ def _wgrad_split(dy_parts, x_parts, cout, cin, pad, terms, bounds=(None, None)):
         d = _wgrad_raw(dyb, x_parts[a], cout, cin, 3, padb, work_share=1.0 / terms)
         dw = d if dw is None else dw.add_(d)
     if bounds[0] is not None or bounds[1] is not None:
-        _lib.check(_lib.load().afcm_unscale(dw.data_ptr(), dw.numel(), _lib.ptr(bounds[0]), _lib.ptr(bounds[1]), _lib.stream_ptr(dw)), 'unscale')
+        _lib.launched(_lib.load().afcm_unscale(dw.data_ptr(), dw.numel(), _lib.ptr(bounds[0]), _lib.ptr(bounds[1]), _lib.stream_ptr(dw)), 'unscale')
     return dw
 
 
@@ -381,8 +381,8 @@ def _conv_raw(x, wp, rows_pad, oscale, cout, ks, pad, obias=None, pitched_out=Fa
     if obias is not None:
         obias = obias.to(torch.float32).contiguous()
         assert obias.numel() == cout
-    _lib.check(lib.afcm_conv2d_ld(y.data_ptr(), x.data_ptr(), wp.data_ptr(), _lib.ptr(oscale), _lib.ptr(obias), _lib.dtype_code(x), n, cin, cout, h, w,
-                                  ks, pad, rows_pad, 0 if xld == w else xld, 0 if yld == q else yld, _lib.stream_ptr(x)), 'conv2d')
+    _lib.launched(lib.afcm_conv2d_ld(y.data_ptr(), x.data_ptr(), wp.data_ptr(), _lib.ptr(oscale), _lib.ptr(obias), _lib.dtype_code(x), n, cin, cout, h, w,
+                                     ks, pad, rows_pad, 0 if xld == w else xld, 0 if yld == q else yld, _lib.stream_ptr(x)), 'conv2d')
     if span is not None:
         span.end()
     return y
@@ -429,8 +429,8 @@ def _wgrad_raw(dy, x, cout, cin, ks, pad, work_share=1.0, dots_with=None):
         if rc != 0:
             dots = None
     if dots is None:
-        _lib.check(lib.afcm_conv2d_wgrad_ld(dw.data_ptr(), ws.data_ptr(), dy.data_ptr(), x.data_ptr(), _lib.dtype_code(x), n, cin, cout,
-                                            h, w, ks, pad, 0 if lddy == dy.shape[3] else lddy, 0 if ldx == w else ldx, _lib.stream_ptr(x)), 'conv2d_wgrad')
+        _lib.launched(lib.afcm_conv2d_wgrad_ld(dw.data_ptr(), ws.data_ptr(), dy.data_ptr(), x.data_ptr(), _lib.dtype_code(x), n, cin, cout,
+                                               h, w, ks, pad, 0 if lddy == dy.shape[3] else lddy, 0 if ldx == w else ldx, _lib.stream_ptr(x)), 'conv2d_wgrad')
     if span is not None:
         span.end()
     return dw if dots_with is None else (dw, dots)
@@ -623,12 +623,12 @@ class _StridedConv2d(torch.autograd.Function):
         # stale images
         w32 = w.detach().to(torch.float32).contiguous()
         wp = torch.empty([(cin + bk - 1) // bk, 9, rows_pad, bk], dtype=x.dtype, device=x.device)
-        _lib.check(lib.afcm_conv2d_pack_weights_bk(wp.data_ptr(), w32.data_ptr(), code, cout, cin, 3, 0, rows_pad, bk, _lib.stream_ptr(x)), 'conv2d_pack_weights')
+        _lib.launched(lib.afcm_conv2d_pack_weights_bk(wp.data_ptr(), w32.data_ptr(), code, cout, cin, 3, 0, rows_pad, bk, _lib.stream_ptr(x)), 'conv2d_pack_weights')
         p, q = (h + 2 * padding - 3) // 2 + 1, (wd + 2 * padding - 3) // 2 + 1
         y = torch.empty([n, cout, p, q], dtype=x.dtype, device=x.device)
         span = profiling.span('conv2d', 2.0 * n * cout * cin * 9 * p * q)
-        _lib.check(lib.afcm_conv2d_stride2(y.data_ptr(), x.data_ptr(), wp.data_ptr(), code, n, cin, cout, h, wd, padding, rows_pad, _lib.stream_ptr(x)),
-                   'conv2d_stride2')
+        _lib.launched(lib.afcm_conv2d_stride2(y.data_ptr(), x.data_ptr(), wp.data_ptr(), code, n, cin, cout, h, wd, padding, rows_pad, _lib.stream_ptr(x)),
+                      'conv2d_stride2')
         if span is not None:
             span.end()
         ctx.save_for_backward(x, w)
@@ -701,8 +701,8 @@ class _WeightNorm(torch.autograd.Function):
         w_hat = torch.empty_like(w)
         wsq = torch.empty([o, i], dtype=torch.float32, device=w.device)
         scale = torch.empty([o], dtype=torch.float32, device=w.device)
-        _lib.check(lib.afcm_weight_norm_fwd(w_hat.data_ptr(), wsq.data_ptr(), scale.data_ptr(), w.data_ptr(), o, i, kh * kw,
-                                            _lib.stream_ptr(w)), 'weight_norm_fwd')
+        _lib.launched(lib.afcm_weight_norm_fwd(w_hat.data_ptr(), wsq.data_ptr(), scale.data_ptr(), w.data_ptr(), o, i, kh * kw,
+                                               _lib.stream_ptr(w)), 'weight_norm_fwd')
         ctx.save_for_backward(w_hat, scale)
         return w_hat, wsq
 
@@ -715,8 +715,8 @@ class _WeightNorm(torch.autograd.Function):
         g_hat = None if g_hat is None else g_hat.to(torch.float32).contiguous()
         g_wsq = None if g_wsq is None else g_wsq.to(torch.float32).contiguous()
         dw = torch.empty_like(w_hat)
-        _lib.check(lib.afcm_weight_norm_bwd(dw.data_ptr(), _lib.ptr(g_hat), _lib.ptr(g_wsq), w_hat.data_ptr(), scale.data_ptr(), o, i, kh * kw,
-                                            _lib.stream_ptr(w_hat)), 'weight_norm_bwd')
+        _lib.launched(lib.afcm_weight_norm_bwd(dw.data_ptr(), _lib.ptr(g_hat), _lib.ptr(g_wsq), w_hat.data_ptr(), scale.data_ptr(), o, i, kh * kw,
+                                               _lib.stream_ptr(w_hat)), 'weight_norm_bwd')
         return dw
 
 
@@ -734,8 +734,8 @@ class _StyleCoefs(torch.autograd.Function):
         r = torch.empty([1], dtype=torch.float32, device=t.device)
         wsq_c = wsq.detach().contiguous() if demodulate else None
         mag = None if magnitude is None else magnitude.detach().to(torch.float32).reshape(1)
-        _lib.check(lib.afcm_style_coefs_fwd(s_eff.data_ptr(), d.data_ptr() if demodulate else None, r.data_ptr(), t.data_ptr(), _lib.ptr(wsq_c),
-                                            _lib.ptr(mag), n, i, o, int(bool(demodulate)), _lib.stream_ptr(t)), 'style_coefs_fwd')
+        _lib.launched(lib.afcm_style_coefs_fwd(s_eff.data_ptr(), d.data_ptr() if demodulate else None, r.data_ptr(), t.data_ptr(), _lib.ptr(wsq_c),
+                                               _lib.ptr(mag), n, i, o, int(bool(demodulate)), _lib.stream_ptr(t)), 'style_coefs_fwd')
         ctx.save_for_backward(t, wsq_c, mag, d, r)
         ctx.demodulate = bool(demodulate)
         if not demodulate:
@@ -754,16 +754,22 @@ class _StyleCoefs(torch.autograd.Function):
         dt = torch.empty_like(t)
         g_wsq = torch.empty_like(wsq) if (ctx.demodulate and ctx.needs_input_grad[1]) else None
         ws = torch.empty([n * i + n * o + n * ((i + 63) // 64)], dtype=torch.float32, device=t.device)
-        _lib.check(lib.afcm_style_coefs_bwd(dt.data_ptr(), _lib.ptr(g_wsq), ws.data_ptr(), _lib.ptr(g_s), _lib.ptr(g_d), t.data_ptr(),
-                                            d.data_ptr() if ctx.demodulate else None, _lib.ptr(wsq), _lib.ptr(mag), r.data_ptr(), n, i, o,
-                                            int(ctx.demodulate), _lib.stream_ptr(t)), 'style_coefs_bwd')
+        _lib.launched(lib.afcm_style_coefs_bwd(dt.data_ptr(), _lib.ptr(g_wsq), ws.data_ptr(), _lib.ptr(g_s), _lib.ptr(g_d), t.data_ptr(),
+                                               d.data_ptr() if ctx.demodulate else None, _lib.ptr(wsq), _lib.ptr(mag), r.data_ptr(), n, i, o,
+                                               int(ctx.demodulate), _lib.stream_ptr(t)), 'style_coefs_bwd')
         return dt, g_wsq, None, None
+
+
+STYLE_CHANNELS_MAX = 16384
 
 
 def modulation_coefficients_fused(w, styles, demodulate=True, magnitude=None):
     """``modulation_coefficients`` with input_gain = magnitude.rsqrt() (the only form SynthesisLayer uses, NET:346) on the
     fused HIP kernels: 2 launches forward, 3 backward, instead of ~35 eager ones."""
     _lib.require_gpu(w, styles, magnitude)
+    # (the style kernels hold one row of I input / O output channels in LDS: csrc/modulation.hip style_coefs_fwd / _bwd)
+    if int(w.shape[1]) > STYLE_CHANNELS_MAX or (demodulate and int(w.shape[0]) > STYLE_CHANNELS_MAX):
+        raise RuntimeError(f'modulation: a {tuple(w.shape)} weight has more than {STYLE_CHANNELS_MAX} channels, the style kernels\' limit')
     if demodulate:
         w_hat, wsq = _WeightNorm.apply(w)
         s_eff, d = _StyleCoefs.apply(styles, wsq, magnitude, True)

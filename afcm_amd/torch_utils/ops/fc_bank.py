@@ -81,9 +81,9 @@ class _MappingInput(torch.autograd.Function):
             c, ew = c.contiguous(), ew.contiguous()
             eb = None if eb is None else eb.contiguous()
         x0 = torch.empty([n, zdim + (wdim if cdim else 0)], dtype=torch.float32, device=z.device)
-        _lib.check(lib.afcm_mapping_input_fwd(x0.data_ptr(), z.data_ptr(), _lib.ptr(c) if cdim else None, _lib.ptr(ew) if cdim else None,
-                                              _lib.ptr(eb) if cdim else None, n, zdim, cdim, wdim, float(alpha), float(beta), _lib.stream_ptr(z)),
-                   'mapping_input_fwd')
+        _lib.launched(lib.afcm_mapping_input_fwd(x0.data_ptr(), z.data_ptr(), _lib.ptr(c) if cdim else None, _lib.ptr(ew) if cdim else None,
+                                                 _lib.ptr(eb) if cdim else None, n, zdim, cdim, wdim, float(alpha), float(beta), _lib.stream_ptr(z)),
+                      'mapping_input_fwd')
         ctx.save_for_backward(c, ew, eb)
         ctx.cfg = (n, zdim, cdim, wdim, float(alpha), float(beta))
         return x0
@@ -104,8 +104,8 @@ class _MappingInput(torch.autograd.Function):
         if ws is None:
             # (zeroed once: the kernel leaves its ticket word at zero; one launch at a time per device and shape -- launches on one stream)
             ws = _MAPIN_WS[key] = torch.zeros([lib.afcm_mapping_input_bwd_workspace_bytes(n, wdim) // 4], dtype=torch.float32, device=gx0.device)
-        _lib.check(lib.afcm_mapping_input_bwd(dew.data_ptr(), _lib.ptr(deb), gx0.data_ptr(), c.data_ptr(), ew.data_ptr(), _lib.ptr(eb), n, zdim, cdim, wdim,
-                                              alpha, beta, ws.data_ptr(), _lib.stream_ptr(gx0)), 'mapping_input_bwd')
+        _lib.launched(lib.afcm_mapping_input_bwd(dew.data_ptr(), _lib.ptr(deb), gx0.data_ptr(), c.data_ptr(), ew.data_ptr(), _lib.ptr(eb), n, zdim, cdim, wdim,
+                                                 alpha, beta, ws.data_ptr(), _lib.stream_ptr(gx0)), 'mapping_input_bwd')
         return None, None, (dew if ctx.needs_input_grad[2] else None), deb, None, None
 
 

@@ -72,7 +72,7 @@ def _act_inplace(y, si, sx, sy, gain, slope, clamp, write_signs):
     rc = lib.afcm_filtered_lrelu_act(_lib.ptr(y), _lib.ptr(s), _lib.dtype_code(y), n, c, h, w,
                                      0 if s is None else s.shape[2], 0 if s is None else s.shape[3], sx, sy,
                                      gain, slope, clamp, mode, _lib.stream_ptr(y))
-    _lib.check(rc, 'filtered_lrelu_act_')
+    _lib.launched(rc, 'filtered_lrelu_act_')
     return so
 
 
@@ -158,7 +158,7 @@ def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, 
     a.sign_layout = si_layout if si is not None else 0
     a.b = _lib.ptr(b)                     # the kernel family (and with it the sign layout a WRITE call produces) depends on it
     a.x_pitch = xld if xld != x.shape[3] else 0         # (the kernel family may depend on the plane size in memory)
-    _lib.check(lib.afcm_filtered_lrelu_shapes(a), 'filtered_lrelu')
+    _lib.launched(lib.afcm_filtered_lrelu_shapes(a), 'filtered_lrelu')
     kld = 0
     if skip is not None:
         skip, kld = _rows.rows(skip)

@@ -112,9 +112,9 @@ class _ConvFilteredLRelu(torch.autograd.Function):
             dn32 = torch.empty([n, o], dtype=f32, device=g.device) if want_next else None
             do32 = torch.empty([n, o], dtype=f32, device=g.device) if want_out else None
             b32 = None if bias is None else bias.to(f32).contiguous()
-            _lib.check(lib.afcm_layer_bwd_coefs(_lib.ptr(db32), _lib.ptr(dn32), _lib.ptr(do32), psum.data_ptr(), int(psum.shape[2]), _lib.ptr(osc),
-                                                _lib.ptr(nsc), _lib.ptr(b32), _lib.ptr(gz if want_next else None), _lib.ptr(dysy), n, o, _lib.stream_ptr(g)),
-                       'layer_bwd_coefs')
+            _lib.launched(lib.afcm_layer_bwd_coefs(_lib.ptr(db32), _lib.ptr(dn32), _lib.ptr(do32), psum.data_ptr(), int(psum.shape[2]), _lib.ptr(osc),
+                                                   _lib.ptr(nsc), _lib.ptr(b32), _lib.ptr(gz if want_next else None), _lib.ptr(dysy), n, o, _lib.stream_ptr(g)),
+                          'layer_bwd_coefs')
             db = None if db32 is None else db32.to(bias.dtype)
             d_next = None if dn32 is None else dn32.to(next_scale.dtype)
             d_out = None if do32 is None else do32.to(out_scale.dtype)
@@ -183,11 +183,13 @@ def conv_filtered_lrelu(x, w, in_scale, out_scale, bias, fu, fd, up, down, paddi
 
 # ---- an encoder feature map that feeds the next encoder layer AND a decoder layer's skip input (NET:678-681, 371-377) ----------------------
 class _ForkState:
-    """What the decoder side tells the fork between forward and backward: the per-plane factor its epilogue applied to (F(y) + skip)."""
-    __slots__ = ('scale',)
+    """What the decoder side tells the fork between forward and backward: the per-plane factor its epilogue applied to (F(y) + skip).
+    Single use: the fork's backward takes it, and `spent` makes a second backward over the same graph (retain_graph) an error instead
+    of a silently unscaled skip gradient."""
+    __slots__ = ('scale', 'spent')
 
     def __init__(self):
-        self.scale = None
+        self.scale, self.spent = None, False
 
 
 class _SkipFork(torch.autograd.Function):
@@ -203,8 +205,11 @@ class _SkipFork(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, ga, gb):
+        if ctx.state.spent:
+            raise RuntimeError('skip_fork: the skip arm\'s style factor was consumed by an earlier backward over this graph; a second '
+                               'backward (retain_graph=True) through the fused generator layers is not supported -- run the forward again')
         scale = ctx.state.scale
-        ctx.state.scale = None
+        ctx.state.scale, ctx.state.spent = None, scale is not None
         if gb is None:
             return ga, None
         if ga is None:

@@ -70,7 +70,7 @@ class _ModulationBank(torch.autograd.Function):
                 L.scale = flat.data_ptr() + 4 * (off + o * i)
                 off += sizes[k]
                 k += 1
-        _lib.check(lib.afcm_modulation_bank_fwd(table, nl, n, _lib.stream_ptr(styles[0])), 'modulation_bank_fwd')
+        _lib.launched(lib.afcm_modulation_bank_fwd(table, nl, n, _lib.stream_ptr(styles[0])), 'modulation_bank_fwd')
         ctx.save_for_backward(flat, *w_hats, *styles, *ds, *[m for m in mags if m is not None])
         ctx.demods, ctx.has_mag, ctx.sizes = tuple(demods), tuple(m is not None for m in mags), sizes
         return tuple(w_hats) + tuple(s_effs) + tuple(ds)
@@ -125,7 +125,7 @@ class _ModulationBank(torch.autograd.Function):
                 L.dw = _lib.ptr(dw)
                 off += sizes[k]
                 k += 1
-        _lib.check(lib.afcm_modulation_bank_bwd(table, nl, n, _lib.stream_ptr(styles[0])), 'modulation_bank_bwd')
+        _lib.launched(lib.afcm_modulation_bank_bwd(table, nl, n, _lib.stream_ptr(styles[0])), 'modulation_bank_bwd')
         dts = [dt if nt else None for dt, nt in zip(dts, need_t)]
         return (None,) + tuple(dws) + tuple(dts) + (None,) * nl
 
