@@ -388,6 +388,306 @@ __global__ __launch_bounds__(NT) void flrelu_sep_kernel(FlreluParams p, const fl
 }
 
 // ---------------------------------------------------------------------------------------------
+// Radial (non-separable) forms of the tile kernel: one of the two filters is a full FD x FD (or FU x FU) 2-D filter, the
+// other stays separable.  StyleGAN3-R's layers produce exactly these two argument sets ("filtered_lrelu with
+// radial filters"):
+//   SUFD  separable up, 2-D down (forward of a radial layer): stages A-C as above, then D + E become one 2-D decimating FIR
+//         over the activated tile.  One item = 4 output columns x R2 output rows; every upsampled row the item reads feeds all
+//         the item's outputs whose tap window covers it, even / odd taps in the two halves of packed FMAs.
+//   FUSD  2-D up, separable down (backward of a radial layer): stage A as above, then B + C become one 2-D polyphase up-FIR
+//         + gain / activation / clamp / codes.  One item = 4 input columns x 2 input rows -> 8 x 4 upsampled elements; the x
+//         phase offset is folded into a 7-tap table with one zero (as in the strip kernel) so the two x phases of a column share
+//         an input and form one packed FMA.  Stages D and E as above.
+// The 2-D coefficient tables live in LDS and are read at wave-uniform addresses (broadcast).  Inside one upsampled / input row of
+// an item, the loops over its output rows and columns are unrolled: the row's data, read once, serves every output of the item
+// whose tap window covers it.  The loop over the item's rows stays ROLLED (#pragma unroll 1): unrolled, the compiler hoists every
+// LDS read of the item and spills (256 VGPRs and 0.4-1.5 KB of scratch per lane).  Sign codes use the tile family's layout 0.
+enum { FLRELU_SUFD = 1, FLRELU_FUSD = 2 };
+
+template <typename T, int MODE, int UP, int DOWN, int FUT, int FD, int TOW, int TOH, int RO, int NT, int SIGN>
+struct FlreluRadialTile : FlreluTile<T, UP, DOWN, FUT, FD, TOW, TOH, RO, NT, SIGN> {
+    typedef FlreluTile<T, UP, DOWN, FUT, FD, TOW, TOH, RO, NT, SIGN> B;
+    static constexpr int FU = B::FU, TUWP = B::TUWP, TUHP = B::TUHP, TIH = B::TIH, TIWP = B::TIWP, PU = B::PU, SGN_W = B::SGN_W;
+    // SUFD: 2-D down table [FD][FD] after the separable up tables; FUSD: 2-D up table [UP][FUT][16] (7 x-phase pairs + pad),
+    // then the separable down taps
+    static constexpr int R2 = 2;                                 // SUFD output rows per item
+    static constexpr int CU2_ROW = 16;
+    static constexpr int NCOEF = MODE == FLRELU_SUFD ? 2 * FU + FD * FD : UP * FUT * CU2_ROW + FD;
+    static constexpr int LDS_FLOATS = B::SZ_A + B::SZ_B + round_up(NCOEF, 4) + B::SGN_WORDS;
+    static_assert(MODE == FLRELU_SUFD || MODE == FLRELU_FUSD, "mode");
+    static_assert(MODE != FLRELU_SUFD || (DOWN % 2 == 0 && FD % 2 == 0 && TOH % R2 == 0 && TOW % 4 == 0), "SUFD item shape");
+    static_assert(MODE != FLRELU_FUSD || (UP == 2 && FUT == 6 && TUHP % 4 == 0 && (TUWP / 8) % 2 == 0), "FUSD item shape");
+    static_assert(MODE != FLRELU_FUSD || B::SZ_B >= TIH * TIWP, "FUSD stages the input tile in the second buffer");
+    static_assert((2 * FU) % 4 == 0, "2-D down table must start on a 16-byte boundary");
+    static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS overflow");
+
+    // ---- SUFD stage D': 2-D decimating FIR + store.  upXY rows DOWN * p0 + i, i < DOWN * (R2 - 1) + FD.
+    static __device__ __forceinline__ void down_2d_store(const float* __restrict__ upXY, const float* __restrict__ cd2, int tid,
+                                                         const FlreluParams& p, int plane, int O0x, int O0y) {
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        constexpr int NC4 = TOW / 4;
+        constexpr int NROW = DOWN * (R2 - 1) + FD;
+        constexpr int NIN4 = cdiv(DOWN * 3 + FD, 4);
+        T* yp = (T*)p.y + (size_t)plane * p.yh * p.yw;
+        for (int item = tid; item < NC4 * (TOH / R2); item += NT) {
+            const int rbk = item / NC4, c4 = item - rbk * NC4;
+            const int p0 = rbk * R2;
+            f32x2 acc[R2][4];
+#pragma unroll
+            for (int t = 0; t < R2; t++)
+#pragma unroll
+                for (int o = 0; o < 4; o++) acc[t][o] = (f32x2){0.f, 0.f};
+#pragma unroll 1
+            for (int i = 0; i < NROW; i++) {                     // (rolled: unrolled, the compiler hoists every LDS read and spills)
+                const float* src = upXY + (DOWN * p0 + i) * PU + DOWN * 4 * c4;
+                float in[NIN4 * 4];
+#pragma unroll
+                for (int q = 0; q < NIN4; q++) {
+                    const float4 v = *(const float4*)(src + 4 * q);
+                    in[4 * q] = v.x; in[4 * q + 1] = v.y; in[4 * q + 2] = v.z; in[4 * q + 3] = v.w;
+                }
+#pragma unroll
+                for (int t = 0; t < R2; t++) {
+                    const int k = i - DOWN * t;
+                    if (k >= 0 && k < FD) {
+                        float c[FD];
+#pragma unroll
+                        for (int q = 0; q < FD / 4; q++) {
+                            const float4 v = *(const float4*)(cd2 + k * FD + 4 * q);
+                            c[4 * q] = v.x; c[4 * q + 1] = v.y; c[4 * q + 2] = v.z; c[4 * q + 3] = v.w;
+                        }
+#pragma unroll
+                        for (int o = 0; o < 4; o++)
+#pragma unroll
+                            for (int k2 = 0; k2 < FD / 2; k2++)
+                                acc[t][o] = __builtin_elementwise_fma((f32x2){c[2 * k2], c[2 * k2 + 1]},
+                                                                      (f32x2){in[DOWN * o + 2 * k2], in[DOWN * o + 2 * k2 + 1]}, acc[t][o]);
+                    }
+                }
+            }
+            const int ox = O0x + 4 * c4;
+#pragma unroll
+            for (int t = 0; t < R2; t++) {
+                const int oy = O0y + p0 + t;
+                if (oy < p.yh) {
+                    T* dst = yp + (size_t)oy * p.yw + ox;
+                    float v[4];
+#pragma unroll
+                    for (int o = 0; o < 4; o++) v[o] = acc[t][o].x + acc[t][o].y;
+                    if (sizeof(T) == 4 && ox + 3 < p.yw && (p.yw & 3) == 0) {
+                        *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
+                    } else {
+#pragma unroll
+                        for (int o = 0; o < 4; o++)
+                            if (ox + o < p.yw) dst[o] = from_f32<T>(v[o]);
+                    }
+                }
+            }
+        }
+    }
+
+    // ---- FUSD stage B': 2-D polyphase up-FIR + gain + leaky ReLU + clamp + sign codes.  sIn -> upXY (pitch PU).
+    template <int PHY>
+    static __device__ __forceinline__ void up_2d_act(const float* __restrict__ sIn, float* __restrict__ upXY,
+                                                     const float* __restrict__ cu2, const unsigned* __restrict__ sgn, int tid,
+                                                     const FlreluParams& p, int plane, int U0x, int U0y, bool lastX, bool lastY) {
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        constexpr int MB2 = 2;                                   // input rows per item (4 upsampled rows)
+        constexpr int NCH = TUWP / 8;                            // 4-input-column chunks per row (8 upsampled columns)
+        constexpr int NRB = TUHP / (MB2 * UP);
+        constexpr int NINR = MB2 + FUT;
+        unsigned char* splane = p.s + (size_t)plane * p.sh * p.swb;
+        for (int item = tid; item < NCH * NRB; item += NT) {
+            const int rb = item / NCH, ch = item - rb * NCH;      // consecutive lanes -> consecutive chunks (lane pairs share a dword)
+            f32x2 acc[MB2][UP][4];                              // (x phase 0, x phase 1) of input column mx, upsampled row (mm, ay)
+#pragma unroll
+            for (int mm = 0; mm < MB2; mm++)
+#pragma unroll
+                for (int ay = 0; ay < UP; ay++)
+#pragma unroll
+                    for (int mx = 0; mx < 4; mx++) acc[mm][ay][mx] = (f32x2){0.f, 0.f};
+#pragma unroll 1
+            for (int ri = 0; ri < NINR; ri++) {                  // (rolled, as in down_2d_store)
+                const float* src = sIn + (rb * MB2 + ri) * TIWP + 4 * ch;
+                float in[12];
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    const float4 v = *(const float4*)(src + 4 * q);
+                    in[4 * q] = v.x; in[4 * q + 1] = v.y; in[4 * q + 2] = v.z; in[4 * q + 3] = v.w;
+                }
+#pragma unroll
+                for (int mm = 0; mm < MB2; mm++)
+#pragma unroll
+                    for (int ay = 0; ay < UP; ay++) {
+                        const int jy = ri - mm - ((ay > PHY) ? 1 : 0);
+                        if (jy >= 0 && jy < FUT) {
+                            f32x2 c[7];
+                            const float* crow = cu2 + (ay * FUT + jy) * CU2_ROW;
+#pragma unroll
+                            for (int q = 0; q < 4; q++) {
+                                const float4 v = *(const float4*)(crow + 4 * q);
+                                if (2 * q < 7) c[2 * q] = (f32x2){v.x, v.y};
+                                if (2 * q + 1 < 7) c[2 * q + 1] = (f32x2){v.z, v.w};
+                            }
+#pragma unroll
+                            for (int mx = 0; mx < 4; mx++)
+#pragma unroll
+                                for (int t = 0; t < 7; t++)
+                                    acc[mm][ay][mx] = __builtin_elementwise_fma(c[t], (f32x2){in[mx + t], in[mx + t]}, acc[mm][ay][mx]);
+                        }
+                    }
+            }
+            const int X = U0x + 8 * ch;
+            const int sbit = (((U0x + p.sx) & 15) + 8 * ch) * 2;  // READ mode: bit offset of the chunk's 8 codes in the staged window
+            const int sw0 = sbit >> 5, sshift = sbit & 31;
+#pragma unroll
+            for (int mm = 0; mm < MB2; mm++)
+#pragma unroll
+                for (int ay = 0; ay < UP; ay++) {
+                    const int row = rb * MB2 * UP + mm * UP + ay;
+                    const int Y = U0y + row;
+                    unsigned codes = 0;
+                    if (SIGN == AFCM_SIGNS_READ) {
+                        const unsigned lo = sgn[row * SGN_W + sw0];
+                        const unsigned hi = (sw0 + 1 < SGN_W) ? sgn[row * SGN_W + sw0 + 1] : 0u;
+                        codes = __builtin_amdgcn_alignbit(hi, lo, sshift) & 0xffffu;
+                    }
+                    float v[8];
+                    unsigned bits = 0;
+#pragma unroll
+                    for (int mx = 0; mx < 4; mx++) {
+                        v[2 * mx] = acc[mm][ay][mx].x;
+                        v[2 * mx + 1] = acc[mm][ay][mx].y;
+                    }
+#pragma unroll
+                    for (int e = 0; e < 8; e++) bits |= act_elem<SIGN>(v[e], p.gain, p.slope, p.clamp, codes >> (2 * e)) << (2 * e);
+                    float* dst = upXY + row * PU + 8 * ch;
+                    *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
+                    *(float4*)(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
+                    if (SIGN == AFCM_SIGNS_WRITE) {
+                        // 2 lanes of a pair hold 16 consecutive columns: assemble one dword
+                        int word = (int)(bits << ((ch & 1) << 4));
+                        word |= __builtin_amdgcn_mov_dpp(word, 0xB1, 0xF, 0xF, true);     // quad_perm [1,0,3,2]
+                        const bool ownX = (8 * ch < TOW * DOWN) || lastX;
+                        const bool ownY = (row < TOH * DOWN) || lastY;
+                        if ((ch & 1) == 0 && ownX && ownY && (X >> 2) < p.swb && Y < p.sh)
+                            *(int*)(splane + (size_t)Y * p.swb + (X >> 2)) = word;
+                    }
+                }
+        }
+    }
+};
+
+template <typename T, int MODE, int UP, int DOWN, int FUT, int FD, int TOW, int TOH, int RO, int NT, int SIGN>
+__global__ __launch_bounds__(NT) void flrelu_radial_kernel(FlreluParams p, const float* __restrict__ fu,
+                                                           const float* __restrict__ fd) {
+    typedef FlreluRadialTile<T, MODE, UP, DOWN, FUT, FD, TOW, TOH, RO, NT, SIGN> K;
+    __shared__ __attribute__((aligned(16))) float lds[K::LDS_FLOATS];
+    float* bufA = lds;
+    float* bufB = lds + K::SZ_A;
+    float* coef = lds + K::SZ_A + K::SZ_B;
+    unsigned* sgn = (unsigned*)(lds + K::SZ_A + K::SZ_B + round_up(K::NCOEF, 4));
+
+    const int tid = threadIdx.x;
+    int bid = xcd_order(blockIdx.x, gridDim.x);
+    const int tx = bid % p.tilesX;
+    bid /= p.tilesX;
+    const int ty = bid % p.tilesY;
+    const int plane = bid / p.tilesY;
+
+    const int O0x = tx * TOW, O0y = ty * TOH;
+    const int U0x = O0x * DOWN, U0y = O0y * DOWN;
+    const int I0x = -floor_div(p.px0 - U0x, UP), phx = pos_mod(p.px0 - U0x, UP);
+    const int I0y = -floor_div(p.py0 - U0y, UP), phy = pos_mod(p.py0 - U0y, UP);
+
+    // coefficient tables (flip_filter flips both axes of a 2-D filter: F2[ky][kx] = flip ? f[ky][kx] : f[n-1-ky][n-1-kx])
+    if constexpr (MODE == FLRELU_SUFD) {
+        float* cuX = coef;
+        float* cuY = coef + K::FU;
+        float* cd2 = coef + 2 * K::FU;
+        if (tid < K::FU) {
+            const int a = tid / FUT, j = tid - a * FUT;
+            const int kx = ((a > phx) ? UP - (a - phx) : phx - a) + UP * j;
+            const int ky = ((a > phy) ? UP - (a - phy) : phy - a) + UP * j;
+            cuX[tid] = p.flip ? fu[kx] : fu[K::FU - 1 - kx];
+            cuY[tid] = p.flip ? fu[ky] : fu[K::FU - 1 - ky];
+        }
+        for (int i = tid; i < FD * FD; i += NT) cd2[i] = p.flip ? fd[i] : fd[FD * FD - 1 - i];
+    } else {
+        float* cu2 = coef;
+        float* cdl = coef + UP * FUT * K::CU2_ROW;
+        for (int i = tid; i < UP * FUT * K::CU2_ROW; i += NT) {
+            const int row = i / K::CU2_ROW, e = i - row * K::CU2_ROW;
+            const int ay = row / FUT, jy = row - ay * FUT;
+            const int t = e >> 1, ax = e & 1;
+            const int jx = t - ((ax > phx) ? 1 : 0);
+            float v = 0.f;
+            if (t < 7 && jx >= 0 && jx < FUT) {
+                const int ky = ((ay > phy) ? UP - (ay - phy) : phy - ay) + UP * jy;
+                const int kx = ((ax > phx) ? UP - (ax - phx) : phx - ax) + UP * jx;
+                v = p.flip ? fu[ky * K::FU + kx] : fu[(K::FU - 1 - ky) * K::FU + (K::FU - 1 - kx)];
+            }
+            cu2[i] = v;
+        }
+        if (tid < FD) cdl[tid] = p.flip ? fd[tid] : fd[FD - 1 - tid];
+    }
+
+    // stage A (as in flrelu_sep_kernel).  FUSD stages the input tile in bufB: its 2-D up stage writes the activated tile to bufA.
+    {
+        float* sIn = MODE == FLRELU_FUSD ? bufB : bufA;
+        const T* xp = (const T*)p.x + (size_t)plane * p.xh * p.xw;
+        const float bias = p.b ? to_f32(((const T*)p.b)[plane % p.C]) : 0.f;
+        constexpr int NLD = cdiv(K::TIH * K::TIWP, NT);
+        T raw[NLD];
+        bool ok[NLD];
+#pragma unroll
+        for (int i = 0; i < NLD; i++) {
+            const int idx = tid + i * NT;
+            const int r = idx / K::TIWP, c = idx - r * K::TIWP;
+            const int iy = I0y + r, ix = I0x + c;
+            ok[i] = (idx < K::TIH * K::TIWP) && (unsigned)ix < (unsigned)p.xw && (unsigned)iy < (unsigned)p.xh;
+            raw[i] = ok[i] ? xp[(size_t)iy * p.xw + ix] : from_f32<T>(0.f);
+        }
+        if (SIGN == AFCM_SIGNS_READ) K::stage_signs(sgn, p, plane, U0x, U0y, tid);
+#pragma unroll
+        for (int i = 0; i < NLD; i++) {
+            const int idx = tid + i * NT;
+            if (idx < K::TIH * K::TIWP) sIn[idx] = ok[i] ? to_f32(raw[i]) + bias : 0.f;
+        }
+    }
+    __syncthreads();
+    const bool lastX = (tx == p.tilesX - 1), lastY = (ty == p.tilesY - 1);
+    if constexpr (MODE == FLRELU_SUFD) {
+        const float* cuX = coef;
+        const float* cuY = coef + K::FU;
+        switch (phx) {
+            case 0: K::template up_x<0>(bufA, bufB, cuX, tid); break;
+            case 1: K::template up_x<1>(bufA, bufB, cuX, tid); break;
+            case 2: if (UP > 2) K::template up_x<(UP > 2 ? 2 : 0)>(bufA, bufB, cuX, tid); break;
+            default: if (UP > 2) K::template up_x<(UP > 2 ? 3 : 0)>(bufA, bufB, cuX, tid); break;
+        }
+        __syncthreads();
+        switch (phy) {
+            case 0: K::template up_y_act<0>(bufB, bufA, cuY, sgn, tid, p, plane, U0x, U0y, lastX, lastY); break;
+            case 1: K::template up_y_act<1>(bufB, bufA, cuY, sgn, tid, p, plane, U0x, U0y, lastX, lastY); break;
+            case 2: if (UP > 2) K::template up_y_act<(UP > 2 ? 2 : 0)>(bufB, bufA, cuY, sgn, tid, p, plane, U0x, U0y, lastX, lastY); break;
+            default: if (UP > 2) K::template up_y_act<(UP > 2 ? 3 : 0)>(bufB, bufA, cuY, sgn, tid, p, plane, U0x, U0y, lastX, lastY); break;
+        }
+        __syncthreads();
+        K::down_2d_store(bufA, coef + 2 * K::FU, tid, p, plane, O0x, O0y);
+    } else {
+        const float* cu2 = coef;
+        const float* cdl = coef + UP * FUT * K::CU2_ROW;
+        if (phy == 0) K::template up_2d_act<0>(bufB, bufA, cu2, sgn, tid, p, plane, U0x, U0y, lastX, lastY);
+        else K::template up_2d_act<1>(bufB, bufA, cu2, sgn, tid, p, plane, U0x, U0y, lastX, lastY);
+        __syncthreads();
+        K::down_x(bufA, bufB, cdl, tid);
+        __syncthreads();
+        K::down_y_store(bufB, cdl, tid, p, plane, O0x, O0y);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Pointwise form: up = down = 1 with 1x1 filters (the ToRGB layer, NET:369-372) and the in-place
 // activation of the generic fallback (filtered_lrelu_act_, filtered_lrelu.cu:1105-1211).
 // One thread = 16 consecutive columns of one row = one sign dword.
@@ -762,6 +1062,27 @@ static int launch_sep(const afcm_filtered_lrelu_args* a, FlreluParams p, hipStre
     return hip_status(hipGetLastError());
 }
 
+template <typename T, int MODE, int UP, int DOWN, int FUT, int FD, int TOW, int TOH, int RO, int NT>
+static int launch_radial(const afcm_filtered_lrelu_args* a, FlreluParams p, hipStream_t st) {
+    p.tilesX = cdiv(a->yw, TOW);
+    p.tilesY = cdiv(a->yh, TOH);
+    const long long blocks = (long long)p.tilesX * p.tilesY * a->n * a->c;
+    AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "filtered_lrelu: grid of %lld blocks is out of range", blocks);
+    dim3 grid((unsigned)blocks), block(NT);
+    switch (a->sign_mode) {
+        case AFCM_SIGNS_NONE:
+            hipLaunchKernelGGL((flrelu_radial_kernel<T, MODE, UP, DOWN, FUT, FD, TOW, TOH, RO, NT, AFCM_SIGNS_NONE>), grid, block, 0, st, p, a->fu, a->fd);
+            break;
+        case AFCM_SIGNS_WRITE:
+            hipLaunchKernelGGL((flrelu_radial_kernel<T, MODE, UP, DOWN, FUT, FD, TOW, TOH, RO, NT, AFCM_SIGNS_WRITE>), grid, block, 0, st, p, a->fu, a->fd);
+            break;
+        default:
+            hipLaunchKernelGGL((flrelu_radial_kernel<T, MODE, UP, DOWN, FUT, FD, TOW, TOH, RO, NT, AFCM_SIGNS_READ>), grid, block, 0, st, p, a->fu, a->fd);
+            break;
+    }
+    return hip_status(hipGetLastError());
+}
+
 template <typename T, int UP, int DOWN, int CPL>
 static int launch_strip(const afcm_filtered_lrelu_args* a, FlreluParams p, hipStream_t st) {
     p.tilesX = a->sign_mode == AFCM_SIGNS_WRITE ? cdiv(a->yw, StripGeom<UP, DOWN, CPL, AFCM_SIGNS_WRITE>::SW) : cdiv(a->yw, StripGeom<UP, DOWN, CPL, AFCM_SIGNS_NONE>::SW);
@@ -831,6 +1152,16 @@ static int dispatch(const afcm_filtered_lrelu_args* a, const FlreluParams& p, hi
     if (sep && a->up == 4 && a->down == 2 && a->fuw == 24 && a->fdw == 12) {
         return launch_sep<T, 4, 2, 6, 12, 64, 20, 5, 384>(a, p, st);      // (20-row tiles: 47 KB of LDS, faster than 35 rows in every mode)
     }
+    // radial layers (StyleGAN3-R): a 12 x 12 2-D down filter in the forward, the same filter as a 2-D up filter in the backward
+    const bool sufd = a->fuh == 0 && a->fdh != 0, fusd = a->fuh != 0 && a->fdh == 0;
+    if (sufd && a->up == 2 && a->down == 2 && a->fuw == 12 && a->fdw == 12 && a->fdh == 12)
+        return launch_radial<T, FLRELU_SUFD, 2, 2, 6, 12, 64, 20, 5, 384>(a, p, st);
+    if (sufd && a->up == 4 && a->down == 2 && a->fuw == 24 && a->fdw == 12 && a->fdh == 12)
+        return launch_radial<T, FLRELU_SUFD, 4, 2, 6, 12, 64, 20, 5, 384>(a, p, st);
+    if (fusd && a->up == 2 && a->down == 2 && a->fuw == 12 && a->fuh == 12 && a->fdw == 12)
+        return launch_radial<T, FLRELU_FUSD, 2, 2, 6, 12, 64, 20, 5, 384>(a, p, st);
+    if (fusd && a->up == 2 && a->down == 4 && a->fuw == 12 && a->fuh == 12 && a->fdw == 24)
+        return launch_radial<T, FLRELU_FUSD, 2, 4, 6, 24, 32, 12, 4, 384>(a, p, st);
     return AFCM_E_NOKERNEL;
 }
 

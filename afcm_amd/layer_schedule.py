@@ -83,6 +83,9 @@ def plan(img_resolution=256, img_channels_in=4, img_channels_out=1, synthesis_kw
     bs = band_schedule(img_resolution, img_channels_out, n, kw['num_critical'], kw['first_cutoff'], kw['first_stopband'],
                        kw['last_stopband_rel'], kw['margin_size'], kw['channel_base'], kw['channel_max'])
     cut, hw, sr, sizes, sizes_e, ch = (bs[k] for k in ('cutoffs', 'half_widths', 'sampling_rates', 'sizes', 'sizes_for_encoder', 'channels'))
+    # use_radial_filters: the down filter of every layer that is not critically sampled is the 2-D radial filter (NET:318-319).
+    # That is decoder idx < n - num_critical and encoder idx >= n - num_critical: the encoder gets the flag inverted (NET:617).
+    radial, n_crit = bool(kw['use_radial_filters']), kw['num_critical']
     enc, dec = [], []
     for idx in range(n):
         r = n - idx - 1
@@ -91,7 +94,8 @@ def plan(img_resolution=256, img_channels_in=4, img_channels_out=1, synthesis_kw
                                                            kw['conv_kernel'], kw['filter_size'], kw['lrelu_upsampling'])
         enc.append(dict(name=f'encoder_{idx}', cin=img_channels_in if idx == 0 else int(ch[rp]), cout=int(ch[r]),
                         in_size=int(sizes_e[rp]), out_size=int(sizes_e[r]), k=kw['conv_kernel'], up=up, down=down, padding=pad,
-                        fu=design_lowpass_filter(ut, cut[rp], hw[rp] * 2, tmp_sr), fd=design_lowpass_filter(dt, cut[r], hw[r] * 2, tmp_sr),
+                        fu=design_lowpass_filter(ut, cut[rp], hw[rp] * 2, tmp_sr),
+                        fd=design_lowpass_filter(dt, cut[r], hw[r] * 2, tmp_sr, radial=radial and idx >= n - n_crit),
                         torgb=False, modulated=False))
     for idx in range(n + 1):
         p = max(idx - 1, 0)
@@ -101,7 +105,8 @@ def plan(img_resolution=256, img_channels_in=4, img_channels_out=1, synthesis_kw
                                                            kw['filter_size'], kw['lrelu_upsampling'], torgb)
         dec.append(dict(name=f'L{idx}_{int(sizes[idx])}_{int(ch[idx])}', cin=int(ch[p]), cout=int(ch[idx]), in_size=int(sizes[p]),
                         out_size=int(sizes[idx]), k=k, up=up, down=down, padding=pad,
-                        fu=design_lowpass_filter(ut, cut[p], hw[p] * 2, tmp_sr), fd=design_lowpass_filter(dt, cut[idx], hw[idx] * 2, tmp_sr),
+                        fu=design_lowpass_filter(ut, cut[p], hw[p] * 2, tmp_sr),
+                        fd=design_lowpass_filter(dt, cut[idx], hw[idx] * 2, tmp_sr, radial=radial and idx < n - n_crit),
                         torgb=torgb, modulated=True))
     return dict(enc=enc, dec=dec, schedule=bs, kw=kw)
 
@@ -116,11 +121,12 @@ def algorithmic_work(pl, batch, elem_size):
     conv_flops = 0
     for L in pl['enc'] + pl['dec']:
         h = L['in_size'] + L['k'] - 1
-        fuw = 1 if L['fu'] is None else len(L['fu'])
-        fdw = 1 if L['fd'] is None else len(L['fd'])
-        sh = L['out_size'] * L['down'] - (L['down'] - 1) + fdw - 1
-        swb = ((sh + 15) & ~15) // 4
+        # sign grid: rows from the down filter's height, dword-padded columns from its width (a radial filter is square)
+        fdh = 1 if L['fd'] is None else int(L['fd'].shape[0])
+        fdw = 1 if L['fd'] is None else int(L['fd'].shape[-1])
+        sh = L['out_size'] * L['down'] - (L['down'] - 1) + fdh - 1
+        sw = L['out_size'] * L['down'] - (L['down'] - 1) + fdw - 1
+        swb = ((sw + 15) & ~15) // 4
         fl_bytes += batch * L['cout'] * (elem_size * (h * h + L['out_size'] ** 2) + sh * swb)
         conv_flops += batch * 2 * L['cout'] * L['cin'] * L['k'] ** 2 * h * h
-        del fuw
     return dict(filtered_lrelu_bytes=fl_bytes, conv_flops=conv_flops)

@@ -6,9 +6,12 @@ gain=sqrt(2), slope=0.2, clamp=None, flip_filter=False, impl='cuda')`` (SG3OPS/f
 ``impl='cuda'`` on a ROCm tensor runs the HIP kernel ``afcm_filtered_lrelu``.  As in the reference
 (SG3OPS/filtered_lrelu.py:159-272) the forward pass keeps only a 2-bit-per-element sign/clamp tensor,
 and the backward pass is the same op with up/down and the filters swapped, reading those codes; so
-``dx`` is again differentiable.  Parameter combinations without a fused kernel (non-separable filters,
-other tap counts) take the generic path upfirdn2d -> in-place activation kernel -> upfirdn2d, also on
-the GPU (SG3OPS/filtered_lrelu.py:223-229) -- never a CPU path.
+``dx`` is again differentiable.  The fused kernels cover the separable 12 / 24-tap cases of the generator
+and the radial (StyleGAN3-R) cases, where one of the two filters is a 12 x 12 2-D filter: separable up with
+2-D down (up 2 or 4, down 2: a radial layer's forward) and 2-D up with separable down (up 2, down 2 or 4: its
+backward).  Other parameter combinations (other tap counts, two 2-D filters, other factors) take the generic
+path upfirdn2d -> in-place activation kernel -> upfirdn2d, also on the GPU (SG3OPS/filtered_lrelu.py:223-229)
+-- never a CPU path.
 """
 import collections
 import warnings
@@ -215,16 +218,25 @@ def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, 
     if rc == _lib.E_NOKERNEL and no_fallback:
         raise NoFusedKernel()
     if rc == _lib.E_NOKERNEL:
-        # Generic path, still on the GPU and still keeping only the packed signs for backward.
         warnings.warn('filtered_lrelu called with parameters that have no fused HIP kernel, using generic fallback', RuntimeWarning)
-        y = x if b is None else x + b.reshape(1, -1, 1, 1)
-        y = _ufd._forward_raw(y, fu, (up, up), (1, 1), (px0, px1, py0, py1), flip_filter, float(up ** 2))
-        if y is x:
-            y = y.clone()
-        so = _act_inplace(y, si, sx, sy, gain, slope, clamp, write_signs)
-        y = _ufd._forward_raw(y, fd, (1, 1), (down, down), (0, 0, 0, 0), flip_filter, 1.0)
+        y, so = _run_generic(x, fu, fd, b, si, cfg, write_signs)
         layout, psum = 0, None
     return y, so, layout, psum
+
+
+def _run_generic(x, fu, fd, b, si, cfg, write_signs):
+    """The generic path of _run: upfirdn2d up -> in-place activation -> upfirdn2d down, still on the GPU and still keeping only
+    the packed signs (layout 0) for backward.  Returns (y, signs written or None).  Separate so that a tool can time it against
+    the fused kernel on the same arguments."""
+    up, down, px0, px1, py0, py1, gain, slope, clamp, flip_filter, sx, sy, _ = cfg
+    x = _rows.dense(x)
+    y = x if b is None else x + b.reshape(1, -1, 1, 1)
+    y = _ufd._forward_raw(y, fu, (up, up), (1, 1), (px0, px1, py0, py1), flip_filter, float(up ** 2))
+    if y is x:
+        y = y.clone()
+    so = _act_inplace(y, si, sx, sy, gain, slope, clamp, write_signs)
+    y = _ufd._forward_raw(y, fd, (1, 1), (down, down), (0, 0, 0, 0), flip_filter, 1.0)
+    return y, so
 
 
 def _backward_cfg(cfg, fu, fd, x_shape, y_shape, sign_layout):

@@ -116,6 +116,9 @@ typedef struct afcm_filtered_lrelu_args {
 /* Output / sign-tensor geometry for the arguments above (filtered_lrelu.cpp:61-94). Fills yh, yw
  * and, for WRITE mode, sh, swb.  Pure host arithmetic. */
 int afcm_filtered_lrelu_shapes(afcm_filtered_lrelu_args* a);
+/* Fused argument sets: the separable 12 / 24-tap cases (up 2 / down 2, up 2 / down 4, up 4 / down 2), and the radial ones, where
+ * one filter is 12 x 12 (fuh / fdh = 12) and the other separable: fu 12 or 24 taps with fd 12 x 12 (up 2 or 4, down 2), and fu 12 x 12
+ * with fd 12 or 24 taps (up 2, down 2 or 4).  Their sign tensors use layout 0.  Every other 2-D argument set returns AFCM_E_NOKERNEL. */
 int afcm_filtered_lrelu(const afcm_filtered_lrelu_args* a, void* stream);
 
 /* Matrix-core path (16-bit dtypes, the separable 12/24-tap cases of the generator): the FIR passes run as banded
