@@ -8,37 +8,19 @@
 //   B = activations (MFMA cols = output pixels), NCHW in HBM, transposed to [pixel][channel] while staging
 //       into LDS so that every tap is a pure address offset of the same LDS patch (im2col never exists)
 //   D = fp32 accumulators in registers; the per-(n,o) scale is applied in the epilogue.
-// bf16/f16 use v_mfma_f32_32x32x16_{bf16,f16}; fp32 uses v_mfma_f32_32x32x2_f32 (exact fp32, for the <=1e-3 parity path).
-// The same kernel computes the data gradient (weights packed transposed + flipped, pad' = k-1-pad).
+// 16-bit 3x3 convs use v_mfma_f32_16x16x32_{bf16,f16} (conv2d_fwd16x_kernel), the stride-2 and 16-bit 1x1 convs v_mfma_f32_32x32x16_{bf16,f16};
+// fp32 uses v_mfma_f32_32x32x2_f32 (exact fp32, for the <=1e-3 parity path).
+// The same kernels compute the data gradient (weights packed transposed + flipped, pad' = k-1-pad).  The weight gradient is in
+// conv2d_wgrad.hip, the per-plane passes (scaling, dot products, the fp32 split) in conv2d_planes.hip.
 #include <stdlib.h>
 #include <string.h>
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv2d_common.h"
+#include "flrelu_mfma_common.h"      // pack2<T>: one v_cvt_pk of exactly a pair
 
 namespace afcm {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) float cf32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 cbf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 cf16x2;
-
-// two fp32 values -> one dword of two 16-bit floats (one v_cvt_pk of exactly this pair, round to nearest even)
-template <typename T>
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        union { cbf16x2 v; unsigned u; } r;
-        r.v = __builtin_convertvector((cf32x2){lo, hi}, cbf16x2);
-        return r.u;
-    } else {
-        union { cf16x2 v; unsigned u; } r;
-        r.v = __builtin_convertvector((cf32x2){lo, hi}, cf16x2);
-        return r.u;
-    }
-}
 
 template <typename T> struct ConvCfg;
 template <> struct ConvCfg<bf16_t> { static constexpr int BK = 16, PITCH = 24; };   // elements; 48-byte rows: conflict-free b128
@@ -77,14 +59,6 @@ struct ConvParams {
     int nkc_real; unsigned magicNK, term_parts; int part_bytes, last_part_bytes;   // last_part_bytes: offset of the highest part any term reads
     const unsigned* bound_a; const unsigned* bound_b;   // magnitude-bound words of the two operands (or null): their power-of-two factors are undone in the epilogue
 };
-// the power of two g with g * bound in [2^14, 2^15) for a magnitude-bound word (amax_bits_kernel); *inverse = 1 / g
-__device__ __forceinline__ float pow2_factor(unsigned bound_bits, float* inverse = nullptr) {
-    const float b = __uint_as_float(bound_bits);
-    int e = 15;                                              // non-finite bound (a NaN fails the comparison): g = 1
-    if (b <= 3.4028234664e38f) frexpf(fmaxf(b, 1e-30f), &e); // b = f * 2^e, f in [0.5, 1)
-    if (inverse) *inverse = ldexpf(1.f, e - 15);
-    return ldexpf(1.f, 15 - e);
-}
 
 __host__ __device__ inline unsigned magic_u32(unsigned d) { return (unsigned)((0x100000000ull + d - 1) / d); }   // 0 for d = 1 (see udiv_magic)
 __device__ __forceinline__ unsigned udiv_magic(unsigned n, unsigned magic) { return magic ? __umulhi(n, magic) : n; }
@@ -1292,161 +1266,6 @@ __global__ __launch_bounds__(256) void conv2d_pack_bank_kernel(const PackBank b)
     pack_tile_body<T, KK, BK>(tile, loc % b.gx[l], loc / b.gx[l], (T*)e.dst_fwd, (T*)e.dst_dgrad, e.w, e.cout, e.cin, e.rows_pad_fwd, e.rows_pad_dgrad);
 }
 
-// 4 consecutive elements as one vector access (8 B for 16-bit types, 16 B for fp32); planes are 4-element aligned when hw % 4 == 0
-template <typename T> struct Vec4 { T v[4]; } __attribute__((aligned(sizeof(T) * 4)));
-
-// y[plane, :] = x[plane, :] * scale[plane]  (dtype conversion fused).  HBM-bound elementwise pass.
-template <typename TI, typename TO>
-__global__ __launch_bounds__(256) void scale_planes_kernel(TO* __restrict__ y, const TI* __restrict__ x, const float* __restrict__ scale,
-                                                           long long planes, int hw) {
-    const int per = (hw + 3) >> 2;
-    const long long total = planes * per;
-    const bool vec = (hw & 3) == 0;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const long long plane = idx / per;
-        const int i0 = (int)(idx - plane * per) << 2;
-        const float sc = scale ? scale[plane] : 1.f;
-        const TI* xp = x + plane * hw + i0;
-        TO* yp = y + plane * hw + i0;
-        if (vec) {
-            const Vec4<TI> in = *(const Vec4<TI>*)xp;
-            Vec4<TO> out;
-#pragma unroll
-            for (int e = 0; e < 4; e++) out.v[e] = from_f32<TO>(to_f32(in.v[e]) * sc);
-            *(Vec4<TO>*)yp = out;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                if (i0 + e < hw) yp[e] = from_f32<TO>(to_f32(xp[e]) * sc);
-        }
-    }
-}
-
-// y[plane, :] = a[plane, :] + scale[plane] * b[plane, :] for 16-bit tensors of one layout (r06): the gradient of an encoder feature map that
-// feeds BOTH the next encoder layer (a = that layer's data gradient) and a decoder layer's skip input (b = the decoder layer's incoming
-// gradient, scale = the styles its epilogue multiplied the sum by).  The op-by-op form was scale_planes (read b, write s b) + autograd's
-// accumulation (read both, write the sum): five passes over a 156 MB plane set where this is three, one rounding instead of two.
-// 16-byte vectors; hw % 8 == 0 (host).
-template <typename T>
-__global__ __launch_bounds__(256) void axpy_planes_kernel(T* __restrict__ y, const T* __restrict__ a, const T* __restrict__ b, const float* __restrict__ scale,
-                                                          long long planes, int hw) {
-    union V16 { uint4 u; T v[8]; };
-    const int per = hw >> 3;                                   // 16-byte vectors per plane
-    for (long long plane = blockIdx.y; plane < planes; plane += gridDim.y) {
-        const float sc = scale ? scale[plane] : 1.f;
-        const uint4* ap = (const uint4*)a + plane * per;
-        const uint4* bp = (const uint4*)b + plane * per;
-        uint4* yp = (uint4*)y + plane * per;
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per; i += gridDim.x * blockDim.x) {
-            V16 av, bv, out;
-            av.u = ap[i];
-            bv.u = bp[i];
-#pragma unroll
-            for (int e = 0; e < 8; e++) out.v[e] = from_f32<T>(to_f32(av.v[e]) + sc * to_f32(bv.v[e]));
-            yp[i] = out.u;
-        }
-    }
-}
-
-// Magnitude bound of a tensor, for the float16 split (split16_kernel): out[0] = max(out[0], bits of max |scale[plane] * x[plane, :]|).
-// Magnitudes compare as their bit patterns; r06: over the FINITE elements only (an inf / NaN element keeps its place in the split's first part
-// whatever the factor).  The consumers turn the bound into the power of two g with
-// g * bound in [2^14, 2^15) (pow2_factor): float16 parts of g * v cannot overflow (65504) and the second part of every element above
-// 2^-18 of the bound is a normal number (below that it is a subnormal: 22 significand bits shrink to 11 at 2^-29 of the bound).  One bound
-// per TENSOR, not per plane: the contraction sums over the input planes, so a per-plane factor cannot leave the sum (a per-sample one could
-// in forward / data gradient, not in the weight gradient, which sums over samples) -- DESIGN.md section 4.4.
-// One atomic per workgroup, and only from workgroups that would raise the value (2048 unconditional atomics on one word cost 50 us).
-__global__ __launch_bounds__(256) void amax_bits_kernel(unsigned* __restrict__ out, const float* __restrict__ x, long long planes, int hw,
-                                                        const float* __restrict__ scale) {
-    __shared__ unsigned red[4];
-    unsigned m = 0;
-    const long long numel = planes * hw;
-    const bool vec = (((uintptr_t)x & 15) == 0) && (hw & 3) == 0;
-    const long long n4 = vec ? (numel >> 2) : 0;
-    const int per = hw >> 2;                                 // 16-byte groups per plane (vec only)
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    auto fold = [&](const uint4 v, long long g) {
-        // non-finite magnitudes (exponent all ones) do not count: one inf or NaN would otherwise take the power-of-two factor -- and with it
-        // 22-bit parts -- away from every finite element of the tensor; the split keeps such an element whole in its first part
-        const unsigned ax = v.x & 0x7fffffffu, ay = v.y & 0x7fffffffu, az = v.z & 0x7fffffffu, aw = v.w & 0x7fffffffu;
-        unsigned a = max(max(ax < 0x7f800000u ? ax : 0u, ay < 0x7f800000u ? ay : 0u), max(az < 0x7f800000u ? az : 0u, aw < 0x7f800000u ? aw : 0u));
-        if (scale) {
-            a = __float_as_uint(__uint_as_float(a) * __builtin_fabsf(scale[g / per]));              // |s| max|x| = max|s x|
-            if (a >= 0x7f800000u) a = 0u;                                                           // (an overflowing or non-finite factor: as above)
-        }
-        m = max(m, a);
-    };
-    // four independent 16-byte loads in flight per lane
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-        const uint4 v0 = ((const uint4*)x)[i], v1 = ((const uint4*)x)[i + stride], v2 = ((const uint4*)x)[i + 2 * stride], v3 = ((const uint4*)x)[i + 3 * stride];
-        fold(v0, i); fold(v1, i + stride); fold(v2, i + 2 * stride); fold(v3, i + 3 * stride);
-    }
-    for (; i < n4; i += stride) fold(((const uint4*)x)[i], i);
-    for (long long j = 4 * n4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; j < numel; j += stride) {
-        const float v = x[j] * (scale ? scale[j / hw] : 1.f);
-        const unsigned a = __float_as_uint(v) & 0x7fffffffu;
-        m = max(m, a < 0x7f800000u ? a : 0u);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = max(max(red[0], red[1]), max(red[2], red[3]));
-        if (m > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, m);
-    }
-}
-
-// out[plane] = <sum_k parts[k][plane, :], b[plane, :]> / g: the style gradient's dot product <x, dx> of an fp32 conv whose backward kept the
-// 16-bit parts of x (split16_kernel) instead of x.  One workgroup per plane; 4 elements per lane and iteration where the plane allows.
-template <typename TP>
-__global__ __launch_bounds__(256) void plane_dot_parts_kernel(float* __restrict__ out, const TP* __restrict__ parts, long long part_stride, int nparts,
-                                                              const float* __restrict__ b, long long planes, int hw, const unsigned* __restrict__ bound) {
-    __shared__ float red[4];
-    const long long plane = blockIdx.x;
-    if (plane >= planes) return;
-    const TP* ap = parts + plane * hw;
-    const float* bp = b + plane * hw;
-    float acc = 0.f;
-    if ((hw & 3) == 0 && (part_stride & 3) == 0) {          // 8-byte part loads, 16-byte b loads (the generator's planes: hw % 4 == 0)
-        union V8 { uint2 u; TP v[4]; };
-        for (int i = threadIdx.x * 4; i < hw; i += blockDim.x * 4) {
-            const float4 b0 = *(const float4*)(bp + i);
-            const float bv[4] = {b0.x, b0.y, b0.z, b0.w};
-            for (int k = 0; k < nparts; k++) {
-                V8 a; a.u = *(const uint2*)(ap + k * part_stride + i);
-#pragma unroll
-                for (int e = 0; e < 4; e++) acc += (float)a.v[e] * bv[e];
-            }
-        }
-    } else {
-        for (int i = threadIdx.x; i < hw; i += blockDim.x) {
-            float a = 0.f;
-            for (int k = 0; k < nparts; k++) a += (float)ap[k * part_stride + i];
-            acc += a * bp[i];
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float inv = 1.f;
-        if (bound) pow2_factor(bound[0], &inv);
-        out[plane] = (red[0] + red[1] + red[2] + red[3]) * inv;
-    }
-}
-
-// t *= 1 / (g_a g_b): the power-of-two factors of two split operands undone (weight gradient of split parts).
-__global__ __launch_bounds__(256) void unscale_kernel(float* __restrict__ t, long long numel, const unsigned* __restrict__ bound_a, const unsigned* __restrict__ bound_b) {
-    float ia = 1.f, ib = 1.f;
-    if (bound_a) pow2_factor(bound_a[0], &ia);
-    if (bound_b) pow2_factor(bound_b[0], &ib);
-    const float inv = ia * ib;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < numel; i += (long long)gridDim.x * blockDim.x) t[i] *= inv;
-}
-
 // The packed image of a split conv's stacked weight parts (afcm_conv2d_split): channel block t (cin16 = 16 nkc_real channels) holds part
 // (term_wparts >> 4 t) & 15 of g * w (g: pow2_factor of the bound word, 1 without one) -- part 0 = r16(v), part 1 = r16(v - part 0), ... -- in the layout of conv2d_pack_kernel
 // (mode 1: the data gradient's transposed, flipped kernel).
@@ -1480,1442 +1299,6 @@ __global__ __launch_bounds__(256) void conv2d_pack_split_kernel(T* __restrict__ 
             q = (T)r;
         }
         dst[idx] = q;
-    }
-}
-
-// Split-precision operands: v = g * scale[plane] * x (g: pow2_factor of the bound word, 1 without one) as a sum of `parts` 16-bit numbers, v ~ a + b (+ c) with a = r16(v), b = r16(v - a),
-// c = r16(v - a - b) (round to nearest even; the differences are exact in fp32).  bfloat16: two parts carry 16 significand bits, three
-// carry all 24.  float16: two parts carry 22 bits wherever b is a normal number, i.e. for |v| >= 2^-3; below that the error is at most
-// 2^-25 ABSOLUTE, so with g the power of two that brings the tensor's largest magnitude near 2^15 it is 2^-40 of that magnitude.
-// parts[k] is a dense tensor of the input's shape, part_stride elements after parts[k - 1].  A non-finite v keeps its class in part a
-// and zeros in the others (inf - inf would make NaNs of infinities).
-template <typename TP, int PARTS>
-__global__ __launch_bounds__(256) void split16_kernel(TP* __restrict__ parts, const float* __restrict__ x, const float* __restrict__ scale,
-                                                      const unsigned* __restrict__ bound, long long planes, int hw, long long part_stride) {
-    const int per = (hw + 3) >> 2;
-    const long long total = planes * per;
-    const bool vec = (hw & 3) == 0;
-    const float gs = bound ? pow2_factor(bound[0]) : 1.f;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
-        const long long plane = idx / per;
-        const int i0 = (int)(idx - plane * per) << 2;
-        const float sc = (scale ? scale[plane] : 1.f) * gs;
-        const float* xp = x + plane * hw + i0;
-        TP* yp = parts + plane * hw + i0;
-        float v[4];
-        if (vec) {
-            const Vec4<float> in = *(const Vec4<float>*)xp;
-#pragma unroll
-            for (int e = 0; e < 4; e++) v[e] = in.v[e] * sc;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) v[e] = (i0 + e < hw) ? xp[e] * sc : 0.f;
-        }
-        Vec4<TP> out[PARTS];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            float r = v[e];
-#pragma unroll
-            for (int k = 0; k < PARTS; k++) {
-                const TP q = (TP)r;
-                out[k].v[e] = q;
-                const float qf = (float)q;
-                r = (__builtin_fabsf(qf) <= 3.4028234664e38f) ? r - qf : 0.f;      // inf / nan: nothing left for the lower parts
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < PARTS; k++) {
-            if (vec) {
-                *(Vec4<TP>*)(yp + k * part_stride) = out[k];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    if (i0 + e < hw) yp[k * part_stride + e] = out[k].v[e];
-            }
-        }
-    }
-}
-
-// Per-plane reductions: out[plane] = sum a*b (or sum a when b == null).  One workgroup per plane, fp32 accumulate, 16-byte
-// loads from the plane's first 16-byte boundary on (both operands share the plane offset; the host checks the base pointers).
-template <typename T>
-__global__ __launch_bounds__(256) void plane_dot_kernel(float* __restrict__ out, const T* __restrict__ a, const T* __restrict__ b,
-                                                        long long planes, int hw) {
-    constexpr int E = 16 / (int)sizeof(T);
-    union V16 { uint4 u; T v[E]; };
-    __shared__ float part[4];
-    const long long plane = blockIdx.x;
-    if (plane >= planes) return;
-    const long long off = plane * hw;
-    const T* ap = a + off;
-    const T* bp = b ? b + off : nullptr;
-    int head = (int)((E - (off % E)) % E);
-    if (head > hw) head = hw;
-    const int nv = (hw - head) / E;
-    float s0 = 0.f, s1 = 0.f;
-    {   // ragged ends: fewer than 2E elements in total
-        const int tail0 = head + nv * E;
-        int i = -1;
-        if ((int)threadIdx.x < head) i = threadIdx.x;
-        else if ((int)threadIdx.x - head < hw - tail0) i = tail0 + (int)threadIdx.x - head;
-        if (i >= 0) s0 = to_f32(ap[i]) * (bp ? to_f32(bp[i]) : 1.f);
-    }
-    const uint4* av = (const uint4*)(ap + head);
-    const uint4* bv = bp ? (const uint4*)(bp + head) : nullptr;
-    int i = threadIdx.x;
-    if (bv) {
-        // four 16-byte loads per operand in flight (128 B per lane) before the first use
-        for (; i + 768 < nv; i += 1024) {
-            V16 a0, a1, a2, a3, b0, b1, b2, b3;
-            a0.u = av[i]; a1.u = av[i + 256]; a2.u = av[i + 512]; a3.u = av[i + 768];
-            b0.u = bv[i]; b1.u = bv[i + 256]; b2.u = bv[i + 512]; b3.u = bv[i + 768];
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                s0 = fmaf(to_f32(a0.v[e]), to_f32(b0.v[e]), s0); s1 = fmaf(to_f32(a1.v[e]), to_f32(b1.v[e]), s1);
-                s0 = fmaf(to_f32(a2.v[e]), to_f32(b2.v[e]), s0); s1 = fmaf(to_f32(a3.v[e]), to_f32(b3.v[e]), s1);
-            }
-        }
-    }
-    for (; i + 256 < nv; i += 512) {
-        V16 a0, a1, b0, b1;
-        a0.u = av[i]; a1.u = av[i + 256];
-        if (bv) {
-            b0.u = bv[i]; b1.u = bv[i + 256];
-#pragma unroll
-            for (int e = 0; e < E; e++) { s0 = fmaf(to_f32(a0.v[e]), to_f32(b0.v[e]), s0); s1 = fmaf(to_f32(a1.v[e]), to_f32(b1.v[e]), s1); }
-        } else {
-#pragma unroll
-            for (int e = 0; e < E; e++) { s0 += to_f32(a0.v[e]); s1 += to_f32(a1.v[e]); }
-        }
-    }
-    if (i < nv) {
-        V16 a0, b0;
-        a0.u = av[i];
-        if (bv) {
-            b0.u = bv[i];
-#pragma unroll
-            for (int e = 0; e < E; e++) s0 = fmaf(to_f32(a0.v[e]), to_f32(b0.v[e]), s0);
-        } else {
-#pragma unroll
-            for (int e = 0; e < E; e++) s0 += to_f32(a0.v[e]);
-        }
-    }
-    float s = s0 + s1;
-#pragma unroll
-    for (int off2 = 32; off2 > 0; off2 >>= 1) s += __shfl_down(s, off2, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[plane] = part[0] + part[1] + part[2] + part[3];
-}
-
-// Small planes (<= 16 KB): one WAVE per plane, four planes per workgroup -- a 36^2 plane is 180 16-byte pieces, so a
-// 256-thread workgroup per plane leaves most lanes without a load and the launch is bound by workgroup turnover.
-template <typename T>
-__global__ __launch_bounds__(256) void plane_dot_wave_kernel(float* __restrict__ out, const T* __restrict__ a, const T* __restrict__ b,
-                                                             long long planes, int hw) {
-    constexpr int E = 16 / (int)sizeof(T);
-    union V16 { uint4 u; T v[E]; };
-    const int lane = threadIdx.x & 63;
-    const long long plane = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (plane >= planes) return;
-    const long long off = plane * hw;
-    const T* ap = a + off;
-    const T* bp = b ? b + off : nullptr;
-    int head = (int)((E - (off % E)) % E);
-    if (head > hw) head = hw;
-    const int nv = (hw - head) / E;
-    float s0 = 0.f, s1 = 0.f;
-    {   // ragged ends: fewer than 2E <= 16 elements in total
-        const int tail0 = head + nv * E;
-        int i = -1;
-        if (lane < head) i = lane;
-        else if (lane - head < hw - tail0) i = tail0 + lane - head;
-        if (i >= 0) s0 = to_f32(ap[i]) * (bp ? to_f32(bp[i]) : 1.f);
-    }
-    const uint4* av = (const uint4*)(ap + head);
-    const uint4* bv = bp ? (const uint4*)(bp + head) : nullptr;
-    int i = lane;
-    for (; i + 64 < nv; i += 128) {
-        V16 a0, a1, b0, b1;
-        a0.u = av[i]; a1.u = av[i + 64];
-        if (bv) {
-            b0.u = bv[i]; b1.u = bv[i + 64];
-#pragma unroll
-            for (int e = 0; e < E; e++) { s0 = fmaf(to_f32(a0.v[e]), to_f32(b0.v[e]), s0); s1 = fmaf(to_f32(a1.v[e]), to_f32(b1.v[e]), s1); }
-        } else {
-#pragma unroll
-            for (int e = 0; e < E; e++) { s0 += to_f32(a0.v[e]); s1 += to_f32(a1.v[e]); }
-        }
-    }
-    if (i < nv) {
-        V16 a0, b0;
-        a0.u = av[i];
-        if (bv) {
-            b0.u = bv[i];
-#pragma unroll
-            for (int e = 0; e < E; e++) s0 = fmaf(to_f32(a0.v[e]), to_f32(b0.v[e]), s0);
-        } else {
-#pragma unroll
-            for (int e = 0; e < E; e++) s0 += to_f32(a0.v[e]);
-        }
-    }
-    float s = s0 + s1;
-#pragma unroll
-    for (int off2 = 32; off2 > 0; off2 >>= 1) s += __shfl_down(s, off2, 64);
-    if (lane == 0) out[plane] = s;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Weight gradient: dW[o][i][r][s] = sum_n sum_{p,q} dy[n,o,p,q] * x[n,i,p+r-pad,q+s-pad]   (inputs already scaled per plane)
-// GEMM with K = pixels: both operands are K-contiguous in NCHW, so the LDS images are plain row copies and the
-// 3 column shifts of a tap row come from ONE 5-dword read per row (shift 0: dwords 0-3, shift 2: dwords 1-4,
-// shift 1: v_alignbyte of neighbours).  One workgroup = 64 o x 64 i x all taps; 4 waves as 2(o) x 2(i), each
-// wave holds KK accumulator tiles of 32x32.  K is split over workgroups by output row; partial sums go to
-// a workspace [split][O][I][KK] and are summed by wgrad_reduce_kernel.
-constexpr int kWgKQ = 64;        // pixels of one output row per K macro-step
-
-// Row-pitched operands (planes [h][ld], the first w columns of a row meaningful -- the 16-bit activation layout of DESIGN.md
-// section 3): 16-byte vectors within a row; the last vector of a row is shifted back to END at column w (no access past the row,
-// the re-read elements are selected out), so nothing depends on what the padding holds.  PER_WAVE: one wave per plane, four
-// planes per workgroup (small planes, as plane_dot_wave_kernel).  Needs w >= 16 / sizeof(T).
-// Gate of the "dot product by homogeneity" (afcm_plane_dot_gated_ld): a plane none of whose strips could reach the clamp takes
-//     out = osc (gz - nsc gsk)                     (nsc, gsk may be NULL: 1, 0)
-// and its wave / workgroup leaves without touching a or b; a flagged plane gets the real dot product, and so does a plane whose two
-// sums cancel to less than 1/8 of their size (|skip| >> |F(y)| amplifies the rounding of z by that ratio).
-struct PlaneGate {
-    const int* flags;     // [planes][slots], NULL: no gate
-    int slots;
-    const float *osc, *gz, *nsc, *gsk;
-};
-template <typename T, bool PER_WAVE>
-__global__ __launch_bounds__(256) void plane_dot_rows_kernel(float* __restrict__ out, const T* __restrict__ a, const T* __restrict__ b,
-                                                             long long planes, int h, int w, int lda, int ldb, PlaneGate gate) {
-    constexpr int E = 16 / (int)sizeof(T);
-    union V16 { uint4 u; T v[E]; };
-    __shared__ float part[4];
-    const int nthr = PER_WAVE ? 64 : 256;
-    const int t = PER_WAVE ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
-    const long long plane = PER_WAVE ? (long long)blockIdx.x * 4 + (threadIdx.x >> 6) : (long long)blockIdx.x;
-    if (plane >= planes) return;                               // PER_WAVE: a whole wave leaves (no barrier below in that mode)
-    if (gate.flags != nullptr) {
-        int any = 0;                                           // (wave- / workgroup-uniform: every thread reads the same words)
-        for (int i = 0; i < gate.slots; i++) any |= gate.flags[plane * gate.slots + i];
-        if (!any) {
-            // ... unless the two sums cancel: each carries the 16-bit rounding of z / skip (2^-9 relative in bf16), so their difference is
-            // trusted down to 1/8 of their size (a skip branch that dwarfs this layer's own output); beyond that the plane takes the real
-            // dot product like a flagged one
-            const float zz = gate.gz[plane], kk = gate.gsk ? (gate.nsc ? gate.nsc[plane] : 1.f) * gate.gsk[plane] : 0.f;
-            const float diff = zz - kk;
-            if (!(gate.gsk != nullptr && fabsf(diff) * 8.f < fabsf(zz) + fabsf(kk))) {
-                if (t == 0) out[plane] = gate.osc[plane] * diff;
-                return;
-            }
-        }
-    }
-    const int nvec = (w + E - 1) / E, total = h * nvec;
-    const unsigned magic = (unsigned)((0x100000000ull + (unsigned)nvec - 1) / (unsigned)nvec);
-    const T* ap = a + plane * h * lda;
-    const T* bp = b ? b + plane * h * ldb : nullptr;
-    float s0 = 0.f, s1 = 0.f;
-    for (int i0 = t; i0 < total; i0 += 4 * nthr) {
-        V16 av[4], bv[4];
-        int skip[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int i = i0 + u * nthr;
-            const int ic = i < total ? i : total - 1;
-            const int row = (int)__umulhi((unsigned)ic, magic), col = (ic - row * nvec) * E;
-            const int colc = col + E <= w ? col : w - E;
-            skip[u] = i < total ? col - colc : E;              // leading elements that an earlier vector already counted (E: none live)
-            av[u].u = *(const uint4*)(ap + (size_t)row * lda + colc);
-            if (bp) bv[u].u = *(const uint4*)(bp + (size_t)row * ldb + colc);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                const float x = e >= skip[u] ? to_f32(av[u].v[e]) : 0.f;
-                const float y = bp ? to_f32(bv[u].v[e]) : 1.f;
-                if (u & 1) s1 = fmaf(x, e >= skip[u] ? y : 0.f, s1); else s0 = fmaf(x, e >= skip[u] ? y : 0.f, s0);
-            }
-        }
-    }
-    float s = s0 + s1;
-#pragma unroll
-    for (int off2 = 32; off2 > 0; off2 >>= 1) s += __shfl_down(s, off2, 64);
-    if (PER_WAVE) {
-        if ((threadIdx.x & 63) == 0) out[plane] = s;
-    } else {
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) out[plane] = part[0] + part[1] + part[2] + part[3];
-    }
-}
-
-
-struct WgradParams {
-    const void* dy;   // [N, O, P, Q]
-    const void* x;    // [N, I, H, W]
-    float* part;      // [splits][O][I][KK]
-    int N, O, I, H, W, P, Q, pad;
-    int lddy, ldx;                // row pitch (elements) of dy / x; = Q / W for dense tensors.  conv2d_wgrad16g_kernel only.
-    int splits, steps_per_split;  // K macro-steps = N * rowgroups * qchunks
-    // conv2d_wgrad16g_kernel: two classes of 64 x 64 tiles.  The tiles (obk < fo, ib < fi) are FULL: `splits` workgroups of
-    // `steps_per_split` steps each; the others have at most 32 live rows or columns -- two of their four wave quadrants multiply nothing and
-    // are skipped -- and get `splits_p` workgroups of `steps_per_split_p` steps (fewer, longer shares: a step costs them ~0.6 of a full
-    // tile's).  No partial class: fo / fi = the tile counts, splits_p = splits.
-    int fo, fi, splits_p, steps_per_split_p;
-    int qchunks;                  // ceil(Q / kWgKQ)
-    int rowgroups;                // ceil(P / R)
-    // conv2d_wgrad16g_kernel, r06: > 0 = splits per IMAGE (splits = N * splits_img): a split never crosses an image, so the slabs of image n are
-    // its own weight gradient dW_n -- what the per-plane dot products <x[n, i], dx[n, i]> are read from (wgrad_reduce_dots_kernel)
-    int splits_img;
-};
-
-// R = output rows per K macro-step (2 for 16-bit: halves the barriers and re-uses the overlapping input rows).
-template <typename T, int KS, int R, int XOFF>
-__global__ __launch_bounds__(512, (sizeof(T) == 4 ? 1 : 2)) void conv2d_wgrad_kernel(WgradParams p) {
-    constexpr bool F32 = sizeof(T) == 4;
-    constexpr int KK = KS * KS;
-    constexpr int EPD = F32 ? 1 : 2;               // elements per staged dword
-    constexpr int PDY = kWgKQ + 8;                 // 72 elements: 16-bit rows of 144 B (odd x 16 B)
-    constexpr int PX = kWgKQ + 24;                 // 88 elements: 176 B rows (odd x 16 B)
-    constexpr int XW = kWgKQ + 8;                  // staged x columns per row (shifts 0..KS-1, +1 alignment, rounded)
-    constexpr int XR = R + KS - 1;                 // staged x rows per channel
-    constexpr int DPR_DY = kWgKQ / EPD, DPR_X = XW / EPD;
-    constexpr int LDS_ONE = 64 * R * PDY + 64 * XR * PX;
-    constexpr int NBUF = (LDS_ONE * (int)sizeof(T) * 2 <= 150 * 1024) ? 2 : 1;     // double-buffer when it fits the 160 KB LDS
-    __shared__ __attribute__((aligned(16))) T lds[NBUF * LDS_ONE];
-    T* lds_dy = lds;
-    T* lds_x = lds + 64 * R * PDY;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wo = wave & 1, wi = (wave >> 1) & 1, th = wave >> 2;     // th: which half of the chunk's pixels this wave accumulates
-    const int r32 = lane & 31, h = lane >> 5;
-    constexpr int NACC = KK;
-
-    int bid = blockIdx.x;
-    const int split = bid % p.splits; bid /= p.splits;
-    const int ib = bid % cdiv(p.I, 64);
-    const int obk = bid / cdiv(p.I, 64);
-    const int o0 = obk * 64, i0 = ib * 64;
-
-    f32x16 acc[NACC];
-#pragma unroll
-    for (int t = 0; t < NACC; t++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-
-    // ---- staging maps.  Rows of 32 dwords are spread as (row = tid/32 + 8*i, dword = tid%32), so the row-dependent
-    // parts of an address advance by a constant per i; the 4-dword tail of every x row is a second small map.
-    constexpr int NC = DPR_DY / 32;                 // 32-dword column groups per row (1 for 16-bit, 2 for fp32)
-    constexpr int TAILD = DPR_X - 32 * NC;          // dwords of the x-row tail (4 / 8)
-    static_assert(DPR_DY % 32 == 0 && TAILD > 0 && TAILD <= 8, "staging maps assume 64-pixel chunks");
-    constexpr int NDY = (64 * R) / 16;              // dy rows (o * R + rr) per thread
-    constexpr int NXM = (64 * XR) / 16;             // x rows (ic * XR + r), main 32*NC dwords
-    constexpr int NXT = cdiv(64 * XR * TAILD, 512); // x tail
-    const int rb = tid >> 5, dlane = tid & 31;
-    unsigned rdy[NDY][NC], rxm[NXM][NC], rxt[NXT];
-    // Loads are raw buffer loads: an invalid element (padding row / column, channel past the end) gets the byte offset
-    // kOob >= num_records and reads as zero -- no branches, one v_cndmask per load.  The step-dependent part of every address
-    // is wave-uniform and lives in the buffer base; the per-thread byte offsets below never change.
-    constexpr unsigned kOob = 0x80000000u;
-    constexpr bool ROWSAME = (16 % R == 0) && (16 % XR == 0);      // row-in-step index of a thread is the same for all its loads
-    unsigned dyoff[NDY], xoff_[NXM], xtoff[NXT];
-    int dyr[NDY], xr_[NXM], xtr[NXT], xtc[NXT];
-#pragma unroll
-    for (int i = 0; i < NDY; i++) {
-        const int row = rb + 16 * i;
-        const int o = o0 + row / R;
-        dyr[i] = row % R;
-        dyoff[i] = o < p.O ? (unsigned)(((o * p.P + dyr[i]) * p.Q + dlane * EPD) * (int)sizeof(T)) : kOob;
-    }
-#pragma unroll
-    for (int i = 0; i < NXM; i++) {
-        const int row = rb + 16 * i;
-        const int ic = i0 + row / XR;
-        xr_[i] = row % XR;
-        xoff_[i] = ic < p.I ? (unsigned)(((ic * p.H + xr_[i]) * p.W + dlane * EPD) * (int)sizeof(T)) : kOob;
-    }
-#pragma unroll
-    for (int i = 0; i < NXT; i++) {
-        const int j = tid + i * 512;
-        const int row = j / TAILD;
-        const int ic = i0 + row / XR;
-        xtr[i] = row % XR;
-        xtc[i] = (32 * NC + j % TAILD) * EPD;
-        xtoff[i] = (row < 64 * XR && ic < p.I) ? (unsigned)(((ic * p.H + xtr[i]) * p.W + xtc[i]) * (int)sizeof(T)) : kOob;
-    }
-
-    const int steps_per_img = p.rowgroups * p.qchunks;
-    const int s0 = split * p.steps_per_split;
-    const int s1 = min(s0 + p.steps_per_split, p.N * steps_per_img);
-    // (image, row group, column chunk) of the next step to load; steps are loaded in order, so this advances by carries
-    int ld_n = s0 / steps_per_img;
-    int ld_rg = (s0 - ld_n * steps_per_img) / p.qchunks;
-    int ld_qc = s0 - ld_n * steps_per_img - ld_rg * p.qchunks;
-
-    auto issue_loads = [&]() __attribute__((always_inline)) {
-        const int prow0 = ld_rg * R, q0 = ld_qc * kWgKQ;
-        const int xorg = (q0 - p.pad) & ~1;
-        // uniform bases: everything that does not depend on the lane (may point before the tensor for padding rows: those
-        // elements are never fetched)
-        const T* dyb = (const T*)p.dy + (size_t)ld_n * p.O * p.P * p.Q + (size_t)prow0 * p.Q + q0;
-        const T* xb = (const T*)p.x + (long long)ld_n * p.I * p.H * p.W + (long long)(prow0 - p.pad) * p.W + xorg;
-        const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc((void*)dyb, 0, kOob, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, kOob, 0x00020000);
-        unsigned dyrows = 0, xrows = 0;               // validity of the R / XR rows of this step
-#pragma unroll
-        for (int r = 0; r < R; r++) dyrows |= (unsigned)(prow0 + r < p.P) << r;
-#pragma unroll
-        for (int r = 0; r < XR; r++) xrows |= (unsigned)((unsigned)(prow0 + r - p.pad) < (unsigned)p.H) << r;
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const int dcol = (dlane + 32 * c) * EPD;
-            const bool dcok = q0 + dcol < p.Q;
-            const bool xcok = (unsigned)(xorg + dcol) < (unsigned)p.W;
-            // validity as an offset mask: 0 or kOob, OR-ed into the byte offset (kept arithmetic so that no branch is formed)
-            const unsigned dym0 = (unsigned)!(dcok && ((dyrows >> dyr[0]) & 1)) << 31, xm0 = (unsigned)!(xcok && ((xrows >> xr_[0]) & 1)) << 31;
-#pragma unroll
-            for (int i = 0; i < NDY; i++) {
-                const unsigned m = ROWSAME ? dym0 : (unsigned)!(dcok && ((dyrows >> dyr[i]) & 1)) << 31;
-                rdy[i][c] = __builtin_amdgcn_raw_buffer_load_b32(rs_dy, (dyoff[i] + 32 * c * 4) | m, 0, 0);
-            }
-#pragma unroll
-            for (int i = 0; i < NXM; i++) {
-                const unsigned m = ROWSAME ? xm0 : (unsigned)!(xcok && ((xrows >> xr_[i]) & 1)) << 31;
-                rxm[i][c] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, (xoff_[i] + 32 * c * 4) | m, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NXT; i++) {
-            const unsigned m = (unsigned)!(((xrows >> xtr[i]) & 1) && (unsigned)(xorg + xtc[i]) < (unsigned)p.W) << 31;
-            rxt[i] = __builtin_amdgcn_raw_buffer_load_b32(rs_x, xtoff[i] | m, 0, 0);
-        }
-        if (++ld_qc == p.qchunks) {
-            ld_qc = 0;
-            if (++ld_rg == p.rowgroups) { ld_rg = 0; ld_n++; }
-        }
-    };
-    auto write_lds = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < NDY; i++)
-#pragma unroll
-            for (int c = 0; c < NC; c++) *(unsigned*)(lds_dy + (dyr[i] * 64 + (rb + 16 * i) / R) * PDY + (dlane + 32 * c) * EPD) = rdy[i][c];
-#pragma unroll
-        for (int i = 0; i < NXM; i++)
-#pragma unroll
-            for (int c = 0; c < NC; c++) *(unsigned*)(lds_x + (xr_[i] * 64 + (rb + 16 * i) / XR) * PX + (dlane + 32 * c) * EPD) = rxm[i][c];
-#pragma unroll
-        for (int i = 0; i < NXT; i++) {
-            const int j = tid + i * 512;
-            if (j / TAILD < 64 * XR) *(unsigned*)(lds_x + (xtr[i] * 64 + (j / TAILD) / XR) * PX + xtc[i]) = rxt[i];
-        }
-    };
-
-    // Pipeline.  Double-buffered (16-bit): while a wave runs the MFMAs of step s from buffer s&1, the others may already be
-    // writing step s+1 into the other buffer and have step s+2's global loads in flight: one barrier per step.
-    // Single-buffered (fp32): write / barrier / compute / barrier.
-    if (s0 < s1) {
-        issue_loads();
-        write_lds();
-        if (NBUF == 2 && s0 + 1 < s1) issue_loads();
-    }
-    __syncthreads();
-    for (int step = s0; step < s1; step++) {
-        constexpr int xoff = XOFF;                  // (q0 - pad) & 1 with q0 a multiple of 64: launch-wide constant
-        if (NBUF == 2) {
-            if (step + 1 < s1) {
-                lds_dy = lds + ((step + 1 - s0) & 1) * LDS_ONE;
-                lds_x = lds_dy + 64 * R * PDY;
-                write_lds();                        // step+1 (its loads were issued one step ago)
-                if (step + 2 < s1) issue_loads();
-            }
-            lds_dy = lds + ((step - s0) & 1) * LDS_ONE;
-            lds_x = lds_dy + 64 * R * PDY;
-        } else {
-            if (step > s0) {
-                __syncthreads();
-                write_lds();
-                __syncthreads();
-            }
-            if (step + 1 < s1) issue_loads();
-        }
-        // Both wave halves accumulate every tap; they split the 64 pixels of the chunk (th 0: first 32, th 1: last 32), so a
-        // staged x row is read once per 16 pixels and feeds all KS shifts x R rows x KS tap rows.
-        if constexpr (F32) {
-#pragma unroll
-            for (int rr = 0; rr < R; rr++)
-#pragma unroll 4
-                for (int kq = 0; kq < kWgKQ / 4; kq++) {
-                    const int k2 = th * (kWgKQ / 4) + kq;
-                    const float a = lds_dy[(rr * 64 + wo * 32 + r32) * PDY + 2 * k2 + h];
-#pragma unroll
-                    for (int t = 0; t < KK; t++) {
-                        const int r = t / KS, sft = t - r * KS;
-                        const float b = lds_x[((rr + r) * 64 + wi * 32 + r32) * PX + 2 * k2 + h + sft + xoff];
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[t], 0, 0, 0);
-                    }
-                }
-        } else {
-            typedef typename std::conditional<std::is_same<T, bf16_t>::value, bf16x8, f16x8>::type frag_t;
-            const T* dy_w = lds_dy + (wo * 32 + r32) * PDY + th * (kWgKQ / 2) + 8 * h;
-            const T* x_w = lds_x + (wi * 32 + r32) * PX + th * (kWgKQ / 2) + 8 * h;
-#pragma unroll
-            for (int kq = 0; kq < kWgKQ / 32; kq++) {
-                frag_t a[R];
-#pragma unroll
-                for (int rr = 0; rr < R; rr++) a[rr] = *(const frag_t*)(dy_w + rr * 64 * PDY + kq * 16);
-                // the staged rows of this lane's channel: each read once, shifted variants built in registers
-#pragma unroll
-                for (int xr = 0; xr < XR; xr++) {
-                    const unsigned* src = (const unsigned*)(x_w + xr * 64 * PX + kq * 16);
-                    const uint4 lo = *(const uint4*)src;
-                    const uint4 hi = *(const uint4*)(src + 4);        // 16-byte read (conflict-free); only .x/.y are used
-                    const unsigned d[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
-#pragma unroll
-                    for (int sft = 0; sft < KS; sft++) {
-                        union { unsigned u[4]; frag_t f; } b;
-                        const int sh = sft + xoff;                            // element shift in [0, 3], compile-time
-#pragma unroll
-                        for (int w = 0; w < 4; w++) {
-                            const unsigned e0 = d[w], e1 = d[w + 1], e2 = d[w + 2];
-                            const unsigned odd_lo = __builtin_amdgcn_alignbyte(e1, e0, 2);
-                            const unsigned odd_hi = __builtin_amdgcn_alignbyte(e2, e1, 2);
-                            b.u[w] = (sh == 0) ? e0 : (sh == 1) ? odd_lo : (sh == 2) ? e1 : odd_hi;
-                        }
-#pragma unroll
-                        for (int rr = 0; rr < R; rr++) {
-                            const int r = xr - rr;
-                            const int t = r * KS + sft;
-                            if (r >= 0 && r < KS) {
-                                if constexpr (std::is_same<T, bf16_t>::value)
-                                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rr], b.f, acc[t], 0, 0, 0);
-                                else
-                                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rr], b.f, acc[t], 0, 0, 0);
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        if (NBUF == 2) __syncthreads();            // everyone done with buffer step&1 and step+1 fully written
-    }
-    // ---- add the two pixel halves through LDS (the staging buffers are free now): th 1 parks its accumulators, th 0 adds
-    // them and writes the partial tile D[row = o][col = i].
-    if (NBUF == 1) __syncthreads();
-    {
-        float* red = (float*)lds;
-        constexpr int TPR_CAP = (int)((size_t)NBUF * LDS_ONE * sizeof(T) / (4 * 16 * 64 * sizeof(float)));     // taps per round
-        constexpr int TPR = TPR_CAP < KK ? TPR_CAP : KK;
-        static_assert(TPR >= 1, "LDS too small for the half-sum");
-        const int wv4 = wave & 3;
-#pragma unroll
-        for (int t0 = 0; t0 < KK; t0 += TPR) {
-            if (t0 > 0) __syncthreads();
-            if (th == 1) {
-#pragma unroll
-                for (int t = t0; t < t0 + TPR && t < KK; t++)
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg++) red[((wv4 * TPR + (t - t0)) * 16 + reg) * 64 + lane] = acc[t][reg];
-            }
-            __syncthreads();
-            if (th == 0) {
-#pragma unroll
-                for (int t = t0; t < t0 + TPR && t < KK; t++)
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg++) acc[t][reg] += red[((wv4 * TPR + (t - t0)) * 16 + reg) * 64 + lane];
-            }
-        }
-    }
-    if (th == 0) {
-        float* out = p.part + (size_t)split * p.O * p.I * KK;
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const int o = o0 + wo * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            const int i = i0 + wi * 32 + r32;
-            if (o < p.O && i < p.I) {
-                float* dst = out + ((size_t)o * p.I + i) * KK;
-#pragma unroll
-                for (int t = 0; t < KK; t++) dst[t] = acc[t][reg];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 16-bit weight gradient, LDS-DMA staged.  Same tiling as conv2d_wgrad_kernel (64 o x 64 i x all taps per workgroup, R = 2
-// output rows x 64 pixels per K step, 8 waves = 2(o) x 2(i) x 2(pixel halves)), but the operands go HBM -> LDS directly
-// (buffer_load_dword ... lds): no staging VGPRs, no ds_write pass, no per-load VALU.  One wave instruction fills 64
-// consecutive LDS dwords = two 128-byte rows (64 pixels of two channels), so rows cannot be padded; bank conflicts are
-// avoided by an XOR swizzle of the 16-byte granules, applied on the SOURCE address of the load and again on the read:
-//     granule g of row r sits at physical granule g ^ ((r >> 1) & 7)            (conflict-free for ds_read_b128's lane groups)
-// LDS image of one step (NBUF of them in a ring):
-//     dy  [rr 0..1][o 0..63][128 B]                                             16 KB
-//     x   [xr 0..XR-1] { main [ch 0..63][128 B] (cols 0..63), tail [ch 0..63][16 B] (cols 64..71) }   XR x 9 KB
-// Every piece is predicated by the buffer descriptor: rows outside the image get num_records = 0, channels past the end
-// fall behind num_records, columns past the end get the out-of-range offset bit -- all of them read as zero.
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-template <int LO, int HI, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (LO < HI) {
-        f(std::integral_constant<int, LO>{});
-        static_for<LO + 1, HI>(f);
-    }
-}
-
-__device__ __forceinline__ void lds_dma_dword(i32x4 rsrc, unsigned voff, unsigned lds_addr) {
-    // M0 carries the wave-uniform LDS destination; lane l lands at lds_addr + 4*l
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc));
-}
-
-// 16 bytes per lane: lane l lands at lds_addr + 16*l
-__device__ __forceinline__ void lds_dma_b128(i32x4 rsrc, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc));
-}
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* base, int num_records) {
-    // the descriptor is wave-uniform by construction; readfirstlane pins it to SGPRs for the "s" asm operand
-    const unsigned long long a = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32) & 0xffff);       // stride 0
-    r.z = __builtin_amdgcn_readfirstlane(num_records);
-    r.w = 0x00020000;
-    return r;
-}
-
-template <typename T, int KS, int XOFF, int NBUF>
-__global__ __launch_bounds__(512, 1) void conv2d_wgrad16_kernel(WgradParams p) {
-    static_assert(sizeof(T) == 2, "16-bit types only");
-    constexpr int R = 2, KK = KS * KS, XR = R + KS - 1;
-    constexpr int ROWB = 128;                       // bytes of one staged row (64 pixels)
-    constexpr int DY_BYTES = R * 64 * ROWB;
-    constexpr int XBLK = 64 * ROWB + 64 * 16;       // one staged x row of all 64 channels: main + tail
-    constexpr int BUF = DY_BYTES + XR * XBLK;
-    constexpr bool TAIL = KS > 1;
-    constexpr int NTAILP = TAIL ? (4 * XR) / 8 : 0; // tail pieces per wave
-    static_assert(!TAIL || (4 * XR) % 8 == 0, "tail pieces must divide over the 8 waves");
-    constexpr int NPIECE = 8 + 4 * XR + NTAILP;     // LDS-DMA instructions per wave and step
-    __shared__ __attribute__((aligned(256))) char lds[NBUF * BUF];
-    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) void*)lds;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wo = wave & 1, wi = (wave >> 1) & 1, th = wave >> 2;     // th: which half of the chunk's pixels this wave accumulates
-    const int r32 = lane & 31, h = lane >> 5;
-
-    // XCD-aware block order: the 8 XCDs take workgroups round-robin, so give XCD x a contiguous range of logical ids;
-    // logical id = split-major, i.e. one XCD's L2 sees all (o, i) tiles of the same pixels.
-    const int tiles_i = cdiv(p.I, 64), tiles = tiles_i * cdiv(p.O, 64);
-    int bid = blockIdx.x;
-    const int total = tiles * p.splits;
-    bid = xcd_order(bid, total);
-    const int split = bid / tiles;
-    const int tile = bid - split * tiles;
-    const int ib = tile % tiles_i, obk = tile / tiles_i;
-    const int o0 = obk * 64, i0 = ib * 64;
-
-    f32x16 acc[KK];
-#pragma unroll
-    for (int t = 0; t < KK; t++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-
-    // ---- load maps.  Wave w owns the row pairs {w, w+8, w+16, w+24} of every 64-row block, so its swizzle key
-    // ((row >> 1) & 7) == w is a constant and one per-lane offset serves all of its pieces.
-    const int half = lane >> 5, slot = lane & 31;
-    const int cdw = ((((slot >> 2) ^ wave) & 7) << 2) | (slot & 3);          // logical dword column of this lane's LDS slot
-    const unsigned lp_dy = (unsigned)((2 * wave + half) * p.P * p.Q * 2 + cdw * 4);
-    const unsigned lp_x = (unsigned)((2 * wave + half) * p.H * p.W * 2 + cdw * 4);
-    const int trow = lane >> 2, tdw = lane & 3;                               // tail piece: 16 channels x 4 dwords
-    const unsigned lp_t = (unsigned)(trow * p.H * p.W * 2 + (32 + tdw) * 4);
-
-    const int steps_per_img = p.rowgroups * p.qchunks;
-    const int s0 = split * p.steps_per_split;
-    const int s1 = min(s0 + p.steps_per_split, p.N * steps_per_img);
-    int ld_n = s0 / steps_per_img;
-    int ld_rg = (s0 - ld_n * steps_per_img) / p.qchunks;
-    int ld_qc = s0 - ld_n * steps_per_img - ld_rg * p.qchunks;
-    int ld_buf = 0;
-
-    // Loads of one step: begin_loads() latches the step's uniform state, issue_piece<I>() issues LDS-DMA instruction I of the
-    // wave's NPIECE.  The pieces are spread between the MFMAs of the previous step's compute: a dword load occupies the
-    // address unit for 16 cycles, so a burst of 26 x 8 waves would stall every wave at the head of the step.
-    int c_prow0 = 0, c_q0 = 0, c_xorg = 0, c_live = 0;
-    unsigned c_bufa = 0, v_dy = 0, v_x = 0, v_t = 0;
-    const T* c_dyn = nullptr;
-    const T* c_xn = nullptr;
-    const int pq = p.P * p.Q, hw = p.H * p.W;
-    auto begin_loads = [&](bool live) __attribute__((always_inline)) {
-        c_live = live ? -1 : 0;                                   // a dead step still issues its pieces (with 0 records)
-        c_prow0 = ld_rg * R; c_q0 = ld_qc * kWgKQ;
-        c_xorg = (c_q0 - p.pad) & ~1;
-        c_bufa = lds0 + ld_buf * BUF;
-        // per-lane column validity -> offset masks
-        v_dy = lp_dy | ((unsigned)!(c_q0 + 2 * cdw < p.Q) << 31);
-        v_x = lp_x | ((unsigned)!((unsigned)(c_xorg + 2 * cdw) < (unsigned)p.W) << 31);
-        v_t = lp_t | ((unsigned)!((unsigned)(c_xorg + 64 + 2 * tdw) < (unsigned)p.W) << 31);
-        c_dyn = (const T*)p.dy + (size_t)ld_n * p.O * pq;
-        c_xn = (const T*)p.x + (size_t)ld_n * p.I * hw;
-        if (live) {
-            if (++ld_qc == p.qchunks) {
-                ld_qc = 0;
-                if (++ld_rg == p.rowgroups) { ld_rg = 0; ld_n++; }
-            }
-        }
-        if (++ld_buf == NBUF) ld_buf = 0;
-    };
-    auto issue_piece = [&](auto idx) __attribute__((always_inline)) {
-        constexpr int I = decltype(idx)::value;
-        if constexpr (I < 8) {
-            constexpr int rr = I >> 2, mm = I & 3;
-            const int ch0 = o0 + 16 * mm, row = c_prow0 + rr;
-            const int inimg = row * p.Q + c_q0;                                // element offset of the piece origin inside a channel
-            int nr = ((p.O - ch0) * pq - inimg) * 2;
-            nr = (row < p.P && nr > 0) ? (nr & c_live) : 0;
-            lds_dma_dword(make_rsrc(c_dyn + (long long)ch0 * pq + inimg, nr), v_dy, c_bufa + rr * (64 * ROWB) + (wave + 8 * mm) * 256);
-        } else if constexpr (I < 8 + 4 * XR) {
-            constexpr int m = I - 8, xr = m >> 2, mm = m & 3;
-            const int ch0 = i0 + 16 * mm, row = c_prow0 - p.pad + xr;
-            const int inimg = row * p.W + c_xorg;
-            int nr = ((p.I - ch0) * hw - inimg) * 2;
-            nr = ((unsigned)row < (unsigned)p.H && nr > 0) ? (nr & c_live) : 0;
-            lds_dma_dword(make_rsrc(c_xn + (long long)ch0 * hw + inimg, nr), v_x, c_bufa + DY_BYTES + xr * XBLK + (wave + 8 * mm) * 256);
-        } else {
-            constexpr int u = I - 8 - 4 * XR;
-            const int q = wave + 8 * u;
-            const int xr = q >> 2, t = q & 3;
-            const int ch0 = i0 + 16 * t, row = c_prow0 - p.pad + xr;
-            const int inimg = row * p.W + c_xorg;
-            int nr = ((p.I - ch0) * hw - inimg) * 2;
-            nr = ((unsigned)row < (unsigned)p.H && nr > 0) ? (nr & c_live) : 0;
-            lds_dma_dword(make_rsrc(c_xn + (long long)ch0 * hw + inimg, nr), v_t, c_bufa + DY_BYTES + xr * XBLK + 64 * ROWB + t * 256);
-        }
-    };
-    // pieces [lo, hi) as one unrolled run
-    auto issue_range = [&](auto lo, auto hi) __attribute__((always_inline)) {
-        constexpr int LO = decltype(lo)::value, HI = decltype(hi)::value;
-        static_for<LO, HI>([&](auto i) __attribute__((always_inline)) { issue_piece(i); });
-    };
-
-    // ---- fragment read offsets inside a buffer (swizzled); the two 16-pixel groups of this wave's half need their own
-    const int rowA = wo * 32 + r32, rowB = wi * 32 + r32;
-    const int fA = (rowA >> 1) & 7, fB = (rowB >> 1) & 7;
-    unsigned a_off[2], xlo_off[2], xhi_off[2];
-#pragma unroll
-    for (int kq = 0; kq < 2; kq++) {
-        const int g = th * 4 + kq * 2 + h;
-        a_off[kq] = rowA * ROWB + ((g ^ fA) << 4);
-        xlo_off[kq] = DY_BYTES + rowB * ROWB + ((g ^ fB) << 4);
-        xhi_off[kq] = (g + 1 < 8) ? DY_BYTES + rowB * ROWB + (((g + 1) ^ fB) << 4) : DY_BYTES + 64 * ROWB + rowB * 16;
-    }
-
-    // ---- pipeline: NBUF-1 steps of loads in flight; a step's loads are waited for (counted vmcnt) before the barrier that
-    // precedes its use.
-#pragma unroll
-    for (int i = 0; i < NBUF - 1; i++) {
-        begin_loads(s0 + i < s1);
-        issue_range(std::integral_constant<int, 0>{}, std::integral_constant<int, NPIECE>{});
-    }
-    if (NBUF == 3) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NPIECE));
-    else asm volatile("s_waitcnt vmcnt(0)");
-    __syncthreads();
-    int cbuf = 0;
-    for (int step = s0; step < s1; step++) {
-        constexpr int xoff = XOFF;
-        begin_loads(step + NBUF - 1 < s1);                 // into the buffer everyone left at the last barrier
-        const char* buf = lds + cbuf * BUF;
-        typedef typename std::conditional<std::is_same<T, bf16_t>::value, bf16x8, f16x8>::type frag_t;
-        static_for<0, 2>([&](auto kqc) __attribute__((always_inline)) {
-            constexpr int kq = decltype(kqc)::value;
-            frag_t a[R];
-#pragma unroll
-            for (int rr = 0; rr < R; rr++) a[rr] = *(const frag_t*)(buf + a_off[kq] + rr * (64 * ROWB));
-            static_for<0, XR>([&](auto xrc) __attribute__((always_inline)) {
-                constexpr int xr = decltype(xrc)::value;
-                constexpr int it = kq * XR + xr, NIT = 2 * XR;
-                issue_range(std::integral_constant<int, (it * NPIECE) / NIT>{}, std::integral_constant<int, ((it + 1) * NPIECE) / NIT>{});
-                const uint4 lo = *(const uint4*)(buf + xlo_off[kq] + xr * XBLK);
-                uint4 hi = lo;
-                if (TAIL) {
-                    hi = *(const uint4*)(buf + xhi_off[kq] + xr * XBLK);
-                    asm volatile("" : : "v"(hi.y), "v"(hi.z), "v"(hi.w));     // keep the read a full (conflict-free) b128
-                }
-                const unsigned d[6] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y};
-#pragma unroll
-                for (int sft = 0; sft < KS; sft++) {
-                    union { unsigned u[4]; frag_t f; } b;
-                    const int sh = sft + xoff;                            // element shift in [0, 3], compile-time
-#pragma unroll
-                    for (int w = 0; w < 4; w++) {
-                        const unsigned e0 = d[w], e1 = d[w + 1], e2 = d[(w + 2) % 6];
-                        const unsigned odd_lo = __builtin_amdgcn_alignbyte(e1, e0, 2);
-                        const unsigned odd_hi = __builtin_amdgcn_alignbyte(e2, e1, 2);
-                        b.u[w] = (sh == 0) ? e0 : (sh == 1) ? odd_lo : (sh == 2) ? e1 : odd_hi;
-                    }
-#pragma unroll
-                    for (int rr = 0; rr < R; rr++) {
-                        const int r = xr - rr;
-                        const int t = r * KS + sft;
-                        if (r >= 0 && r < KS) {
-                            if constexpr (std::is_same<T, bf16_t>::value)
-                                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rr], b.f, acc[t], 0, 0, 0);
-                            else
-                                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rr], b.f, acc[t], 0, 0, 0);
-                        }
-                    }
-                }
-            });
-        });
-        // the next step's loads (issued NBUF-2 iterations ago, or just now when NBUF == 2) must have landed
-        if (NBUF == 3) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NPIECE));
-        else asm volatile("s_waitcnt vmcnt(0)");
-        __syncthreads();
-        if (++cbuf == NBUF) cbuf = 0;
-    }
-    // ---- add the two pixel halves through LDS (the ring is free now): th 1 parks its accumulators, th 0 adds them and
-    // writes the partial tile D[row = o][col = i].
-    asm volatile("s_waitcnt vmcnt(0)");
-    __syncthreads();
-    {
-        float* red = (float*)lds;
-        constexpr int TPR_CAP = (NBUF * BUF) / (4 * 16 * 64 * (int)sizeof(float));     // taps per round
-        constexpr int TPR = TPR_CAP < KK ? TPR_CAP : KK;
-        static_assert(TPR >= 1, "LDS too small for the half-sum");
-        const int wv4 = wave & 3;
-#pragma unroll
-        for (int t0 = 0; t0 < KK; t0 += TPR) {
-            if (t0 > 0) __syncthreads();
-            if (th == 1) {
-#pragma unroll
-                for (int t = t0; t < t0 + TPR && t < KK; t++)
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg++) red[((wv4 * TPR + (t - t0)) * 16 + reg) * 64 + lane] = acc[t][reg];
-            }
-            __syncthreads();
-            if (th == 0) {
-#pragma unroll
-                for (int t = t0; t < t0 + TPR && t < KK; t++)
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg++) acc[t][reg] += red[((wv4 * TPR + (t - t0)) * 16 + reg) * 64 + lane];
-            }
-        }
-    }
-    if (th == 0) {
-        float* out = p.part + (size_t)split * p.O * p.I * KK;
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            const int o = o0 + wo * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-            const int i = i0 + wi * 32 + r32;
-            if (o < p.O && i < p.I) {
-                float* dst = out + ((size_t)o * p.I + i) * KK;
-#pragma unroll
-                for (int t = 0; t < KK; t++) dst[t] = acc[t][reg];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// 16-bit weight gradient, 16-byte LDS-DMA pieces.  The address unit spends about the same time on a wave instruction
-// whatever its width, and conv2d_wgrad16_kernel is bound by exactly that (208 dword pieces per step); this variant moves
-// the same bytes in 56 pieces of 16 B per lane.  A lane fetches one granule = 8 pixels from a 4-byte aligned address, so
-// validity is per granule, not per pixel:
-//   * x is staged from column q0 - 8: the granule left of the image is dropped whole (pad = 2: taps reach back 2 columns);
-//   * the granule that straddles the right edge of x brings the head of the next row: the wave that loaded it zeroes those
-//     pixels in LDS before the barrier;
-//   * dy beyond its right edge then multiplies zeros of x (its columns q >= Q pair with x columns >= W), whatever it holds.
-// Supported: KS = 3 with pad = 2 (the generator's convs) and KS = 1 with pad = 0; everything else takes the dword kernel.
-// LDS image of one step:   dy [rr 0..1][o 64][8 granules]   x main [xr][ch 64][8 granules]   x tail [ch>>3][xr][ch&7][1 granule]
-// with granule g of row r at slot g ^ ((r >> 1) & 7); B fragments of tap column s are the 5-dword window
-// (granule g).d3, (granule g+1).d0..3 shifted by s.
-
-// SMALL (both tensors below 2^31 bytes): ONE buffer descriptor per tensor for the whole kernel; a piece's position is a 32-bit
-// offset added to the lane offsets and its validity (row outside the image, dead step) an OR mask on bit 31.  The general form
-// rebuilds a 128-bit descriptor per piece -- 64-bit base, exact record count, validity select, three v_readfirstlane --
-// ~45 scalar instructions per piece, 310 per K step of 36 MFMAs: the wave's own instruction stream, not the matrix pipe, set
-// the step time (PMC r01e: MFMA pipe 49 % busy, 8.7 SALU per MFMA).
-constexpr int kWgradRing = 3;      // LDS ring depth of conv2d_wgrad16g_kernel (2: measured in profiles/r04_wgrad_ring.txt)
-// X16 (r05): the same tile on v_mfma_f32_16x16x32 -- a wave's 32 (o) x 32 (i) tile is 2 x 2 tiles of 16 x 16 per tap (the same 144
-// accumulator registers), a K step is 32 pixels = FOUR granules, one per 16-lane group: wave th takes pixels 32 th .. 32 th + 31 of the
-// chunk.  ds_read_b128 serves the lanes in groups that hold all 16 rows with TWO neighbouring granules (G, G + 1), so the swizzle is
-// slot = granule ^ (((row >> 1) & 3) << 1): both row sets of a group take the even XOR values once, G and G + 1 differ in bit 0 (G even)
-// or flip bits that keep the even set (G odd: the hi half of the x windows): 16 distinct slots for every read (the (row >> 1) & 7 form
-// of the 32x32x16 kernel is conflict-free only when all lanes of a group read the SAME granule).  A/B of the shapes: profiles/r05_*.
-template <typename T, int KS, int NBUF, bool SMALL, bool X16 = false>
-__global__ __launch_bounds__(512, 1) void conv2d_wgrad16g_kernel(WgradParams p) {
-    static_assert(sizeof(T) == 2, "16-bit types only");
-    constexpr int R = 2, KK = KS * KS, XR = R + KS - 1;
-    auto swz = [](int row) __attribute__((always_inline)) { return X16 ? (((row >> 1) & 3) << 1) : ((row >> 1) & 7); };
-    constexpr int ROWB = 128;                       // bytes of one staged row (64 pixels)
-    constexpr int DY_BYTES = R * 64 * ROWB;
-    constexpr int XMAIN = XR * 64 * ROWB;
-    constexpr bool TAIL = KS > 1;
-    constexpr int XTAIL = TAIL ? 8 * XR * 8 * 16 : 0;               // [ch>>3][xr][ch&7][16 B]
-    constexpr int BUF = DY_BYTES + XMAIN + XTAIL;
-    constexpr int NPIECE = R + XR + (TAIL ? 1 : 0);                 // LDS-DMA instructions per wave and step
-    constexpr int XLEAD = TAIL ? 8 : 0;                             // x is staged from column q0 - XLEAD
-    constexpr unsigned kOob = 0x80000000u;
-    static_assert(XR * 8 <= 64, "tail piece: one lane per (xr, channel)");
-    __shared__ __attribute__((aligned(1024))) char lds[NBUF * BUF];
-    const unsigned lds0 = (unsigned)(unsigned long long)(__attribute__((address_space(3))) void*)lds;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // th: which half of the chunk's pixels this wave accumulates; (wo, wi): its 32 x 32 quadrant of the tile.  The two waves of a SIMD
-    // (wave, wave + 4) take DIAGONALLY OPPOSITE quadrants: when a tile's rows 32.. or columns 32.. lie outside the matrix (the last tile of a
-    // 91-channel operand: 27 live rows), every SIMD then holds one live and one idle wave instead of two SIMDs holding both
-    const int th = wave >> 2, wo = (wave & 1) ^ th, wi = ((wave >> 1) & 1) ^ th;
-    const int r32 = lane & 31, h = lane >> 5;
-
-    const int tiles_i = cdiv(p.I, 64), tiles_o = cdiv(p.O, 64);
-    int bid = blockIdx.x;
-    const int n_full = p.fo * p.fi, total = n_full * p.splits + (tiles_i * tiles_o - n_full) * p.splits_p;
-    bid = xcd_order(bid, total);          // XCD x: contiguous logical ids (split-major within a class)
-    // integer division runs on the vector pipe even for uniform operands: pin the results to SGPRs, or every per-step address
-    // and descriptor computation derived from them runs as 64-bit VALU code + v_readfirstlane (measured: ~130 vector
-    // instructions per step beside the 36 MFMAs)
-    int split, obk, ib, my_steps;
-    if (bid < n_full * p.splits) {
-        split = __builtin_amdgcn_readfirstlane(bid / n_full);
-        const int tile = bid - split * n_full;                                       // index in the fo x fi grid of full tiles
-        obk = __builtin_amdgcn_readfirstlane(tile / p.fi);
-        ib = tile - obk * p.fi;
-        my_steps = p.steps_per_split;
-    } else {
-        // partial tiles: the column ib = fi (when fi < tiles_i), all tiles_o rows of it, then the row obk = fo (fo < tiles_o), ib < fi
-        const int rel = bid - n_full * p.splits, n_part = tiles_i * tiles_o - n_full;
-        split = __builtin_amdgcn_readfirstlane(rel / n_part);
-        const int j = rel - split * n_part;
-        const int ncol = p.fi < tiles_i ? tiles_o : 0;
-        if (j < ncol) { obk = j; ib = p.fi; } else { obk = p.fo; ib = j - ncol; }
-        my_steps = p.steps_per_split_p;
-    }
-    const int o0 = obk * 64, i0 = ib * 64;
-
-    // 32x32x16: one 32 x 32 tile per tap, element e = MFMA register e; 16x16x32: element 4 (2 ob2 + ib2) + reg of the (ob2, ib2) 16 x 16 tile
-    f32x16 acc[KK];
-#pragma unroll
-    for (int t = 0; t < KK; t++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) acc[t][e] = 0.f;
-
-    // ---- load maps.  Wave w stages rows (channels) 8w..8w+7 of both operands: lane = (row, slot) of an 8-row piece.
-    const int prow = 8 * wave + (lane >> 3), pslot = lane & 7;
-    const int pg = pslot ^ swz(prow);                                            // logical granule that lives in this slot
-    const int pq = p.P * p.lddy, hw = p.H * p.ldx;                                // plane strides (rows by pitch)
-    // p.W also feeds per-lane offsets, so the compiler keeps it in a VGPR and then evaluates the (uniform) row addresses of the
-    // x pieces on the vector pipe; an explicit scalar copy keeps them on the SALU
-    const int Ws = __builtin_amdgcn_readfirstlane(p.ldx), Qs = __builtin_amdgcn_readfirstlane(p.lddy);
-    const unsigned lp_dy = (o0 + prow < p.O) ? (unsigned)(prow * pq * 2 + pg * 16) : kOob;
-    const unsigned lp_x = (i0 + prow < p.I) ? (unsigned)(prow * hw * 2 + pg * 16) : kOob;
-    const int txr = lane >> 3, trow = 8 * wave + (lane & 7);                     // tail piece: lane = (xr, row), lanes >= 8 XR idle
-    const unsigned lp_t = (i0 + trow < p.I) ? (unsigned)((trow * hw + txr * p.ldx + 64) * 2) : kOob;
-    const long long dy_bytes = (long long)p.N * p.O * pq * 2, x_bytes = (long long)p.N * p.I * hw * 2;
-    // SMALL: the two descriptors of the kernel (records = the tensor's bytes: a granule straddling its end reads zeros there)
-    const i32x4 rs_dy = make_rsrc(p.dy, SMALL ? (int)dy_bytes : 0), rs_x = make_rsrc(p.x, SMALL ? (int)x_bytes : 0);
-    unsigned c_dy32 = 0, c_x32 = 0;                                              // byte offsets of (image n, channel o0 / i0)
-
-    const int steps_per_img = p.rowgroups * p.qchunks;
-    int s0 = split * my_steps;
-    int s1 = min(s0 + my_steps, p.N * steps_per_img);
-    if (p.splits_img > 0) {                                                      // image-aligned shares (my_steps = ceil(steps_per_img / splits_img))
-        const int img = __builtin_amdgcn_readfirstlane(split / p.splits_img), j = split - img * p.splits_img;
-        s0 = img * steps_per_img + j * my_steps;
-        s1 = min(s0 + my_steps, (img + 1) * steps_per_img);
-        if (s1 < s0) s1 = s0;                                                    // (a share past the image's last step: zeros)
-    }
-    // a quadrant wholly outside the matrix: its waves only issue their share of the loads
-    const bool quad_dead = o0 + wo * 32 >= p.O || i0 + wi * 32 >= p.I;
-    int ld_n = __builtin_amdgcn_readfirstlane(s0 / steps_per_img);
-    int ld_rg = __builtin_amdgcn_readfirstlane((s0 - ld_n * steps_per_img) / p.qchunks);
-    int ld_qc = s0 - ld_n * steps_per_img - ld_rg * p.qchunks;
-    int ld_buf = 0;
-    int u_qc = ld_qc;                                                            // chunk (of its row pair) of the step being multiplied
-
-    // state of the step being loaded (c_*) and of the one before it (f_*: the step whose x edge is fixed up next)
-    int c_prow0 = 0, c_q0 = 0, c_live = 0, f_q0 = 0, f_live = 0;
-    unsigned c_bufa = 0, f_bufa = 0, v_dy = 0, v_x = 0, v_t = 0;
-    long long c_dyoff = 0, c_xoff = 0;                                           // byte offsets of the image (n) in dy / x
-    auto begin_loads = [&](bool live) __attribute__((always_inline)) {
-        f_q0 = c_q0; f_live = c_live; f_bufa = c_bufa;
-        c_live = live ? -1 : 0;                                                  // a dead step still issues its pieces (0 records)
-        c_prow0 = ld_rg * R; c_q0 = ld_qc * kWgKQ;
-        c_bufa = ld_buf * BUF;
-        const int xorg = c_q0 - XLEAD;
-        v_dy = lp_dy | ((unsigned)!(c_q0 + 8 * pg < p.Q) << 31);
-        v_x = lp_x | ((unsigned)!((unsigned)(xorg + 8 * pg) < (unsigned)p.W) << 31);
-        v_t = lp_t | ((unsigned)!((unsigned)(xorg + 64) < (unsigned)p.W && (unsigned)(c_prow0 - p.pad + txr) < (unsigned)p.H) << 31);
-        c_dyoff = (long long)ld_n * p.O * pq * 2;
-        c_xoff = (long long)ld_n * p.I * hw * 2;
-        if (SMALL) {
-            c_dy32 = (unsigned)((ld_n * p.O + o0) * pq) * 2u;
-            c_x32 = (unsigned)((ld_n * p.I + i0) * hw) * 2u;
-        }
-        if (live) {
-            if (++ld_qc == p.qchunks) {
-                ld_qc = 0;
-                if (++ld_rg == p.rowgroups) { ld_rg = 0; ld_n++; }
-            }
-        }
-        if (++ld_buf == NBUF) ld_buf = 0;
-    };
-    // records = bytes up to the end of the tensor (a straddling granule's dwords beyond it read as zero), 0 for a dead row
-    auto records = [&](long long remaining, bool ok) __attribute__((always_inline)) -> int {
-        const int r = remaining > 0x7fffffffll ? 0x7fffffff : (int)remaining;
-        return (ok && r > 0) ? (r & c_live) : 0;
-    };
-    auto issue_piece = [&](auto idx) __attribute__((always_inline)) {
-        constexpr int I = decltype(idx)::value;
-        if constexpr (SMALL) {
-            // offset of the piece (scalar) + lane offset; invalid lanes carry bit 31 in v_*, an invalid piece ORs it in for all
-            if constexpr (I < R) {
-                constexpr int rr = I;
-                const int row = c_prow0 + rr;
-                const unsigned soff = c_dy32 + (unsigned)(row * Qs + c_q0) * 2u;
-                const unsigned sinv = (row < p.P && c_live) ? 0u : kOob;
-                lds_dma_b128(rs_dy, ((v_dy & ~kOob) + soff) | (v_dy & kOob) | sinv, lds0 + c_bufa + rr * (64 * ROWB) + wave * 1024);
-            } else if constexpr (I < R + XR) {
-                constexpr int xr = I - R;
-                const int row = c_prow0 - p.pad + xr;
-                const unsigned soff = c_x32 + (unsigned)(row * Ws + c_q0 - XLEAD) * 2u;
-                const unsigned sinv = ((unsigned)row < (unsigned)p.H && c_live) ? 0u : kOob;
-                lds_dma_b128(rs_x, ((v_x & ~kOob) + soff) | (v_x & kOob) | sinv, lds0 + c_bufa + DY_BYTES + xr * (64 * ROWB) + wave * 1024);
-            } else {
-                const int row = c_prow0 - p.pad;                                 // lanes add their xr
-                const unsigned soff = c_x32 + (unsigned)(row * Ws + c_q0 - XLEAD) * 2u;
-                const unsigned sinv = c_live ? 0u : kOob;
-                if (lane < 8 * XR)
-                    lds_dma_b128(rs_x, ((v_t & ~kOob) + soff) | (v_t & kOob) | sinv, lds0 + c_bufa + DY_BYTES + XMAIN + wave * (XR * 128));
-            }
-        } else if constexpr (I < R) {
-            constexpr int rr = I;
-            const int row = c_prow0 + rr;
-            const long long off = c_dyoff + ((long long)o0 * pq + row * Qs + c_q0) * 2;
-            lds_dma_b128(make_rsrc((const char*)p.dy + off, records(dy_bytes - off, row < p.P)), v_dy,
-                         lds0 + c_bufa + rr * (64 * ROWB) + wave * 1024);
-        } else if constexpr (I < R + XR) {
-            constexpr int xr = I - R;
-            const int row = c_prow0 - p.pad + xr;
-            const long long off = c_xoff + ((long long)i0 * hw + row * Ws + c_q0 - XLEAD) * 2;
-            lds_dma_b128(make_rsrc((const char*)p.x + off, records(x_bytes - off, (unsigned)row < (unsigned)p.H)), v_x,
-                         lds0 + c_bufa + DY_BYTES + xr * (64 * ROWB) + wave * 1024);
-        } else {
-            const int row = c_prow0 - p.pad;                                     // lanes add their xr
-            const long long off = c_xoff + ((long long)i0 * hw + row * Ws + c_q0 - XLEAD) * 2;
-            if (lane < 8 * XR)
-                lds_dma_b128(make_rsrc((const char*)p.x + off, records(x_bytes - off, true)), v_t,
-                             lds0 + c_bufa + DY_BYTES + XMAIN + wave * (XR * 128));
-        }
-    };
-    auto issue_range = [&](auto lo, auto hi) __attribute__((always_inline)) {
-        constexpr int LO = decltype(lo)::value, HI = decltype(hi)::value;
-        static_for<LO, HI>([&](auto i) __attribute__((always_inline)) { issue_piece(i); });
-    };
-    // zero the pixels right of x's edge inside the granule that straddles it, in the rows this wave loaded (step f_*)
-    auto fix_edge = [&]() __attribute__((always_inline)) {
-        const int rel = p.W - (f_q0 - XLEAD);                                    // edge column relative to the staged origin
-        const int gw = rel >> 3, vw = rel & 7;                                   // granule, valid pixels in it (even)
-        if (f_live && vw != 0 && gw >= 0 && gw <= (TAIL ? 8 : 7) && lane < 8 * XR) {
-            const int xr = lane >> 3, row = 8 * wave + (lane & 7);
-            char* g = lds + f_bufa + DY_BYTES +
-                      (gw < 8 ? xr * (64 * ROWB) + row * ROWB + ((gw ^ swz(row)) << 4) : XMAIN + wave * (XR * 128) + lane * 16);
-#pragma unroll
-            for (int d = 1; d < 4; d++)
-                if (2 * d >= vw) *(unsigned*)(g + 4 * d) = 0u;
-        }
-    };
-
-    // ---- fragment read offsets inside a buffer (swizzled)
-    // X16: index 0 / 1 = the 16-row block (ob2 for dy, ib2 for x); lane = (row c16, granule G = 4 th + (lane >> 4)) -- rows 16 apart share
-    // the swizzle, so block 1 is block 0 + 16 rows (the tail granule of x: + 2 channel octets)
-    const int c16 = lane & 15, g4 = lane >> 4;
-    const int rowA = wo * 32 + (X16 ? c16 : r32), rowB = wi * 32 + (X16 ? c16 : r32);
-    const int fA = swz(rowA), fB = swz(rowB);
-    unsigned a_off[2], x0_off[2], x1_off[2][XR];
-#pragma unroll
-    for (int kq = 0; kq < 2; kq++) {
-        // 32x32x16: 16-pixel groups interleaved over the sibling waves: th 0: 0, 2; th 1: 1, 3
-        const int g = X16 ? 4 * th + g4 : kq * 4 + th * 2 + h;
-        const int ra = X16 ? rowA + 16 * kq : rowA, rb = X16 ? rowB + 16 * kq : rowB;
-        a_off[kq] = ra * ROWB + ((g ^ fA) << 4);
-        x0_off[kq] = DY_BYTES + rb * ROWB + ((g ^ fB) << 4);
-#pragma unroll
-        for (int xr = 0; xr < XR; xr++)
-            x1_off[kq][xr] = (g + 1 < 8) ? DY_BYTES + xr * (64 * ROWB) + rb * ROWB + (((g + 1) ^ fB) << 4)
-                                         : DY_BYTES + XMAIN + (rb >> 3) * (XR * 128) + xr * 128 + (rb & 7) * 16;
-    }
-
-    // ---- pipeline: NBUF-1 steps of loads in flight; a step's loads are waited for (counted vmcnt) before the barrier that
-    // precedes its use.
-#pragma unroll
-    for (int i = 0; i < NBUF - 1; i++) {
-        begin_loads(s0 + i < s1);
-        issue_range(std::integral_constant<int, 0>{}, std::integral_constant<int, NPIECE>{});
-    }
-    asm volatile("s_waitcnt vmcnt(0)");
-    if (NBUF == 3) {                       // both prologue steps have landed: fix both edges
-        fix_edge();
-        { const int q = f_q0, l = f_live; const unsigned b = f_bufa; f_q0 = c_q0; f_live = c_live; f_bufa = c_bufa; fix_edge(); f_q0 = q; f_live = l; f_bufa = b; }
-    } else {
-        f_q0 = c_q0; f_live = c_live; f_bufa = c_bufa;
-        fix_edge();
-    }
-    __syncthreads();
-    int cbuf = 0;
-    for (int step = s0; step < s1; step++) {
-        // LATE (16x16x32, 3x3): the live waves run begin_loads' ~50 scalar / vector instructions after their first iteration's MFMAs
-        // instead of between the barrier and the first MFMA of all eight waves at once (their pieces then go out in iterations 1 .. 7):
-        // 8.55 -> 8.28 ms in the step (profiles/r05_wgrad_late_ab.txt)
-        constexpr bool LATE = X16 && TAIL;
-        if constexpr (!LATE) begin_loads(step + NBUF - 1 < s1);                 // into the buffer everyone left at the last barrier
-        const char* buf = lds + cbuf * BUF;
-        typedef typename std::conditional<std::is_same<T, bf16_t>::value, bf16x8, f16x8>::type frag_t;
-        // 16-pixel groups of the chunk that lie beyond the row's end would multiply zeros (rows of 86, 150, 278 pixels end
-        // with 22 pixels of a 64-pixel chunk): a wave skips its dead groups and only issues its share of the next loads.  The
-        // groups alternate between the two waves that share a SIMD (th 0 / th 1), so a 22-pixel chunk costs both one group.
-        const int vq = quad_dead ? 0 : p.Q - u_qc * kWgKQ;
-        if (++u_qc == p.qchunks) u_qc = 0;
-        // one x row of one 16-pixel group: the next loads' share, the three shifted B fragments, 3 or 6 MFMAs
-        auto row_mfmas = [&](auto kqc, auto xrc, const uint4 lo, const uint4 hi, const frag_t* a) __attribute__((always_inline)) {
-            constexpr int kq = decltype(kqc)::value, xr = decltype(xrc)::value;
-            constexpr int it = kq * XR + xr, NIT = 2 * XR;
-            issue_range(std::integral_constant<int, (it * NPIECE) / NIT>{}, std::integral_constant<int, ((it + 1) * NPIECE) / NIT>{});
-            asm volatile("" : : "v"(lo.x), "v"(lo.y), "v"(lo.z));               // keep the read a full (conflict-free) b128
-            const unsigned d[5] = {lo.w, hi.x, hi.y, hi.z, hi.w};               // pixels 8g+6 .. 8g+15 of the staged row
-#pragma unroll
-            for (int sft = 0; sft < KS; sft++) {
-                union { unsigned u[4]; frag_t f; } b;
-#pragma unroll
-                for (int w = 0; w < 4; w++)
-                    b.u[w] = (sft == 0) ? d[w] : (sft == 1) ? __builtin_amdgcn_alignbyte(d[w + 1], d[w], 2) : d[w + 1];
-#pragma unroll
-                for (int rr = 0; rr < R; rr++) {
-                    const int r = xr - rr;
-                    const int t = r * KS + sft;
-                    if (r >= 0 && r < KS) {
-                        if constexpr (std::is_same<T, bf16_t>::value)
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rr], b.f, acc[t], 0, 0, 0);
-                        else
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rr], b.f, acc[t], 0, 0, 0);
-                    }
-                }
-            }
-        };
-        if constexpr (X16) {
-            // one K step of 32 pixels per wave: 8 iterations (x row, 16-channel block of x), each the next loads' share, one window
-            // (read one iteration ahead), its KS shifted B fragments and their MFMAs into the (o block, i block) tiles of the taps
-            typedef __attribute__((ext_vector_type(4))) float cf32x4;
-            auto mma = [&](const frag_t& av, const frag_t& bv, int t, int blk) __attribute__((always_inline)) {
-                cf32x4 c = {acc[t][4 * blk + 0], acc[t][4 * blk + 1], acc[t][4 * blk + 2], acc[t][4 * blk + 3]};
-                if constexpr (std::is_same<T, bf16_t>::value) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, c, 0, 0, 0);
-                else c = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, c, 0, 0, 0);
-                acc[t][4 * blk + 0] = c[0]; acc[t][4 * blk + 1] = c[1]; acc[t][4 * blk + 2] = c[2]; acc[t][4 * blk + 3] = c[3];
-            };
-            if (th * 32 >= vq) {                       // this wave's 32 pixels lie beyond the row's end: only its share of the next loads
-                if constexpr (LATE) begin_loads(step + NBUF - 1 < s1);
-                issue_range(std::integral_constant<int, 0>{}, std::integral_constant<int, NPIECE>{});
-            } else if constexpr (!TAIL) {
-                frag_t a[2][R];
-#pragma unroll
-                for (int ob2 = 0; ob2 < 2; ob2++)
-#pragma unroll
-                    for (int rr = 0; rr < R; rr++) a[ob2][rr] = *(const frag_t*)(buf + a_off[ob2] + rr * (64 * ROWB));
-                static_for<0, 2 * XR>([&](auto itc) __attribute__((always_inline)) {
-                    constexpr int it = decltype(itc)::value, xr = it >> 1, ib2 = it & 1, NIT = 2 * XR;
-                    issue_range(std::integral_constant<int, (it * NPIECE) / NIT>{}, std::integral_constant<int, ((it + 1) * NPIECE) / NIT>{});
-                    const frag_t bv = *(const frag_t*)(buf + x0_off[ib2] + xr * (64 * ROWB));
-#pragma unroll
-                    for (int ob2 = 0; ob2 < 2; ob2++) mma(a[ob2][xr], bv, 0, 2 * ob2 + ib2);
-                });
-            } else {
-                frag_t a[2][R];
-#pragma unroll
-                for (int ob2 = 0; ob2 < 2; ob2++)
-#pragma unroll
-                    for (int rr = 0; rr < R; rr++) a[ob2][rr] = *(const frag_t*)(buf + a_off[ob2] + rr * (64 * ROWB));
-                uint4 lo_n = *(const uint4*)(buf + x0_off[0]);
-                uint4 hi_n = *(const uint4*)(buf + x1_off[0][0]);
-                static_for<0, 2 * XR>([&](auto itc) __attribute__((always_inline)) {
-                    constexpr int it = decltype(itc)::value, xr = it >> 1, ib2 = it & 1, NIT = 2 * XR;
-                    const uint4 lo = lo_n, hi = hi_n;
-                    if constexpr (it + 1 < NIT) {
-                        constexpr int xr1 = (it + 1) >> 1, ib1 = (it + 1) & 1;
-                        lo_n = *(const uint4*)(buf + x0_off[ib1] + xr1 * (64 * ROWB));
-                        hi_n = *(const uint4*)(buf + x1_off[ib1][xr1]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (LATE) {
-                        static_assert(!LATE || NPIECE == NIT - 1, "one piece per iteration after the first");
-                        if constexpr (it > 0) issue_piece(std::integral_constant<int, it - 1>{});
-                    } else
-                        issue_range(std::integral_constant<int, (it * NPIECE) / NIT>{}, std::integral_constant<int, ((it + 1) * NPIECE) / NIT>{});
-                    asm volatile("" : : "v"(lo.x), "v"(lo.y), "v"(lo.z));               // keep the read a full (conflict-free) b128
-                    const unsigned d[5] = {lo.w, hi.x, hi.y, hi.z, hi.w};               // pixels 8G+6 .. 8G+15 of the staged row
-#pragma unroll
-                    for (int sft = 0; sft < KS; sft++) {
-                        union { unsigned u[4]; frag_t f; } bw;
-#pragma unroll
-                        for (int w = 0; w < 4; w++)
-                            bw.u[w] = (sft == 0) ? d[w] : (sft == 1) ? __builtin_amdgcn_alignbyte(d[w + 1], d[w], 2) : d[w + 1];
-#pragma unroll
-                        for (int rr = 0; rr < R; rr++) {
-                            const int r = xr - rr;
-                            if (r >= 0 && r < KS) {
-#pragma unroll
-                                for (int ob2 = 0; ob2 < 2; ob2++) mma(a[ob2][rr], bw.f, r * KS + sft, 2 * ob2 + ib2);
-                            }
-                        }
-                    }
-                    if constexpr (LATE && it == 0) begin_loads(step + NBUF - 1 < s1);
-                    __builtin_amdgcn_sched_barrier(0);
-                });
-            }
-        } else if constexpr (!TAIL) {
-            static_for<0, 2>([&](auto kqc) __attribute__((always_inline)) {
-                constexpr int kq = decltype(kqc)::value;
-                if ((kq * 2 + th) * 16 >= vq) {
-                    issue_range(std::integral_constant<int, (kq * XR * NPIECE) / (2 * XR)>{}, std::integral_constant<int, ((kq + 1) * XR * NPIECE) / (2 * XR)>{});
-                    return;
-                }
-                frag_t a[R];
-#pragma unroll
-                for (int rr = 0; rr < R; rr++) a[rr] = *(const frag_t*)(buf + a_off[kq] + rr * (64 * ROWB));
-                static_for<0, XR>([&](auto xrc) __attribute__((always_inline)) {
-                    constexpr int xr = decltype(xrc)::value;
-                    constexpr int it = kq * XR + xr, NIT = 2 * XR;
-                    issue_range(std::integral_constant<int, (it * NPIECE) / NIT>{}, std::integral_constant<int, ((it + 1) * NPIECE) / NIT>{});
-                    const frag_t b = *(const frag_t*)(buf + x0_off[kq] + xr * (64 * ROWB));
-                    constexpr int rr = xr;
-                    if constexpr (std::is_same<T, bf16_t>::value) acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[rr], b, acc[0], 0, 0, 0);
-                    else acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rr], b, acc[0], 0, 0, 0);
-                });
-            });
-        } else {
-            // The x windows are read one row ahead of their MFMAs, also across the two groups (left to itself the scheduler emits
-            // read, wait, multiply for every row: eight exposed LDS round trips per step with only the sibling wave to cover
-            // them).  The reads ahead are unconditional -- a dead group's window is simply not used.
-            frag_t a[2][R];
-#pragma unroll
-            for (int rr = 0; rr < R; rr++) a[0][rr] = *(const frag_t*)(buf + a_off[0] + rr * (64 * ROWB));
-            uint4 lo_n = *(const uint4*)(buf + x0_off[0]);
-            uint4 hi_n = *(const uint4*)(buf + x1_off[0][0]);
-            static_for<0, 2>([&](auto kqc) __attribute__((always_inline)) {
-                constexpr int kq = decltype(kqc)::value;
-                if ((kq * 2 + th) * 16 >= vq) {
-                    issue_range(std::integral_constant<int, (kq * XR * NPIECE) / (2 * XR)>{}, std::integral_constant<int, ((kq + 1) * XR * NPIECE) / (2 * XR)>{});
-                    if constexpr (kq == 0) {
-#pragma unroll
-                        for (int rr = 0; rr < R; rr++) a[1][rr] = *(const frag_t*)(buf + a_off[1] + rr * (64 * ROWB));
-                        lo_n = *(const uint4*)(buf + x0_off[1]);
-                        hi_n = *(const uint4*)(buf + x1_off[1][0]);
-                    }
-                    return;
-                }
-                static_for<0, XR>([&](auto xrc) __attribute__((always_inline)) {
-                    constexpr int xr = decltype(xrc)::value;
-                    const uint4 lo = lo_n, hi = hi_n;
-                    if constexpr (xr + 1 < XR) {
-                        lo_n = *(const uint4*)(buf + x0_off[kq] + (xr + 1) * (64 * ROWB));
-                        hi_n = *(const uint4*)(buf + x1_off[kq][xr + 1 < XR ? xr + 1 : xr]);
-                    } else if constexpr (kq == 0) {
-                        lo_n = *(const uint4*)(buf + x0_off[1]);
-                        hi_n = *(const uint4*)(buf + x1_off[1][0]);
-                    }
-                    if constexpr (kq == 0 && xr == 1) {
-#pragma unroll
-                        for (int rr = 0; rr < R; rr++) a[1][rr] = *(const frag_t*)(buf + a_off[1] + rr * (64 * ROWB));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    row_mfmas(kqc, xrc, lo, hi, a[kq]);
-                    __builtin_amdgcn_sched_barrier(0);
-                });
-            });
-        }
-        // the next step's loads (issued NBUF-2 iterations ago, or just now when NBUF == 2) must have landed; patch its edge
-        if (NBUF == 3) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(NPIECE));
-        else { asm volatile("s_waitcnt vmcnt(0)"); f_q0 = c_q0; f_live = c_live; f_bufa = c_bufa; }
-        fix_edge();
-        __syncthreads();
-        if (++cbuf == NBUF) cbuf = 0;
-    }
-    // ---- add the two pixel halves through LDS (the ring is free now): th 1 parks its accumulators, th 0 adds them and
-    // writes the partial tile D[row = o][col = i].
-    asm volatile("s_waitcnt vmcnt(0)");
-    __syncthreads();
-    {
-        float* red = (float*)lds;
-        constexpr int TPR_CAP = (NBUF * BUF) / (4 * 16 * 64 * (int)sizeof(float));     // taps per round
-        constexpr int TPR = TPR_CAP < KK ? TPR_CAP : KK;
-        static_assert(TPR >= 1, "LDS too small for the half-sum");
-        const int wv4 = wo + 2 * wi;                                     // the quadrant: both pixel halves of it meet in the same slot
-#pragma unroll
-        for (int t0 = 0; t0 < KK; t0 += TPR) {
-            if (t0 > 0) __syncthreads();
-            if (th == 1) {
-#pragma unroll
-                for (int t = t0; t < t0 + TPR && t < KK; t++)
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg++) red[((wv4 * TPR + (t - t0)) * 16 + reg) * 64 + lane] = acc[t][reg];
-            }
-            __syncthreads();
-            if (th == 0) {
-#pragma unroll
-                for (int t = t0; t < t0 + TPR && t < KK; t++)
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg++) acc[t][reg] += red[((wv4 * TPR + (t - t0)) * 16 + reg) * 64 + lane];
-            }
-        }
-    }
-    if (th == 0) {
-        float* out = p.part + (size_t)split * p.O * p.I * KK;
-#pragma unroll
-        for (int reg = 0; reg < 16; reg++) {
-            // 16x16x32: element 4 (2 ob2 + ib2) + r of the (ob2, ib2) tile = row 16 ob2 + 4 (lane >> 4) + r, column 16 ib2 + (lane & 15)
-            const int o = o0 + wo * 32 + (X16 ? 16 * (reg >> 3) + 4 * g4 + (reg & 3) : (reg & 3) + 8 * (reg >> 2) + 4 * h);
-            const int i = i0 + wi * 32 + (X16 ? 16 * ((reg >> 2) & 1) + c16 : r32);
-            if (o < p.O && i < p.I) {
-                float* dst = out + ((size_t)o * p.I + i) * KK;
-#pragma unroll
-                for (int t = 0; t < KK; t++) dst[t] = acc[t][reg];
-            }
-        }
-    }
-}
-
-// Slabs an element's tile wrote (WgradParams: full tiles `splits`, partial ones `splits_p`; the slabs beyond were never written)
-struct WgradSlabs { int I, KK, fo, fi, splits, splits_p; };
-__device__ __forceinline__ int slabs_of(const WgradSlabs& w, long long idx) {
-    if (w.splits_p == w.splits) return w.splits;
-    const int oi = (int)(idx / w.KK), o = oi / w.I, i = oi - o * w.I;
-    return ((o >> 6) < w.fo && (i >> 6) < w.fi) ? w.splits : w.splits_p;
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(float* __restrict__ dw, const float* __restrict__ part, long long numel, WgradSlabs w) {
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < numel; idx += (long long)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        const int splits = slabs_of(w, idx);
-        for (int k = 0; k < splits; k++) s += part[(size_t)k * numel + idx];
-        dw[idx] = s;
-    }
-}
-
-// Same reduction for numel % 4 == 0 with 16-byte loads and the split index spread over the workgroup: 256 threads =
-// COLS float4 columns x (256 / COLS) split groups, group partials summed through LDS.  A 64 -> 64 layer has 36,864 outputs and 256
-// splits (151 MB of partials): one thread per output is 144 workgroups of serial 4-byte loads on a 256-CU chip.
-template <int COLS>
-__global__ __launch_bounds__(256) void wgrad_reduce4_kernel(float* __restrict__ dw, const float* __restrict__ part, long long numel4, WgradSlabs w) {
-    constexpr int GROUPS = 256 / COLS;
-    typedef __attribute__((ext_vector_type(4))) float f32x4v;
-    __shared__ f32x4v red[GROUPS][COLS];
-    const int col = threadIdx.x % COLS, grp = threadIdx.x / COLS;
-    const long long c4 = (long long)blockIdx.x * COLS + col;
-    f32x4v s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-    if (c4 < numel4) {
-        const f32x4v* src = (const f32x4v*)part + c4;
-        // the four elements of a column may belong to tiles of different classes (9 taps per (o, i): columns straddle i and tile borders):
-        // common slabs as whole vectors, the rest element by element
-        int ne[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) ne[e] = slabs_of(w, 4 * c4 + e);
-        const int splits = min(min(ne[0], ne[1]), min(ne[2], ne[3]));
-        const int most = max(max(ne[0], ne[1]), max(ne[2], ne[3]));
-        for (int k2 = splits + grp; k2 < most; k2 += GROUPS) {
-            const f32x4v v = src[(size_t)k2 * numel4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) s1[e] += k2 < ne[e] ? v[e] : 0.f;
-        }
-        int k = grp;
-        for (; k + 3 * GROUPS < splits; k += 4 * GROUPS) {
-            const f32x4v v0 = src[(size_t)k * numel4], v1 = src[(size_t)(k + GROUPS) * numel4];
-            const f32x4v v2 = src[(size_t)(k + 2 * GROUPS) * numel4], v3 = src[(size_t)(k + 3 * GROUPS) * numel4];
-            s0 += v0; s1 += v1; s0 += v2; s1 += v3;
-        }
-        for (; k < splits; k += GROUPS) s0 += src[(size_t)k * numel4];
-    }
-    s0 += s1;
-    if (GROUPS > 1) {
-        red[grp][col] = s0;
-        __syncthreads();
-        if (grp == 0 && c4 < numel4) {
-#pragma unroll
-            for (int g = 1; g < GROUPS; g++) s0 += red[g][col];
-            ((f32x4v*)dw)[c4] = s0;
-        }
-    } else if (c4 < numel4) {
-        ((f32x4v*)dw)[c4] = s0;
-    }
-}
-
-
-// Slab reduction of an IMAGE-ALIGNED weight gradient (WgradParams::splits_img) that also returns, per image n and input channel i,
-//     dots[n][i] = sum_{o, tap} wq[o][i][tap] * dW_n[o][i][tap]          dW_n = the sum of image n's slabs, wq = w rounded to the conv's 16-bit type
-// = <x[n, i], dx[n, i]> with dx = conv^T(wq, dy): the contraction <dy_n, conv(wq[:, i], x[n, i])> written from the weight side instead of
-// the pixel side.  For the layer below this is <g, z> -- the gradient of the styles its epilogue multiplied z by -- which r01-r05 read from
-// g and z themselves: a full pass over both tensors (312-624 MB per 276^2 layer, 50-118 us) for numbers that these slabs already hold
-// (27-38 MB, read here anyway).  Differs from the pixel-side dot product only by the 16-bit rounding of the STORED dx.
-// One workgroup (16 waves) per input channel i; wave q takes images q, q + 16, ...; lane = output row of a block of 64.
-template <typename T, int KK>
-__global__ __launch_bounds__(1024) void wgrad_reduce_dots_kernel(float* __restrict__ dw, float* __restrict__ dots, const float* __restrict__ part,
-                                                                 const float* __restrict__ w, int N, int O, int I, int splits_img) {
-    // 16 waves: wave q takes images q, q + 16, ... (one each at batch 16); lane = output row of a block of 64.  (r06, first form: 4 waves, four
-    // images each in turn -- 58 us for the 64 -> 64 layer's 38 MB of slabs where the plain reduction took 7.)
-    constexpr int NW = 16;
-    __shared__ float red[NW - 1][64][KK];
-    const int i = blockIdx.x, lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-    const size_t slab = (size_t)O * I * KK;
-    float dotp[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) dotp[k] = 0.f;
-    for (int ob = 0; ob < O; ob += 64) {
-        const int o = ob + lane;
-        const bool live = o < O;
-        const size_t e0 = ((size_t)(live ? o : O - 1) * I + i) * KK;
-        float wq[KK], tot[KK];
-#pragma unroll
-        for (int t = 0; t < KK; t++) { wq[t] = live ? to_f32(from_f32<T>(w[e0 + t])) : 0.f; tot[t] = 0.f; }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int n = q + NW * k;
-            if (n >= N) break;                                  // (wave-uniform)
-            float acc[KK];
-#pragma unroll
-            for (int t = 0; t < KK; t++) acc[t] = 0.f;
-            for (int sp = 0; sp < splits_img; sp++) {
-                const float* src = part + (size_t)(n * splits_img + sp) * slab + e0;
-#pragma unroll
-                for (int t = 0; t < KK; t++) acc[t] += src[t];
-            }
-            float d = 0.f;
-#pragma unroll
-            for (int t = 0; t < KK; t++) { tot[t] += acc[t]; d = fmaf(wq[t], acc[t], d); }
-            dotp[k] += d;
-        }
-        if (ob > 0) __syncthreads();                            // (the previous block's partials have been read)
-        if (q > 0) {
-#pragma unroll
-            for (int t = 0; t < KK; t++) red[q - 1][lane][t] = tot[t];
-        }
-        __syncthreads();
-        if (q == 0 && live) {
-#pragma unroll
-            for (int t = 0; t < KK; t++) {
-                float s = tot[t];
-#pragma unroll
-                for (int k = 0; k < NW - 1; k++) s += red[k][lane][t];
-                dw[e0 + t] = s;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int n = q + NW * k;
-        if (n >= N) break;
-        float d = dotp[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off);
-        if (lane == 0) dots[(size_t)n * I + i] = d;
     }
 }
 
@@ -2980,6 +1363,34 @@ static bool conv_fast_epilogue(const ConvParams& p) {
     return (p.TW & 15) == 0 && (p.ldy & 7) == 0 && (p.Q & 1) == 0;
 }
 
+// conv2d_fwd16x_kernel<T, BM_O, SPLIT> on `grid` workgroups; the fast epilogue where conv_fast_epilogue allows it (plain outputs only)
+template <typename T, int BM_O, bool SPLIT>
+static int launch_fwd16x(const ConvParams& p, dim3 grid, hipStream_t st) {
+    if (!SPLIT && conv_fast_epilogue(p)) hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, false, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, SPLIT>), grid, dim3(256), 0, st, p);
+    return hip_status(hipGetLastError());
+}
+
+// ConvParams of a conv of x [n, cin, h, w] into y [n, cout, P, Q] (row pitches ldx / ldy) on output tiles of TH x TW pixels (patch rows
+// of PWL), packed weights of rows_pad rows in nkc K-chunks: a plain conv (no split-precision terms), one launch for all rows
+static ConvParams conv_params(void* y, const void* x, const void* wp, const float* oscale, const float* obias, int n, int cin, int cout,
+                              int h, int w, int P, int Q, int pad, int ldx, int ldy, int TH, int TW, int PWL, int rows_pad, int nkc) {
+    ConvParams p;
+    p.x = x; p.y = y; p.wp = wp; p.oscale = oscale; p.obias = obias;
+    p.N = n; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w;
+    p.P = P; p.Q = Q;
+    p.pad = pad;
+    p.ldx = ldx; p.ldy = ldy;
+    p.TH = TH; p.TW = TW; p.PWL = PWL;
+    p.tilesX = cdiv(p.Q, p.TW); p.tilesY = cdiv(p.P, p.TH);
+    p.magicTW = (unsigned)((0x100000000ull + (unsigned)p.TW - 1) / (unsigned)p.TW);
+    p.magicTX = magic_u32((unsigned)p.tilesX); p.magicTY = magic_u32((unsigned)p.tilesY); p.magicN = magic_u32((unsigned)p.N); p.magicPC = magic_u32((unsigned)(p.PWL >> 2));
+    p.Opad = rows_pad;
+    p.nkc = nkc;
+    p.nkc_real = p.nkc; p.magicNK = 0; p.term_parts = 0; p.part_bytes = 0; p.last_part_bytes = 0; p.bound_a = p.bound_b = nullptr; p.total_blocks = 0; p.o_base = 0;
+    return p;
+}
+
 // o_base / row_blocks: the launch covers output rows [o_base, o_base + row_blocks * BM_O) (16-bit 3x3 16x16x32 kernel only; 0: all rows)
 template <typename T, int BM_O>
 static int launch_conv(ConvParams p, int ks, hipStream_t st, int o_base = 0, int row_blocks = 0) {
@@ -2989,16 +1400,14 @@ static int launch_conv(ConvParams p, int ks, hipStream_t st, int o_base = 0, int
     dim3 grid((unsigned)blocks), block(256);
     p.total_blocks = (int)blocks;
     if constexpr (sizeof(T) == 2) {
-        if (ks == 3) {
-            // (the 64-row kernel is persistent: one round of three workgroups per CU; the 128-row kernel takes one item per workgroup)
-            const dim3 g16 = BM_O == 64 ? dim3((unsigned)conv_persistent_grid(blocks, 3)) : grid;
-            if (conv_fast_epilogue(p)) hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, false, true>), g16, block, 0, st, p);
-            else hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O>), g16, block, 0, st, p);
-            return hip_status(hipGetLastError());
-        }
+        // 16-bit: 3x3 on the 16x16x32 kernel (the 64-row kernel is persistent: one round of three workgroups per CU; the 128-row kernel
+        // takes one item per workgroup), 1x1 on the general one
+        if (ks == 3) return launch_fwd16x<T, BM_O, false>(p, BM_O == 64 ? dim3((unsigned)conv_persistent_grid(blocks, 3)) : grid, st);
+        hipLaunchKernelGGL((conv2d_fwd_kernel<T, BM_O, 1>), grid, block, 0, st, p);
+    } else {
+        if (ks == 3) hipLaunchKernelGGL((conv2d_fwd_kernel<T, BM_O, 3>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((conv2d_fwd_kernel<T, BM_O, 1>), grid, block, 0, st, p);
     }
-    if (ks == 3) hipLaunchKernelGGL((conv2d_fwd_kernel<T, BM_O, 3>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((conv2d_fwd_kernel<T, BM_O, 1>), grid, block, 0, st, p);
     return hip_status(hipGetLastError());
 }
 
@@ -3122,19 +1531,11 @@ extern "C" int afcm_conv2d_stride2(void* y, const void* x, const void* wpacked, 
     AFCM_REQUIRE(pad >= 0 && pad <= 2, "padding must be in [0, k-1]");
     AFCM_REQUIRE(rows_pad >= cout && rows_pad % 128 == 0, "conv2d_stride2: rows_pad must be a multiple of 128 covering cout");
     AFCM_REQUIRE(h + 2 * pad >= 3 && w + 2 * pad >= 3, "output must be at least 1x1");
-    ConvParams p;
-    p.x = x; p.y = y; p.wp = wpacked; p.oscale = nullptr; p.obias = nullptr;
-    p.N = n; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w;
-    p.P = (h + 2 * pad - 3) / 2 + 1; p.Q = (w + 2 * pad - 3) / 2 + 1;
-    p.pad = pad;
-    p.ldx = w; p.ldy = p.Q;
-    choose_tile_s2(p.P, p.Q, &p.TH, &p.TW, &p.PWL);
-    p.tilesX = cdiv(p.Q, p.TW); p.tilesY = cdiv(p.P, p.TH);
-    p.magicTW = (unsigned)((0x100000000ull + (unsigned)p.TW - 1) / (unsigned)p.TW);
-    p.magicTX = magic_u32((unsigned)p.tilesX); p.magicTY = magic_u32((unsigned)p.tilesY); p.magicN = magic_u32((unsigned)p.N); p.magicPC = magic_u32((unsigned)(p.PWL >> 2));
-    p.Opad = rows_pad;
-    p.nkc = cdiv(cin, afcm_conv2d_block_k(dtype));
-    p.nkc_real = p.nkc; p.magicNK = 0; p.term_parts = 0; p.part_bytes = 0; p.last_part_bytes = 0; p.bound_a = p.bound_b = nullptr; p.total_blocks = 0; p.o_base = 0;
+    const int P = (h + 2 * pad - 3) / 2 + 1, Q = (w + 2 * pad - 3) / 2 + 1;
+    int TH, TW, PWL;
+    choose_tile_s2(P, Q, &TH, &TW, &PWL);
+    const ConvParams p = conv_params(y, x, wpacked, nullptr, nullptr, n, cin, cout, h, w, P, Q, pad, w, Q, TH, TW, PWL, rows_pad,
+                                     cdiv(cin, afcm_conv2d_block_k(dtype)));
     const long long blocks = (long long)p.tilesX * p.tilesY * n * cdiv(cout, 128);
     AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d_stride2: grid of %lld blocks is out of range", blocks);
     AFCM_REQUIRE((long long)cin * h * w * 2ll < (1ll << 31), "conv2d_stride2: image out of range");
@@ -3158,30 +1559,22 @@ extern "C" int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const
     AFCM_REQUIRE(pad >= 0 && pad <= ks - 1, "padding must be in [0, k-1]");
     AFCM_REQUIRE(dtype == AFCM_F32 || (w % 2 == 0), "16-bit conv2d needs an even input width (got %d)", w);
     AFCM_REQUIRE(rows_pad >= cout && rows_pad % 64 == 0, "rows_pad must be a multiple of 64 covering cout");
-    ConvParams p;
-    p.x = x; p.y = y; p.wp = wpacked; p.oscale = oscale; p.obias = obias;
-    p.N = n; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w;
-    p.P = h + 2 * pad - ks + 1; p.Q = w + 2 * pad - ks + 1;
-    AFCM_REQUIRE(p.P >= 1 && p.Q >= 1, "output must be at least 1x1");
-    p.pad = pad;
-    p.ldx = x_pitch ? x_pitch : w; p.ldy = y_pitch ? y_pitch : p.Q;
-    if (p.ldx != w || p.ldy != p.Q) {
+    const int P = h + 2 * pad - ks + 1, Q = w + 2 * pad - ks + 1;
+    AFCM_REQUIRE(P >= 1 && Q >= 1, "output must be at least 1x1");
+    const int ldx = x_pitch ? x_pitch : w, ldy = y_pitch ? y_pitch : Q;
+    if (ldx != w || ldy != Q) {
         AFCM_REQUIRE(dtype != AFCM_F32 && ks == 3, "conv2d: row pitches need the 16-bit 3x3 kernel");
-        AFCM_REQUIRE(p.ldx >= w && p.ldy >= p.Q && ((p.ldx | p.ldy) & 1) == 0, "conv2d: row pitches %d / %d must be even and cover the widths %d / %d", p.ldx, p.ldy, w, p.Q);
-        AFCM_REQUIRE((long long)cout * p.P * p.ldy < (1ll << 30), "conv2d: pitched output image is out of range");
+        AFCM_REQUIRE(ldx >= w && ldy >= Q && ((ldx | ldy) & 1) == 0, "conv2d: row pitches %d / %d must be even and cover the widths %d / %d", ldx, ldy, w, Q);
+        AFCM_REQUIRE((long long)cout * P * ldy < (1ll << 30), "conv2d: pitched output image is out of range");
     }
-    AFCM_REQUIRE(dtype == AFCM_F32 || ks != 3 || (long long)cout * p.P * p.ldy * 2 < (1ll << 30), "conv2d: 16-bit output image of %lld bytes is out of range (< 2^30)", (long long)cout * p.P * p.ldy * 2);
+    AFCM_REQUIRE(dtype == AFCM_F32 || ks != 3 || (long long)cout * P * ldy * 2 < (1ll << 30), "conv2d: 16-bit output image of %lld bytes is out of range (< 2^30)", (long long)cout * P * ldy * 2);
     if (dtype != AFCM_F32 && ks == 3 && cin <= 4 && cout <= 64) {
         // a handful of input channels: the contraction index is (tap column, channel), no channel padding (conv2d_direct.hip; r06)
-        return conv2d_direct_small_cin(x, y, wpacked, oscale, obias, dtype, n, cin, cout, h, w, pad, rows_pad, 32, p.ldx, p.ldy, (hipStream_t)stream);
+        return conv2d_direct_small_cin(x, y, wpacked, oscale, obias, dtype, n, cin, cout, h, w, pad, rows_pad, 32, ldx, ldy, (hipStream_t)stream);
     }
-    choose_tile(p.P, p.Q, ks, &p.TH, &p.TW, &p.PWL, (dtype != AFCM_F32 && ks == 3) ? kPatchMaxX16 : kPatchMax);
-    p.tilesX = cdiv(p.Q, p.TW); p.tilesY = cdiv(p.P, p.TH);
-    p.magicTW = (unsigned)((0x100000000ull + (unsigned)p.TW - 1) / (unsigned)p.TW);
-    p.magicTX = magic_u32((unsigned)p.tilesX); p.magicTY = magic_u32((unsigned)p.tilesY); p.magicN = magic_u32((unsigned)p.N); p.magicPC = magic_u32((unsigned)(p.PWL >> 2));
-    p.Opad = rows_pad;
-    p.nkc = cdiv(cin, conv_bk(dtype, ks));
-    p.nkc_real = p.nkc; p.magicNK = 0; p.term_parts = 0; p.part_bytes = 0; p.last_part_bytes = 0; p.bound_a = p.bound_b = nullptr; p.total_blocks = 0; p.o_base = 0;
+    int TH, TW, PWL;
+    choose_tile(P, Q, ks, &TH, &TW, &PWL, (dtype != AFCM_F32 && ks == 3) ? kPatchMaxX16 : kPatchMax);
+    ConvParams p = conv_params(y, x, wpacked, oscale, obias, n, cin, cout, h, w, P, Q, pad, ldx, ldy, TH, TW, PWL, rows_pad, cdiv(cin, conv_bk(dtype, ks)));
     hipStream_t st = (hipStream_t)stream;
     // 64-row blocks when they waste fewer padded rows than 128-row blocks
     const bool small = (rows_pad % 128 != 0) || cout <= 64;
@@ -3193,14 +1586,9 @@ extern "C" int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const
         // 96-row blocks instead of 128 + 64 measured the same: profiles/r05_conv_bm96_ab.txt)
         const long long blocks = (long long)p.tilesX * p.tilesY * p.N * cdiv(cout, 96);
         AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d: grid of %lld blocks is out of range", blocks);
-        p.total_blocks = (int)blocks; p.o_base = 0;
+        p.total_blocks = (int)blocks;
         const dim3 g96((unsigned)conv_persistent_grid(blocks, 2));
-        if (conv_fast_epilogue(p)) {
-            if (dtype == AFCM_F16) hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 96, false, true>), g96, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 96, false, true>), g96, dim3(256), 0, st, p);
-        } else if (dtype == AFCM_F16) hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 96>), g96, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 96>), g96, dim3(256), 0, st, p);
-        return hip_status(hipGetLastError());
+        return dtype == AFCM_F16 ? launch_fwd16x<f16_t, 96, false>(p, g96, st) : launch_fwd16x<bf16_t, 96, false>(p, g96, st);
     }
     if (dtype != AFCM_F32 && ks == 3 && rows_pad % 128 == 64 && rows_pad > 128) {
         const int big = rows_pad / 128;
@@ -3213,55 +1601,6 @@ extern "C" int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const
         case AFCM_F16: return small ? launch_conv<f16_t, 64>(p, ks, st) : launch_conv<f16_t, 128>(p, ks, st);
         default: return small ? launch_conv<bf16_t, 64>(p, ks, st) : launch_conv<bf16_t, 128>(p, ks, st);
     }
-}
-
-
-extern "C" int afcm_split16(void* parts, const float* x, const float* scale, const uint32_t* bound, int32_t dtype, int64_t planes, int32_t hw,
-                            int32_t nparts, int64_t part_stride, void* stream) {
-    AFCM_REQUIRE(parts != nullptr && x != nullptr && planes > 0 && hw > 0, "split16: empty input");
-    AFCM_REQUIRE(dtype == AFCM_BF16 || dtype == AFCM_F16, "split16: parts are bfloat16 or float16");
-    AFCM_REQUIRE(nparts == 2 || nparts == 3, "split16: 2 or 3 parts (got %d)", nparts);
-    AFCM_REQUIRE(part_stride >= planes * (long long)hw && part_stride % 4 == 0, "split16: part stride %lld must cover the tensor and be a multiple of 4", (long long)part_stride);
-    AFCM_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)parts & 7) == 0, "split16: x must be 16-byte, parts 8-byte aligned");
-    long long blocks = (planes * ((hw + 3) >> 2) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    dim3 grid((unsigned)blocks), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define AFCM_SPLIT(T, K) hipLaunchKernelGGL((split16_kernel<T, K>), grid, block, 0, st, (T*)parts, x, scale, (const unsigned*)bound, (long long)planes, hw, (long long)part_stride)
-    if (dtype == AFCM_BF16) { if (nparts == 2) AFCM_SPLIT(bf16_t, 2); else AFCM_SPLIT(bf16_t, 3); }
-    else { if (nparts == 2) AFCM_SPLIT(f16_t, 2); else AFCM_SPLIT(f16_t, 3); }
-#undef AFCM_SPLIT
-    return hip_status(hipGetLastError());
-}
-
-extern "C" int afcm_amax_bits(uint32_t* out, const float* x, int64_t planes, int32_t hw, const float* scale, void* stream) {
-    AFCM_REQUIRE(out != nullptr && x != nullptr && planes > 0 && hw > 0, "amax_bits: empty input");
-    AFCM_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)x & 3) == 0, "amax_bits: misaligned pointer");
-    long long blocks = (planes * hw / 16 + 255) / 256;          // >= 4 16-byte groups per lane
-    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-    hipLaunchKernelGGL(amax_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (unsigned*)out, x, (long long)planes, hw, scale);
-    return hip_status(hipGetLastError());
-}
-
-extern "C" int afcm_plane_dot_parts(float* out, const void* parts, int64_t part_stride, int32_t nparts, const float* b, int32_t dtype, int64_t planes,
-                                    int32_t hw, const uint32_t* bound, void* stream) {
-    AFCM_REQUIRE(out != nullptr && parts != nullptr && b != nullptr && planes > 0 && hw > 0, "plane_dot_parts: empty input");
-    AFCM_REQUIRE(dtype == AFCM_BF16 || dtype == AFCM_F16, "plane_dot_parts: parts are bfloat16 or float16");
-    AFCM_REQUIRE(nparts >= 1 && nparts <= 3 && part_stride >= planes * (long long)hw, "plane_dot_parts: 1..3 parts, a stride covering the tensor");
-    AFCM_REQUIRE(planes < (1ll << 31), "plane_dot_parts: too many planes");
-    AFCM_REQUIRE(((uintptr_t)parts & 7) == 0 && ((uintptr_t)b & 15) == 0, "plane_dot_parts: parts must be 8-byte, b 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == AFCM_BF16) hipLaunchKernelGGL((plane_dot_parts_kernel<bf16_t>), dim3((unsigned)planes), dim3(256), 0, st, out, (const bf16_t*)parts, (long long)part_stride, nparts, b, (long long)planes, hw, (const unsigned*)bound);
-    else hipLaunchKernelGGL((plane_dot_parts_kernel<f16_t>), dim3((unsigned)planes), dim3(256), 0, st, out, (const f16_t*)parts, (long long)part_stride, nparts, b, (long long)planes, hw, (const unsigned*)bound);
-    return hip_status(hipGetLastError());
-}
-
-extern "C" int afcm_unscale(float* t, int64_t numel, const uint32_t* bound_a, const uint32_t* bound_b, void* stream) {
-    AFCM_REQUIRE(t != nullptr && numel > 0, "unscale: empty input");
-    long long blocks = (numel + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(unscale_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, t, (long long)numel, (const unsigned*)bound_a, (const unsigned*)bound_b);
-    return hip_status(hipGetLastError());
 }
 
 extern "C" int afcm_conv2d_pack_split(void* dst, const float* w, const uint32_t* bound, int32_t dtype, int32_t cout, int32_t cin, int32_t mode,
@@ -3300,19 +1639,12 @@ extern "C" int afcm_conv2d_split(float* y, const void* x_parts, const void* wpac
     AFCM_REQUIRE(max_part <= 2, "conv2d_split: parts 0..2");
     AFCM_REQUIRE(part_stride >= (long long)n * cin * h * w && (long long)max_part * part_stride * 2 < (1ll << 31) - (long long)cin * h * w * 2,
                  "conv2d_split: part stride %lld out of range", (long long)part_stride);
-    ConvParams p;
-    p.x = x_parts; p.y = y; p.wp = wpacked; p.oscale = oscale; p.obias = obias;
-    p.N = n; p.Cin = cin; p.Cout = cout; p.H = h; p.W = w;
-    p.P = h + 2 * pad - ks + 1; p.Q = w + 2 * pad - ks + 1;
-    AFCM_REQUIRE(p.P >= 1 && p.Q >= 1, "output must be at least 1x1");
-    p.pad = pad;
-    p.ldx = w; p.ldy = p.Q;
-    choose_tile(p.P, p.Q, ks, &p.TH, &p.TW, &p.PWL, kPatchMaxX16);
-    p.tilesX = cdiv(p.Q, p.TW); p.tilesY = cdiv(p.P, p.TH);
-    p.magicTW = (unsigned)((0x100000000ull + (unsigned)p.TW - 1) / (unsigned)p.TW);
-    p.magicTX = magic_u32((unsigned)p.tilesX); p.magicTY = magic_u32((unsigned)p.tilesY); p.magicN = magic_u32((unsigned)p.N); p.magicPC = magic_u32((unsigned)(p.PWL >> 2));
-    p.Opad = rows_pad;
-    p.nkc_real = cdiv(cin, conv_bk(dtype, 3));
+    const int P = h + 2 * pad - ks + 1, Q = w + 2 * pad - ks + 1;
+    AFCM_REQUIRE(P >= 1 && Q >= 1, "output must be at least 1x1");
+    int TH, TW, PWL;
+    choose_tile(P, Q, ks, &TH, &TW, &PWL, kPatchMaxX16);
+    const int nkc_real = cdiv(cin, conv_bk(dtype, 3));
+    ConvParams p = conv_params(y, x_parts, wpacked, oscale, obias, n, cin, cout, h, w, P, Q, pad, w, Q, TH, TW, PWL, rows_pad, nkc_real);
     p.nkc = terms * p.nkc_real;
     p.magicNK = magic_u32((unsigned)p.nkc_real);
     p.term_parts = term_parts;
@@ -3322,247 +1654,9 @@ extern "C" int afcm_conv2d_split(float* y, const void* x_parts, const void* wpac
     const bool small = (rows_pad % 128 != 0) || cout <= 64;
     const long long blocks = (long long)p.tilesX * p.tilesY * p.N * cdiv(p.Cout, small ? 64 : 128);
     AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d_split: grid of %lld blocks is out of range", blocks);
-    const dim3 block(256);
     hipStream_t st = (hipStream_t)stream;
-    p.total_blocks = (int)blocks; p.o_base = 0;
+    p.total_blocks = (int)blocks;
     const dim3 pgrid(small ? (unsigned)conv_persistent_grid(blocks, 3) : (unsigned)blocks);
-    if (dtype == AFCM_BF16) {
-        if (small) hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 64, true>), pgrid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv2d_fwd16x_kernel<bf16_t, 128, true>), pgrid, block, 0, st, p);
-    } else {
-        if (small) hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 64, true>), pgrid, block, 0, st, p);
-        else hipLaunchKernelGGL((conv2d_fwd16x_kernel<f16_t, 128, true>), pgrid, block, 0, st, p);
-    }
-    return hip_status(hipGetLastError());
-}
-
-// Split count for the weight gradient: enough workgroups to fill the chip, bounded by the K macro-steps.
-static int wgrad_rows_per_step(int dtype) { return dtype == AFCM_F32 ? 1 : 2; }
-
-// Workgroups per 64 x 64 tile.  One workgroup per CU is resident (LDS ring), so aim for ONE full round of the 256 CUs and never one
-// workgroup more: rounding up (258 workgroups = two rounds) halves the throughput, and every extra split costs a 36 x 64 x 64 x 4 B
-// partial tile written and read back (at 768 workgroups the partials of a 64 -> 64 layer were 2/3 of its time).
-// Every tile gets the same count.  (Tiles whose last 32 rows or columns lie outside the matrix skip those quadrants: 3-6 % on the
-// 91-channel layers, L11 0.33 -> 0.31 ms.  A two-class plan that gave them 0.6 of a full tile's workgroups on top made those layers
-// SLOWER, L11 0.31 -> 0.36: a lone wave per SIMD cannot hide its own LDS latency, a step costs a partial tile nearer 0.8 than 0.6 of a
-// full one -- profiles/r05_wgrad_partial_tiles.txt.  The kernel and the reduce kernels keep the two-class machinery, WgradParams::fo /
-// fi / splits_p.)
-static int wgrad_splits(int n, int cout, int cin, int p_rows) {
-    const int tiles = cdiv(cout, 64) * cdiv(cin, 64);
-    const long long ksteps = (long long)n * p_rows;   // upper bound on the macro-steps of any dtype
-    int s = 256 / tiles;
-    if (s > ksteps) s = (int)ksteps;
-    return s < 1 ? 1 : s;
-}
-
-extern "C" int afcm_conv2d_wgrad_splits(int32_t n, int32_t cout, int32_t cin, int32_t p_rows) {
-    return wgrad_splits(n, cout, cin, p_rows);   // slabs of the workspace: the most any tile writes
-}
-
-extern "C" int afcm_conv2d_wgrad(float* dw, float* workspace, const void* dy, const void* x, int32_t dtype, int32_t n, int32_t cin,
-                                 int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, void* stream) {
-    return afcm_conv2d_wgrad_ld(dw, workspace, dy, x, dtype, n, cin, cout, h, w, ks, pad, 0, 0, stream);
-}
-
-static int wgrad_impl(float* dw, float* workspace, const void* dy, const void* x, int32_t dtype, int32_t n, int32_t cin,
-                      int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t dy_pitch, int32_t x_pitch, float* dots, const float* wref, void* stream) {
-    AFCM_REQUIRE(dw != nullptr && workspace != nullptr && dy != nullptr && x != nullptr, "conv2d_wgrad: null pointer");
-    AFCM_REQUIRE(dtype == AFCM_F32 || dtype == AFCM_F16 || dtype == AFCM_BF16, "x must be float32, float16 or bfloat16");
-    AFCM_REQUIRE(ks == 1 || ks == 3, "only 1x1 and 3x3 kernels are supported");
-    AFCM_REQUIRE(pad >= 0 && pad <= ks - 1, "padding must be in [0, k-1]");
-    WgradParams p;
-    p.dy = dy; p.x = x; p.part = workspace;
-    p.N = n; p.O = cout; p.I = cin; p.H = h; p.W = w; p.pad = pad;
-    p.P = h + 2 * pad - ks + 1; p.Q = w + 2 * pad - ks + 1;
-    AFCM_REQUIRE(p.P >= 1 && p.Q >= 1, "output must be at least 1x1");
-    AFCM_REQUIRE(dtype == AFCM_F32 || (w % 2 == 0 && p.Q % 2 == 0), "16-bit conv2d_wgrad needs even widths (got %d, %d)", w, p.Q);
-    p.lddy = dy_pitch ? dy_pitch : p.Q; p.ldx = x_pitch ? x_pitch : w;
-    const bool pitched = p.lddy != p.Q || p.ldx != w;
-    AFCM_REQUIRE(!pitched || (p.lddy >= p.Q && p.ldx >= w && ((p.lddy | p.ldx) & 1) == 0), "conv2d_wgrad: row pitches %d / %d must be even and cover the widths %d / %d", p.lddy, p.ldx, p.Q, w);
-    const int R = wgrad_rows_per_step(dtype);
-    p.qchunks = cdiv(p.Q, kWgKQ);
-    p.rowgroups = cdiv(p.P, R);
-    const long long ksteps = (long long)n * p.rowgroups * p.qchunks;
-    const bool granule = (ks == 3 && pad == 2) || (ks == 1 && pad == 0);     // 16-byte LDS-DMA pieces; other paddings: 4-byte pieces
-    p.fo = cdiv(cout, 64); p.fi = cdiv(cin, 64);                             // one tile class: every tile is full
-    p.splits = p.splits_p = wgrad_splits(n, cout, cin, p.P);
-    if (p.splits > ksteps) p.splits = (int)ksteps;
-    if (p.splits_p > ksteps) p.splits_p = (int)ksteps;
-    p.steps_per_split = (int)((ksteps + p.splits - 1) / p.splits);
-    p.steps_per_split_p = (int)((ksteps + p.splits_p - 1) / p.splits_p);
-    p.splits_img = 0;
-    if (dots != nullptr) {
-        // image-aligned shares: the same number of workgroups, each inside one image (the granule kernel, a split count that is a
-        // multiple of the batch, at most 64 images: what wgrad_reduce_dots_kernel covers) -- else the caller takes its dot products
-        // from the tensors themselves
-        if (!(dtype != AFCM_F32 && granule) || n > 64 || p.splits % n != 0 || p.splits / n < 1) return AFCM_E_NOKERNEL;
-        AFCM_REQUIRE(wref != nullptr, "conv2d_wgrad_dots: the weight tensor the dot products are taken with is missing");
-        p.splits_img = p.splits / n;
-        const long long per_img = (long long)p.rowgroups * p.qchunks;
-        p.steps_per_split = p.steps_per_split_p = (int)((per_img + p.splits_img - 1) / p.splits_img);
-    }
-    const long long n_full = (long long)p.fo * p.fi;
-    const long long blocks = n_full * p.splits + ((long long)cdiv(cout, 64) * cdiv(cin, 64) - n_full) * p.splits_p;
-    dim3 grid((unsigned)blocks), block(512);
-    hipStream_t st = (hipStream_t)stream;
-#define AFCM_WG(T, R) do { if (ks == 3 && (pad & 1) == 0) hipLaunchKernelGGL((conv2d_wgrad_kernel<T, 3, R, 0>), grid, block, 0, st, p); \
-                           else if (ks == 3) hipLaunchKernelGGL((conv2d_wgrad_kernel<T, 3, R, 1>), grid, block, 0, st, p); \
-                           else hipLaunchKernelGGL((conv2d_wgrad_kernel<T, 1, R, 0>), grid, block, 0, st, p); } while (0)
-#define AFCM_WG16(T) do { constexpr int NB = 3; \
-                           if (ks == 3 && (pad & 1) == 0) hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 3, 0, NB>), grid, block, 0, st, p); \
-                           else if (ks == 3) hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 3, 1, NB>), grid, block, 0, st, p); \
-                           else hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 1, 0, NB>), grid, block, 0, st, p); } while (0)
-#define AFCM_WG16G_(T, X) do { constexpr int NB = kWgradRing; \
-                            if (small && ks == 3) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 3, NB, true, X>), grid, block, 0, st, p); \
-                            else if (small) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 1, NB, true, X>), grid, block, 0, st, p); \
-                            else if (ks == 3) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 3, NB, false, X>), grid, block, 0, st, p); \
-                            else hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 1, NB, false, X>), grid, block, 0, st, p); } while (0)
-    // MFMA shape (template flag X16; profiles/r05_conv_shape_ab.txt): 16x16x32 holds a higher clock on the large layers (+3 .. 6 %), but its K
-    // step is 32 pixels where the 32x32x16 form skips dead 16-pixel groups: rows whose last 64-pixel chunk holds 33 .. 48 pixels (the 38-wide
-    // planes of the 36^2 layers) cost it a whole extra step (-12 % there) -- those keep the 32x32x16 form.
-    const int q_last = p.Q % 64;
-    const bool wg_x16 = !(q_last > 32 && q_last <= 48);
-#define AFCM_WG16G(T) do { if (wg_x16) AFCM_WG16G_(T, true); else AFCM_WG16G_(T, false); } while (0)
-    // tensors below 2 GB: one descriptor per tensor; larger ones: a descriptor per LDS-DMA piece (the general form)
-    const bool small = (long long)n * cout * p.P * p.lddy * 2 < (1ll << 31) - 65536 &&
-                       (long long)n * cin * h * p.ldx * 2 < (1ll << 31) - 65536;
-    // rows by pitch: the 16-byte LDS-DMA kernel only (a granule straddling x's right edge is zeroed in LDS whatever follows it)
-    AFCM_REQUIRE(!pitched || (dtype != AFCM_F32 && granule), "conv2d_wgrad: row pitches need the 16-bit granule kernel (3x3 pad 2 or 1x1 pad 0)");
-    switch (dtype) {
-        case AFCM_F32: AFCM_WG(float, 1); break;
-        case AFCM_F16: if (granule) AFCM_WG16G(f16_t); else AFCM_WG16(f16_t); break;
-        default: if (granule) AFCM_WG16G(bf16_t); else AFCM_WG16(bf16_t); break;
-    }
-#undef AFCM_WG16G
-#undef AFCM_WG16G_
-#undef AFCM_WG16
-#undef AFCM_WG
-    int rc = hip_status(hipGetLastError());
-    if (rc != AFCM_OK) return rc;
-    const long long numel = (long long)cout * cin * ks * ks;
-    if (p.splits_img > 0) {
-        const dim3 rgrid((unsigned)cin), rblock(1024);
-#define AFCM_RD(T) do { if (ks == 3) hipLaunchKernelGGL((wgrad_reduce_dots_kernel<T, 9>), rgrid, rblock, 0, st, dw, dots, (const float*)workspace, wref, n, cout, cin, p.splits_img); \
-                        else hipLaunchKernelGGL((wgrad_reduce_dots_kernel<T, 1>), rgrid, rblock, 0, st, dw, dots, (const float*)workspace, wref, n, cout, cin, p.splits_img); } while (0)
-        if (dtype == AFCM_F16) AFCM_RD(f16_t); else AFCM_RD(bf16_t);
-#undef AFCM_RD
-        return hip_status(hipGetLastError());
-    }
-    const WgradSlabs slabs{cin, ks * ks, p.fo, p.fi, p.splits, p.splits_p};
-    long long rb = (numel + 255) / 256;
-    if (rb > 2048) rb = 2048;
-    // splits beyond the last populated one were never launched with work: they still wrote zeros (acc = 0)
-    if ((numel & 3) == 0 && (((uintptr_t)dw | (uintptr_t)workspace) & 15) == 0) {
-        const long long n4 = numel / 4;
-        if (p.splits >= 64) hipLaunchKernelGGL(wgrad_reduce4_kernel<16>, dim3((unsigned)cdiv(n4, 16)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
-        else if (p.splits >= 8) hipLaunchKernelGGL(wgrad_reduce4_kernel<64>, dim3((unsigned)cdiv(n4, 64)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
-        else hipLaunchKernelGGL(wgrad_reduce4_kernel<256>, dim3((unsigned)cdiv(n4, 256)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
-    } else {
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, dw, (const float*)workspace, numel, slabs);
-    }
-    return hip_status(hipGetLastError());
-}
-
-extern "C" int afcm_conv2d_wgrad_ld(float* dw, float* workspace, const void* dy, const void* x, int32_t dtype, int32_t n, int32_t cin,
-                                    int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t dy_pitch, int32_t x_pitch, void* stream) {
-    return wgrad_impl(dw, workspace, dy, x, dtype, n, cin, cout, h, w, ks, pad, dy_pitch, x_pitch, nullptr, nullptr, stream);
-}
-
-extern "C" int afcm_conv2d_wgrad_dots_ld(float* dw, float* dots, float* workspace, const void* dy, const void* x, const float* wref, int32_t dtype,
-                                         int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t dy_pitch,
-                                         int32_t x_pitch, void* stream) {
-    AFCM_REQUIRE(dots != nullptr, "conv2d_wgrad_dots: dots must be non-null");
-    return wgrad_impl(dw, workspace, dy, x, dtype, n, cin, cout, h, w, ks, pad, dy_pitch, x_pitch, dots, wref, stream);
-}
-
-extern "C" int afcm_scale_planes(void* y, const void* x, const float* scale, int32_t dtype_in, int32_t dtype_out, int64_t planes,
-                                 int32_t hw, void* stream) {
-    AFCM_REQUIRE(y != nullptr && x != nullptr && planes > 0 && hw > 0, "scale_planes: empty input");
-    long long blocks = (planes * ((hw + 3) >> 2) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    dim3 grid((unsigned)blocks), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define AFCM_SP(TI, TO) hipLaunchKernelGGL((scale_planes_kernel<TI, TO>), grid, block, 0, st, (TO*)y, (const TI*)x, scale, (long long)planes, hw)
-    if (dtype_in == AFCM_F32 && dtype_out == AFCM_F32) AFCM_SP(float, float);
-    else if (dtype_in == AFCM_F32 && dtype_out == AFCM_BF16) AFCM_SP(float, bf16_t);
-    else if (dtype_in == AFCM_F32 && dtype_out == AFCM_F16) AFCM_SP(float, f16_t);
-    else if (dtype_in == AFCM_BF16 && dtype_out == AFCM_BF16) AFCM_SP(bf16_t, bf16_t);
-    else if (dtype_in == AFCM_F16 && dtype_out == AFCM_F16) AFCM_SP(f16_t, f16_t);
-    else if (dtype_in == AFCM_BF16 && dtype_out == AFCM_F32) AFCM_SP(bf16_t, float);
-    else if (dtype_in == AFCM_F16 && dtype_out == AFCM_F32) AFCM_SP(f16_t, float);
-    else { set_error("scale_planes: unsupported dtype pair %d -> %d", dtype_in, dtype_out); return AFCM_E_INVALID; }
-#undef AFCM_SP
-    return hip_status(hipGetLastError());
-}
-
-extern "C" int afcm_axpy_planes(void* y, const void* a, const void* b, const float* scale, int32_t dtype, int64_t planes, int32_t hw, void* stream) {
-    AFCM_REQUIRE(y != nullptr && a != nullptr && b != nullptr && planes > 0 && hw > 0, "axpy_planes: empty input");
-    AFCM_REQUIRE(dtype == AFCM_F16 || dtype == AFCM_BF16, "axpy_planes: 16-bit tensors only");
-    if ((hw & 7) != 0 || ((((uintptr_t)y | (uintptr_t)a | (uintptr_t)b)) & 15) != 0) return AFCM_E_NOKERNEL;
-    const int per = hw >> 3;
-    // grid.y = planes (one scale per workgroup), grid.x = 1 KB-per-thread-block slices of a plane: >= 4 vectors per thread on the large planes
-    const dim3 grid((unsigned)((per + 1023) / 1024), (unsigned)(planes < 65535 ? planes : 65535));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == AFCM_BF16) hipLaunchKernelGGL((axpy_planes_kernel<bf16_t>), grid, dim3(256), 0, st, (bf16_t*)y, (const bf16_t*)a, (const bf16_t*)b, scale, (long long)planes, hw);
-    else hipLaunchKernelGGL((axpy_planes_kernel<f16_t>), grid, dim3(256), 0, st, (f16_t*)y, (const f16_t*)a, (const f16_t*)b, scale, (long long)planes, hw);
-    return hip_status(hipGetLastError());
-}
-
-extern "C" int afcm_plane_dot(float* out, const void* a, const void* b, int32_t dtype, int64_t planes, int32_t hw, void* stream) {
-    AFCM_REQUIRE(out != nullptr && a != nullptr && planes > 0 && hw > 0, "plane_dot: empty input");
-    AFCM_REQUIRE(planes < (1ll << 31), "plane_dot: too many planes");
-    AFCM_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 15) == 0, "plane_dot: operands must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int esize = dtype == AFCM_F32 ? 4 : 2;
-    const bool per_wave = (long long)hw * esize <= 16384;
-    dim3 grid((unsigned)(per_wave ? (planes + 3) / 4 : planes)), block(256);
-#define AFCM_PD(T) do { \
-        if (per_wave) hipLaunchKernelGGL((plane_dot_wave_kernel<T>), grid, block, 0, st, out, (const T*)a, (const T*)b, (long long)planes, hw); \
-        else hipLaunchKernelGGL((plane_dot_kernel<T>), grid, block, 0, st, out, (const T*)a, (const T*)b, (long long)planes, hw); } while (0)
-    switch (dtype) {
-        case AFCM_F32: AFCM_PD(float); break;
-        case AFCM_F16: AFCM_PD(f16_t); break;
-        case AFCM_BF16: AFCM_PD(bf16_t); break;
-        default: set_error("plane_dot: bad dtype"); return AFCM_E_INVALID;
-    }
-#undef AFCM_PD
-    return hip_status(hipGetLastError());
-}
-
-static int plane_dot_rows(float* out, const void* a, const void* b, int32_t dtype, int64_t planes, int32_t h, int32_t w,
-                          int32_t a_pitch, int32_t b_pitch, const PlaneGate& gate, void* stream) {
-    AFCM_REQUIRE(out != nullptr && a != nullptr && planes > 0 && h > 0 && w > 0, "plane_dot: empty input");
-    AFCM_REQUIRE(planes < (1ll << 31), "plane_dot: too many planes");
-    const int esize = dtype == AFCM_F32 ? 4 : 2;
-    const int lda = a_pitch ? a_pitch : w, ldb = b_pitch ? b_pitch : w;
-    AFCM_REQUIRE(lda >= w && ldb >= w, "plane_dot: row pitches %d / %d are below the width %d", lda, ldb, w);
-    AFCM_REQUIRE(w >= 16 / esize, "plane_dot: rows of %d elements are shorter than one 16-byte vector", w);
-    AFCM_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3) == 0 && (esize == 4 || ((w | lda | ldb) & 1) == 0), "plane_dot: rows must start on 4-byte boundaries");
-    AFCM_REQUIRE((long long)h * (lda > ldb ? lda : ldb) < (1ll << 31) / 16, "plane_dot: plane is out of range");
-    hipStream_t st = (hipStream_t)stream;
-    const bool per_wave = (long long)h * w * esize <= 16384;
-    dim3 grid((unsigned)(per_wave ? (planes + 3) / 4 : planes)), block(256);
-#define AFCM_PDR(T) do { \
-        if (per_wave) hipLaunchKernelGGL((plane_dot_rows_kernel<T, true>), grid, block, 0, st, out, (const T*)a, (const T*)b, (long long)planes, h, w, lda, ldb, gate); \
-        else hipLaunchKernelGGL((plane_dot_rows_kernel<T, false>), grid, block, 0, st, out, (const T*)a, (const T*)b, (long long)planes, h, w, lda, ldb, gate); } while (0)
-    switch (dtype) {
-        case AFCM_F32: AFCM_PDR(float); break;
-        case AFCM_F16: AFCM_PDR(f16_t); break;
-        case AFCM_BF16: AFCM_PDR(bf16_t); break;
-        default: set_error("plane_dot: bad dtype"); return AFCM_E_INVALID;
-    }
-#undef AFCM_PDR
-    return hip_status(hipGetLastError());
-}
-
-extern "C" int afcm_plane_dot_ld(float* out, const void* a, const void* b, int32_t dtype, int64_t planes, int32_t h, int32_t w,
-                                 int32_t a_pitch, int32_t b_pitch, void* stream) {
-    return plane_dot_rows(out, a, b, dtype, planes, h, w, a_pitch, b_pitch, PlaneGate{nullptr, 0, nullptr, nullptr, nullptr, nullptr}, stream);
-}
-
-extern "C" int afcm_plane_dot_gated_ld(float* out, const void* a, const void* b, int32_t dtype, int64_t planes, int32_t h, int32_t w,
-                                       int32_t a_pitch, int32_t b_pitch, const int32_t* flags, int32_t slots, const float* out_scale,
-                                       const float* gz, const float* next_scale, const float* gskip, void* stream) {
-    AFCM_REQUIRE(flags != nullptr && slots > 0 && out_scale != nullptr && gz != nullptr && b != nullptr, "plane_dot_gated: null pointer");
-    return plane_dot_rows(out, a, b, dtype, planes, h, w, a_pitch, b_pitch, PlaneGate{flags, slots, out_scale, gz, next_scale, gskip}, stream);
+    if (dtype == AFCM_BF16) return small ? launch_fwd16x<bf16_t, 64, true>(p, pgrid, st) : launch_fwd16x<bf16_t, 128, true>(p, pgrid, st);
+    return small ? launch_fwd16x<f16_t, 64, true>(p, pgrid, st) : launch_fwd16x<f16_t, 128, true>(p, pgrid, st);
 }

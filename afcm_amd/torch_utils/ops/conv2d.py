@@ -1,5 +1,5 @@
 """Dense stride-1 convolution with per-plane input/output scaling on the MFMA kernels of
-afcm_amd/csrc/conv2d.hip -- the compute behind ``modulated_conv2d`` (NET:25-64) and the encoder's
+afcm_amd/csrc/conv2d*.hip -- the compute behind ``modulated_conv2d`` (NET:25-64) and the encoder's
 ``conv2d_gradfix.conv2d`` call (NET:505).
 
     y[n, o] = out_scale[n, o] * sum_{i, r, s} w[o, i, r, s] * (in_scale[n, i] * x[n, i, p + r - pad, q + s - pad])
@@ -420,7 +420,7 @@ def _wgrad_raw(dy, x, cout, cin, ks, pad, work_share=1.0, dots_with=None):
     ws = torch.empty([splits, cout, cin, ks, ks], dtype=torch.float32, device=x.device)
     span = profiling.span('conv2d_wgrad', work)
     dots = None
-    if dots_with is not None and WGRAD_DOTS and x.dtype in (torch.bfloat16, torch.float16):
+    if dots_with is not None and x.dtype in (torch.bfloat16, torch.float16):
         wref = dots_with.detach().to(torch.float32).contiguous()
         dots = torch.empty([n, cin], dtype=torch.float32, device=x.device)
         rc = _lib.check(lib.afcm_conv2d_wgrad_dots_ld(dw.data_ptr(), dots.data_ptr(), ws.data_ptr(), dy.data_ptr(), x.data_ptr(), wref.data_ptr(),
@@ -434,10 +434,6 @@ def _wgrad_raw(dy, x, cout, cin, ks, pad, work_share=1.0, dots_with=None):
     if span is not None:
         span.end()
     return dw if dots_with is None else (dw, dots)
-
-
-# the per-plane dot products <x, dx> from the weight gradient's per-image slabs where the split plan allows (module switch: tests compare)
-WGRAD_DOTS = True
 
 
 class _ScaledConv2d(torch.autograd.Function):
@@ -590,7 +586,6 @@ class _ConvWgrad(torch.autograd.Function):
         return g_dy, g_x, None, None
 
 
-ZERO_STUFF_UPFIRDN = True      # module switch (A/B): the stride-2 backward's zero-stuffed dy through upfirdn2d(up=2, one tap)
 _ONE_TAP = {}
 
 
@@ -641,7 +636,7 @@ class _StridedConv2d(torch.autograd.Function):
         pad = ctx.padding
         n, _, h, wd = x.shape
         fh, fw = h + 2 * pad - 2, wd + 2 * pad - 2
-        if ZERO_STUFF_UPFIRDN and fw % 2 == 0 and dy.shape[3] % 2 == 0:
+        if fw % 2 == 0 and dy.shape[3] % 2 == 0:
             # zero-stuffed dy = the gradient of the stride-1 result: upfirdn2d with up 2 and a one-tap filter writes it in ONE pass (row
             # kernel: 16-byte stores), differentiable like the slice assignment it replaces (a fill + a strided copy: two passes)
             from . import upfirdn2d as _upf
