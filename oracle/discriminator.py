@@ -23,7 +23,17 @@ def setup_filter(f):
     return f / f.sum()
 
 
-def conv2d_resample(x, w, f=None, down=1, padding=0, up=1, flip_weight=True):
+def _stored(lowp, x):
+    """A tensor the product stores: rounded where ``lowp`` (see ``discriminator``) says so, untouched in the fp32 network."""
+    return x if lowp is None else lowp.store(x)
+
+
+def _cast(lowp, x):
+    """The ``.to(dtype)`` at a 16-bit block's entry (``lowp.cast``: the value rounded in both references)."""
+    return x if lowp is None else lowp.cast(x)
+
+
+def conv2d_resample(x, w, f=None, down=1, padding=0, up=1, flip_weight=True, lowp=None):
     """conv2d_resample.py:57-155.  Down only: the branches the discriminator takes (1x1: decimate then convolve; 3x3: blur then strided
     conv).  With up > 1: the DEFINITION the reference states as its generic path (:151-155) -- zero-insert upsampling through the
     low-pass filter (gain up^2), the convolution (true convolution when flip_weight is False, as Conv2dLayer asks for up > 1,
@@ -51,23 +61,39 @@ def conv2d_resample(x, w, f=None, down=1, padding=0, up=1, flip_weight=True):
         py0 += (fw - down + 1) // 2
         py1 += (fw - down) // 2
     if kw == 1 and kh == 1 and down > 1:                      # :118-122  downsample first, then 1x1
-        x = ops.upfirdn2d(x, f, down=down, padding=[px0, px1, py0, py1])
-        return F.conv2d(x, w)
+        x = _stored(lowp, ops.upfirdn2d(x, f, down=down, padding=[px0, px1, py0, py1]))
+        return _stored(lowp, F.conv2d(x, w))
     if down > 1:                                              # :130-134  blur, then strided conv
-        x = ops.upfirdn2d(x, f, padding=[px0, px1, py0, py1])
-        return F.conv2d(x, w, stride=down)
+        x = _stored(lowp, ops.upfirdn2d(x, f, padding=[px0, px1, py0, py1]))
+        return _stored(lowp, F.conv2d(x, w, stride=down))
     assert px0 == px1 == py0 == py1 and px0 >= 0              # :151-153
-    return F.conv2d(x, w, padding=px0)
+    return _stored(lowp, F.conv2d(x, w, padding=px0))
 
 
-def conv2d_layer(sd, prefix, x, kernel_size, act='linear', down=1, gain=1.0, conv_clamp=None, filt=None, up=1):
+def conv2d_layer(sd, prefix, x, kernel_size, act='linear', down=1, gain=1.0, conv_clamp=None, filt=None, up=1, lowp=None, trace=None):
+    """``lowp`` (down-sampling and plain layers only): the layer as a 16-bit block runs it -- see ``discriminator``."""
     w = sd[prefix + 'weight']
-    w = w * (1.0 / np.sqrt(w.shape[1] * kernel_size ** 2))                    # layers.py:137,154
+    weight_gain = 1.0 / np.sqrt(w.shape[1] * kernel_size ** 2)                # layers.py:137,154
     b = sd.get(prefix + 'bias')
-    x = conv2d_resample(x, w, f=filt, down=down, padding=kernel_size // 2, up=up, flip_weight=(up == 1))
+    if lowp is None:
+        w = w * weight_gain
+    else:
+        assert up == 1
+        w = lowp.weight(w, weight_gain)
+        b = lowp.bias(b) if b is not None else None
+    x = conv2d_resample(x, w, f=filt, down=down, padding=kernel_size // 2, up=up, flip_weight=(up == 1), lowp=lowp)
     act_gain = ops.ACTIVATIONS[act][2] * gain
     act_clamp = conv_clamp * gain if conv_clamp is not None else None
-    return ops.bias_act(x, b, act=act, gain=act_gain, clamp=act_clamp)
+    if lowp is not None and b is not None:
+        # bias_act adds the bias in fp32 (x + b is never stored) and stores its dx, which the bias gradient then sums
+        x, b = lowp.grad(x + b.reshape(1, -1, 1, 1)), None
+    y = ops.bias_act(x, b, act=act, gain=act_gain, clamp=act_clamp)
+    # the product skips the bias_act launch (and its rounding) only for a linear layer with unit gain, no clamp and no bias
+    y = y if (act == 'linear' and act_gain == 1 and act_clamp is None and b is None) else _stored(lowp, y)
+    trace = getattr(lowp, 'trace', None) if trace is None else trace
+    if trace is not None:
+        trace[prefix] = y.detach()                                             # tests compare branch decisions at each activation
+    return y
 
 
 def fully_connected(sd, prefix, x, act='linear', lr_multiplier=1.0):
@@ -104,22 +130,38 @@ def label_mapping(sd, c, num_layers=8, lr_multiplier=0.01):
     return x
 
 
-def discriminator(sd, img, img_resolution, mbstd_group_size=4, conv_clamp=None, c=None):
+def discriminator_block(sd, p, x, img, conv_clamp=None, filt=None, lowp=None, trace=None):
+    """DiscriminatorBlock.forward, architecture 'resnet' (generator.py:661-692): ``x`` None for the first block, which takes ``img``.
+    ``lowp``: the block runs in 16 bit -- its input is cast, every tensor it stores is rounded (``lowp.store``), and each of the two
+    consumers of the trunk's input gets its own rounding of the gradient it sends back (autograd sums 16-bit gradients in 16 bit)."""
+    filt = setup_filter([1, 3, 3, 1]) if filt is None else filt
+    if x is None:
+        x = conv2d_layer(sd, p + 'fromrgb.', _cast(lowp, img), 1, act='lrelu', conv_clamp=conv_clamp, lowp=lowp, trace=trace)
+    else:
+        x = _cast(lowp, x)
+    y = conv2d_layer(sd, p + 'skip.', _stored(lowp, x), 1, down=2, gain=np.sqrt(0.5), filt=filt, lowp=lowp, trace=trace)
+    x = conv2d_layer(sd, p + 'conv0.', _stored(lowp, x), 3, act='lrelu', conv_clamp=conv_clamp, lowp=lowp, trace=trace)
+    x = conv2d_layer(sd, p + 'conv1.', x, 3, act='lrelu', down=2, gain=np.sqrt(0.5), conv_clamp=conv_clamp, filt=filt, lowp=lowp, trace=trace)
+    return _stored(lowp, y + x)
+
+
+def discriminator(sd, img, img_resolution, mbstd_group_size=4, conv_clamp=None, c=None, lowp=None, num_fp16_res=0):
     """CoModDiscriminator.forward(img, c), architecture 'resnet', fp32; ``c`` given (and a ``mapping.*`` branch in the state dict):
-    the conditional form -- the epilogue's cmap_dim outputs projected onto the mapped label (generator.py:771-773)."""
+    the conditional form -- the epilogue's cmap_dim outputs projected onto the mapped label (generator.py:771-773).
+
+    ``lowp`` with ``num_fp16_res`` > 0 (test infrastructure, tests/disc16_ref.py): the ``num_fp16_res`` highest-resolution blocks as
+    the product runs them in 16 bit (generator.py:808,819).  ``lowp.weight(w, gain)`` / ``lowp.bias(b)`` / ``lowp.cast(x)`` give the operands
+    those blocks multiply (rounded to the 16-bit type), ``lowp.store(t)`` stands wherever the product stores a 16-bit tensor (``lowp.grad(t)``: where it
+    stores only t's gradient): the identity for the plain reference, a rounding node for the one that emulates the storage.  Without it nothing changes."""
     filt = setup_filter([1, 3, 3, 1])
     log2 = int(np.log2(img_resolution))
+    fp16_resolution = max(2 ** (log2 + 1 - num_fp16_res), 8)
+    trace = getattr(lowp, 'trace', None)                      # every layer's output, the fp32 blocks' too
     x = None
     for res in [2 ** i for i in range(log2, 2, -1)]:
-        p = f'b{res}.'
-        if x is None:
-            x = conv2d_layer(sd, p + 'fromrgb.', img, 1, act='lrelu', conv_clamp=conv_clamp)
-        y = conv2d_layer(sd, p + 'skip.', x, 1, down=2, gain=np.sqrt(0.5), filt=filt)
-        x = conv2d_layer(sd, p + 'conv0.', x, 3, act='lrelu', conv_clamp=conv_clamp)
-        x = conv2d_layer(sd, p + 'conv1.', x, 3, act='lrelu', down=2, gain=np.sqrt(0.5), conv_clamp=conv_clamp, filt=filt)
-        x = y + x
+        x = discriminator_block(sd, f'b{res}.', x, img, conv_clamp, filt, lowp if (lowp is not None and res >= fp16_resolution) else None, trace)
     x = minibatch_std(x, mbstd_group_size)
-    x = conv2d_layer(sd, 'b4.conv.', x, 3, act='lrelu', conv_clamp=conv_clamp)
+    x = conv2d_layer(sd, 'b4.conv.', x, 3, act='lrelu', conv_clamp=conv_clamp, trace=trace)
     x = fully_connected(sd, 'b4.fc.', x.flatten(1), act='lrelu')
     x = fully_connected(sd, 'b4.out.', x)
     if 'mapping.embed.weight' in sd:

@@ -254,7 +254,18 @@ def test_full_training_iteration_runs_in_bf16():
 @pytest.mark.parametrize('dtype,tol', [(torch.float16, 2e-2), (torch.bfloat16, 8e-2)])
 def test_discriminator_16bit_blocks_track_the_fp32_reference(dtype, tol):
     """num_fp16_res (generator.py:808,819): the highest-resolution blocks in 16 bit (HIP upfirdn2d / bias_act in that dtype,
-    16-bit convs on the MFMA kernels) vs the fp32 golden logits and R1 gradient; looser bound = 16-bit rounding only."""
+    16-bit convs on the MFMA kernels) vs the fp32 golden logits and R1 gradient; looser bound = 16-bit rounding only.
+
+    The parameter gradients of the R1 term are held to the golden's ``gr1/*`` arrays, per tensor, by the two float64 references
+    of tests/disc16_ref.py (computed here, on the CPU): the kernels may be no more than twice as far from the truth as rounding
+    alone puts the reference that emulates the 16-bit storage.  "Rounding alone" against the fp32 GOLDEN includes the rounding of
+    the weights and of the image to the 16-bit type (the golden multiplies unrounded fp32 operands), which the pure reference
+    shares with the kernels; so the inequality is asserted twice, each side against its own truth:
+        relL2(kernel - golden) <= 2 relL2(emulated - golden)      and      relL2(kernel - pure) <= 2 relL2(emulated - pure).
+    (Measured, bfloat16: the first alone with E = relL2(emulated - pure) fails for the fp32 blocks' weights, b4.conv.weight
+    2.8e-2 against E = 4.5e-3, by the operand rounding and not by the kernels -- the network test of test_gpu_disc16.py holds
+    them to E / 4 of the emulated reference.)  The R1 image gradient likewise, wherever that is the smaller bar than 4 tol."""
+    import disc16_ref as R
     from afcm_amd.networks_discriminator import CoModDiscriminator
     g = load_golden('D2_tiny128_clamp')
     res, n, cb, cm, group, clamp = [int(v) for v in g['meta']]
@@ -263,13 +274,31 @@ def test_discriminator_16bit_blocks_track_the_fp32_reference(dtype, tol):
     D.load_state_dict({k[3:]: torch.from_numpy(np.array(v)) for k, v in g.items() if k.startswith('sd/')}, strict=True)
     D = D.cuda()
     assert [getattr(D, f'b{r}').use_fp16 for r in (128, 64, 32, 16, 8)] == [True, True, True, False, False]
+    assert R.NETWORK == 'D2_tiny128_clamp' and R.NETWORK_FP16_RES == 3
+    pure, emulated, _ = R.network_references(g, dtype)
     real = torch.from_numpy(g['real']).cuda().requires_grad_(True)
     logits = D(real, None)
     assert logits.dtype == torch.float32
     scale = max(1.0, float(np.abs(g['real_logits']).max()))
     assert np.abs(logits.detach().cpu().numpy() - g['real_logits']).max() <= tol * scale
     r1, = torch.autograd.grad(logits.sum(), real, create_graph=True)
-    d = r1.detach().cpu().numpy() - g['r1_grads']
-    assert np.sqrt((d ** 2).sum() / (g['r1_grads'] ** 2).sum()) <= 4 * tol
-    (r1.square().sum()).backward()
+
+    def held(name, got, golden, old_bar=None):
+        golden = torch.from_numpy(np.array(golden)).double()
+        rel_g, noise_g = R.rel_l2(got, golden), R.rel_l2(emulated[name], golden)
+        rel_p, noise_p = R.rel_l2(got, pure[name]), R.rel_l2(emulated[name], pure[name])
+        bar_g = R.GOLDEN_FACTOR * noise_g if old_bar is None else min(old_bar, R.GOLDEN_FACTOR * noise_g)
+        print(f'{name} {dtype}: vs the fp32 golden {rel_g:.3e} (emulated {noise_g:.3e}), vs the pure reference {rel_p:.3e} (emulated, E {noise_p:.3e})')
+        return [] if (rel_g <= bar_g and rel_p <= R.GOLDEN_FACTOR * noise_p) else [(name, rel_g, bar_g, rel_p, noise_p)]
+    bad = held('r1_grads', r1.detach().double().cpu(), g['r1_grads'], old_bar=4 * tol)
+    # the R1 term as the golden states it (loss_r1 = mean over the batch of |r1|^2 / 2), so that gr1/* are its gradients
+    (r1.square().sum([1, 2, 3]).mean() * 0.5).backward()
     assert all(torch.isfinite(p.grad).all() for p in D.parameters() if p.grad is not None)
+    params = dict(D.named_parameters())
+    for k in [str(k) for k in g['names']]:
+        got = torch.zeros(g['gr1/' + k].shape, dtype=torch.float64) if params[k].grad is None else params[k].grad.detach().double().cpu()
+        if float(np.abs(g['gr1/' + k]).max()) == 0.0:       # a parameter the R1 term does not reach
+            assert float(got.abs().max()) == 0.0, k
+        else:
+            bad += held('gr1/' + k, got, g['gr1/' + k])
+    assert not bad, bad
