@@ -603,84 +603,8 @@ __global__ __launch_bounds__((64 * MfmaGeom<UP, DOWN, TOW, TOH>::NG), (mfma_tile
 }
 
 // ---------------------------------------------------------------------------------------------
-template <int UP, int DOWN> struct MfmaTile;
-template <> struct MfmaTile<2, 2> { static constexpr int TOW = 64, TOH = 32; };
-template <> struct MfmaTile<2, 4> { static constexpr int TOW = 32, TOH = 32; };
-template <> struct MfmaTile<4, 2> { static constexpr int TOW = 64, TOH = 32; };
-// Tall variant for planes of 33..48 output rows (the 36^2 / 38^2 planes of the 256^2 generator): ONE 48-row tile instead of two
-// 32-row tiles that are 12 % full in their second row.  The constant fragments do not depend on the tile shape (only on up,
-// down and the filters), so both variants share one prepared workspace; the sign layout is tile-independent.
-constexpr int kTallTOH = 48;
-
-// Kernel family of a call.  The wave-autonomous kernels (filtered_lrelu_wave.hip) take every matrix-core case without a bias
-// operand; they write / read sign layout 2, the LDS-tile kernels below layout 1, so a READ call follows the layout of its tensor.
-template <typename T, int UP, int DOWN, int TOW, int TOH>
-int launch_wave_tile(const afcm_filtered_lrelu_args* a, FlreluMfmaParams p, hipStream_t st);
-template <typename T, int UP, int DOWN>
-int prepare_wave(const afcm_filtered_lrelu_args* a, int py0_frag, int dshift, hipStream_t st);
-
-constexpr int kWavePitchSlack = 128;        // elements a row pitch may exceed the plane width by (wave kernels)
-static bool wave_family(const afcm_filtered_lrelu_args* a) {
-    if (a->sign_mode == AFCM_SIGNS_READ) return a->sign_layout == 2;
-    // no bias operand; offsets + out-of-range markers stay below 2^31.  Decided on the plane sizes plus the largest pitch overhead
-    // launch_wave() accepts -- NOT on the pitches themselves: afcm_filtered_lrelu_shapes() runs before the caller has chosen them,
-    // and the sign layout / strip geometry it reports must be the one the launch uses.
-    return a->b == nullptr && (long long)a->xh * (a->xw + kWavePitchSlack) < (1ll << 28) &&
-           (long long)a->yh * (a->yw + kWavePitchSlack) < (1ll << 28);
-}
-
-// Output rows per strip of the wave kernels: 32; one 48-row strip for the 36^2 / 38^2 planes (up 2 / down 2).  (Measured and
-// dropped: 16-row strips for down 4, whose 32-row strips need 240-250 registers = two waves per SIMD: at 16 rows a strip still
-// needs 176-199 and computes 1.5x instead of 1.25x its own rows -- forward 1.63 vs 1.89 TB/s over the down-4 layers.)
-static int wave_toh(int up, int down, int rows) {
-    return (up == 2 && down == 2 && rows > 32 && rows <= kTallTOH) ? kTallTOH : 32;
-}
-
-// READ calls of the wave kernels: output rows by which the strips' origin moves up (<= 0) so that every strip's first upsampled
-// row, U0y + sy = (ty TOH + oy0) down + sy, is a multiple of 16 = a row block of the sign tensor (kSignsReadAligned in
-// filtered_lrelu_wave.hip).  Possible when sy is a multiple of gcd(down, 16) = down; costs at most 16 / down - 1 extra rows on
-// top of the plane.  Pure host arithmetic on pitch-independent arguments: shapes() and the launch agree.
-// ... and, where sy is not a multiple of `down`, the remaining dshift = (oy0 down + sy) mod 16 < down upsampled rows by which the
-// strips' upsampled grid itself starts early: the constant fragments of such a call are prepared with their rows moved by dshift
-// (the tiles have 6-12 spare rows: (TOH - 1) down + taps + dshift <= 16 NVB for every shape), so EVERY read call is aligned.
-static bool wave_read_origin(const afcm_filtered_lrelu_args* a, int* oy0, int* dshift) {
-    *oy0 = 0;
-    *dshift = 0;
-    if (a->sign_mode != AFCM_SIGNS_READ || a->sign_layout != 2) return false;
-    const int m = pos_mod(a->sy, 16);
-    *oy0 = -(m / a->down);
-    *dshift = m % a->down;
-    return true;
-}
-// rows the strips of a wave launch have to cover
-static int wave_rows(const afcm_filtered_lrelu_args* a) {
-    int oy0, dshift;
-    wave_read_origin(a, &oy0, &dshift);
-    return a->yh - oy0;
-}
-
-static bool tall_tile(int up, int down, int yh, int sign_mode, bool wave) {
-    if (wave) return wave_toh(up, down, yh) == kTallTOH;                    // (callers pass wave_rows())
-    (void)down;
-    if (up != 2) return false;
-    if (yh > 32 && yh <= kTallTOH) return true;
-    // The sign-WRITING kernels (forward) also gain on larger planes whenever 48-row tiles cover the plane with no more padded rows
-    // than 32-row tiles (276 rows: 6 x 48 = 9 x 32; 84 rows: 2 x 48 = 3 x 32): 7 % fewer halo rows, a third fewer workgroups --
-    // enc0..3 forward 0.207 / 0.277 / 0.383 -> 0.181 / 0.250 / 0.337 ms.  The sign-READING kernels lose 5-20 % on the same tiles
-    // (their staged sign window and keep-mask table scale with the tile), so the transposed op keeps 32 rows.
-    // up to 7 % more padded rows still pay (the 532- and 512-row planes of the 512^2 generator: 576 vs 544, 528 vs 512 rows --
-    // filtered_lrelu 10.0 -> 9.8 ms per step there); at 12.5 % (256 rows) the gain is gone
-    constexpr int slack = 7;                                                   // extra padded rows tolerated, in percent
-    if (sign_mode != AFCM_SIGNS_READ && 100 * cdiv(yh, kTallTOH) * kTallTOH <= (100 + slack) * cdiv(yh, 32) * 32) return true;
-    return false;
-}
-
-template <typename T, int UP, int DOWN, int TOW, int TOH, int SIGN>
-static void launch_one(const FlreluMfmaParams& p, bool bias, dim3 grid, dim3 block, hipStream_t st) {
-    if (bias) hipLaunchKernelGGL((flrelu_mfma_kernel<T, UP, DOWN, TOW, TOH, SIGN, true>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((flrelu_mfma_kernel<T, UP, DOWN, TOW, TOH, SIGN, false>), grid, block, 0, st, p);
-}
-
+// Launchers.  Which family, tile and origin a call gets is the plan's business (flrelu_plan, filtered_lrelu.hip); what stays
+// here is filling the parameters and the checks on what shapes() could not see: the row pitches.
 static int fill_params(const afcm_filtered_lrelu_args* a, FlreluMfmaParams& p, int tilesX, int tilesY) {
     p.x = a->x; p.y = a->y; p.b = a->b; p.s = a->signs; p.ws = a->workspace; p.plane_sum = a->plane_sum;
     p.oscale = a->oscale; p.oscale2 = a->oscale2; p.skip = a->skip;
@@ -705,111 +629,74 @@ static int fill_params(const afcm_filtered_lrelu_args* a, FlreluMfmaParams& p, i
 }
 
 template <typename T, int UP, int DOWN, int TOW, int TOH>
-static int launch_mfma_tile(const afcm_filtered_lrelu_args* a, hipStream_t st) {
+static int launch_mfma_tile(const afcm_filtered_lrelu_args* a, const FlreluPlan& pl, hipStream_t st) {
     typedef MfmaGeom<UP, DOWN, TOW, TOH> G;
     FlreluMfmaParams p;
-    const int rc = fill_params(a, p, cdiv(a->yw, TOW), cdiv(a->yh, TOH));
+    const int rc = fill_params(a, p, pl.tilesX, pl.tilesY);
     if (rc != AFCM_OK) return rc;
     dim3 grid((unsigned)p.total_tiles), block(64 * G::NG);
-    const bool bias = a->b != nullptr;
-    switch (a->sign_mode) {
-        case AFCM_SIGNS_NONE: launch_one<T, UP, DOWN, TOW, TOH, AFCM_SIGNS_NONE>(p, bias, grid, block, st); break;
-        case AFCM_SIGNS_WRITE: launch_one<T, UP, DOWN, TOW, TOH, AFCM_SIGNS_WRITE>(p, bias, grid, block, st); break;
-        default: launch_one<T, UP, DOWN, TOW, TOH, AFCM_SIGNS_READ>(p, bias, grid, block, st); break;
-    }
+    with_sign_mode(a->sign_mode, [&](auto sign) {
+        constexpr int SIGN = decltype(sign)::value;
+        if (a->b != nullptr) hipLaunchKernelGGL((flrelu_mfma_kernel<T, UP, DOWN, TOW, TOH, SIGN, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((flrelu_mfma_kernel<T, UP, DOWN, TOW, TOH, SIGN, false>), grid, block, 0, st, p);
+    });
     return hip_status(hipGetLastError());
 }
 
-// wave kernels: one strip of wave_toh() output rows spans the plane's width
+// wave kernels: one strip of pl.toh output rows spans the plane's width
 template <typename T, int UP, int DOWN>
-static int launch_wave(const afcm_filtered_lrelu_args* a, hipStream_t st) {
+static int launch_wave(const afcm_filtered_lrelu_args* a, const FlreluPlan& pl, hipStream_t st) {
     AFCM_REQUIRE(a->b == nullptr, "filtered_lrelu: sign layout 2 (wave kernels) takes no bias operand");
     AFCM_REQUIRE(a->x_pitch == 0 || (a->x_pitch >= a->xw && a->x_pitch <= a->xw + kWavePitchSlack), "filtered_lrelu: x_pitch %d outside [xw, xw + %d]", a->x_pitch, kWavePitchSlack);
     AFCM_REQUIRE(a->skip_pitch == 0 || (a->skip_pitch >= a->yw && a->skip_pitch <= a->yw + kWavePitchSlack), "filtered_lrelu: skip_pitch %d outside [yw, yw + %d]", a->skip_pitch, kWavePitchSlack);
     // a pitched y is written in whole 64-column groups: the kernel covers columns < 64 * ceil(yw / 64) only, so a larger pitch would
     // leave uninitialised padding behind (the layout's contract is finite padding, include/afcm_hip.h)
     AFCM_REQUIRE(a->y_pitch == 0 || (a->y_pitch >= a->yw && a->y_pitch <= cdiv(a->yw, 64) * 64), "filtered_lrelu: y_pitch %d outside [yw, 64 * ceil(yw / 64) = %d]", a->y_pitch, cdiv(a->yw, 64) * 64);
-    const int toh = wave_toh(UP, DOWN, wave_rows(a));
     FlreluMfmaParams p;
-    const int rc = fill_params(a, p, 1, cdiv(wave_rows(a), toh));
+    const int rc = fill_params(a, p, pl.tilesX, pl.tilesY);
     if (rc != AFCM_OK) return rc;
-    int dshift;
-    p.read_aligned = wave_read_origin(a, &p.oy0, &dshift) ? 1 : 0;
-    p.py0 += dshift;                 // the fragments were prepared for this origin (prepare_mfma)
-    p.sy -= dshift;
+    p.oy0 = pl.oy0;
+    p.read_aligned = a->sign_mode == AFCM_SIGNS_READ ? 1 : 0;   // every READ call of this family is aligned (flrelu_plan)
+    p.py0 += pl.dshift;              // the fragments were prepared for this origin (prepare_mfma)
+    p.sy -= pl.dshift;
     p.clamp_flags = a->sign_mode == AFCM_SIGNS_READ ? nullptr : a->clamp_flags;
     // (r06) dense output rows with a partial second 64-column group, not line-aligned: see flush() in filtered_lrelu_wave.hip
     p.st_plain = (p.yld == p.yw && p.yw > 64 && ((p.yw * 2) & 127) != 0) ? 1 : 0;
     if constexpr (UP == 2 && DOWN == 2) {
-        if (toh == kTallTOH) return launch_wave_tile<T, 2, 2, 64, kTallTOH>(a, p, st);
+        if (pl.toh == kTallTOH) return launch_wave_tile<T, 2, 2, 64, kTallTOH>(a, p, st);
     }
     return launch_wave_tile<T, UP, DOWN, MfmaTile<UP, DOWN>::TOW, 32>(a, p, st);
 }
 
 template <typename T, int UP, int DOWN>
-static int launch_mfma(const afcm_filtered_lrelu_args* a, hipStream_t st) {
-    constexpr int TOW = MfmaTile<UP, DOWN>::TOW, TOH = MfmaTile<UP, DOWN>::TOH;
-    if (wave_family(a)) return launch_wave<T, UP, DOWN>(a, st);
-    if constexpr (UP == 2) {
-        if (tall_tile(UP, DOWN, a->yh, a->sign_mode, false)) return launch_mfma_tile<T, UP, DOWN, TOW, kTallTOH>(a, st);
-    }
-    return launch_mfma_tile<T, UP, DOWN, TOW, TOH>(a, st);
-}
-
-template <typename T, int UP, int DOWN>
-static int prepare_mfma(const afcm_filtered_lrelu_args* a, hipStream_t st) {
+static int prepare_mfma(const afcm_filtered_lrelu_args* a, const FlreluPlan& pl, hipStream_t st) {
     constexpr int TOW = MfmaTile<UP, DOWN>::TOW, TOH = MfmaTile<UP, DOWN>::TOH;
     typedef MfmaGeom<UP, DOWN, TOW, TOH> G;
     const float gain_total = (float)a->up * (float)a->up * a->gain;
     // aligned READ calls of the wave kernels: the strips' first upsampled row is (ty TOH + oy0) DOWN - dshift, no longer a multiple
     // of UP: the up-y fragments are built for the phase of py0 measured from THAT row
-    int oy0 = 0, dshift = 0;
-    if (wave_family(a)) wave_read_origin(a, &oy0, &dshift);
-    const int py0_frag = a->py0 + dshift - oy0 * DOWN;
+    const int py0_frag = a->py0 + pl.dshift - pl.oy0 * DOWN;
     hipLaunchKernelGGL((flrelu_mfma_prepare_kernel<T, UP, DOWN, TOW, TOH>), dim3(cdiv(G::NFRAG * 512, 256)), dim3(256), 0, st,
-                       (T*)a->workspace, a->fu, a->fd, a->px0, py0_frag, a->flip_filter, gain_total, a->slope, dshift);
+                       (T*)a->workspace, a->fu, a->fd, a->px0, py0_frag, a->flip_filter, gain_total, a->slope, pl.dshift);
     const int rc = hip_status(hipGetLastError());
-    return rc != AFCM_OK ? rc : prepare_wave<T, UP, DOWN>(a, py0_frag, dshift, st);
+    return rc != AFCM_OK ? rc : prepare_wave<T, UP, DOWN>(a, py0_frag, pl.dshift, st);
 }
 
-static int mfma_case(const afcm_filtered_lrelu_args* a) {
-    if (a->dtype != AFCM_BF16 && a->dtype != AFCM_F16) return 0;
-    if (a->fuh != 0 || a->fdh != 0) return 0;
-    if (a->xw & 1) return 0;                   // staged loads and stores move aligned 16-bit pairs: even plane widths
-    const long long yw = ((long long)a->xw * a->up + a->px0 + a->px1 - (a->fuw - 1) - (a->fdw - 1) + (a->down - 1)) / a->down;
-    if (yw & 1) return 0;
-    if (a->up == 2 && a->down == 2 && a->fuw == 12 && a->fdw == 12) return 22;
-    if (a->up == 2 && a->down == 4 && a->fuw == 12 && a->fdw == 24) return 24;
-    if (a->up == 4 && a->down == 2 && a->fuw == 24 && a->fdw == 12) return 42;
-    return 0;
-}
-
-int flrelu_mfma_supported(const afcm_filtered_lrelu_args* a) { return mfma_case(a) != 0; }
-
-// sign layout a WRITE call of this configuration produces (1: row-quad bytes, 2: column-blocked row-quad bytes)
-int flrelu_mfma_sign_layout(const afcm_filtered_lrelu_args* a) { return wave_family(a) ? 2 : 1; }
-
-// row pitches (x_pitch / y_pitch / skip_pitch): the wave kernels address rows by pitch, the LDS-tile kernels take dense tensors
-int flrelu_mfma_row_pitch_ok(const afcm_filtered_lrelu_args* a) { return mfma_case(a) != 0 && wave_family(a); }
-
-int flrelu_mfma_tiles(const afcm_filtered_lrelu_args* a) {
-    switch (mfma_case(a)) {
-        case 22: return wave_family(a) ? cdiv(wave_rows(a), wave_toh(2, 2, wave_rows(a))) : cdiv(a->yw, MfmaTile<2, 2>::TOW) * cdiv(a->yh, tall_tile(2, 2, a->yh, a->sign_mode, false) ? kTallTOH : MfmaTile<2, 2>::TOH);
-        case 24: return wave_family(a) ? cdiv(wave_rows(a), wave_toh(2, 4, wave_rows(a))) : cdiv(a->yw, MfmaTile<2, 4>::TOW) * cdiv(a->yh, tall_tile(2, 4, a->yh, a->sign_mode, false) ? kTallTOH : MfmaTile<2, 4>::TOH);
-        case 42: return wave_family(a) ? cdiv(wave_rows(a), wave_toh(4, 2, wave_rows(a))) : cdiv(a->yw, MfmaTile<4, 2>::TOW) * cdiv(a->yh, MfmaTile<4, 2>::TOH);
-        default: return 0;
-    }
-}
-
-int flrelu_mfma_launch(const afcm_filtered_lrelu_args* a, bool prepare, hipStream_t st) {
-#define AFCM_MF(T) do { switch (mfma_case(a)) { \
-        case 22: return prepare ? prepare_mfma<T, 2, 2>(a, st) : launch_mfma<T, 2, 2>(a, st); \
-        case 24: return prepare ? prepare_mfma<T, 2, 4>(a, st) : launch_mfma<T, 2, 4>(a, st); \
-        case 42: return prepare ? prepare_mfma<T, 4, 2>(a, st) : launch_mfma<T, 4, 2>(a, st); \
-        default: return AFCM_E_NOKERNEL; } } while (0)
-    if (a->dtype == AFCM_BF16) AFCM_MF(bf16_t);
-    else AFCM_MF(f16_t);
-#undef AFCM_MF
+// The entry of the matrix-core units: the plan's case -> template arguments, then the launch of the plan's family or its prepare.
+int flrelu_mfma(const afcm_filtered_lrelu_args* a, const FlreluPlan& pl, bool prepare, hipStream_t st) {
+    return with_up_down(pl.up, pl.down, [&](auto up, auto down) {
+        constexpr int UP = decltype(up)::value, DOWN = decltype(down)::value, TOW = MfmaTile<UP, DOWN>::TOW;
+        auto run = [&](auto t) {
+            typedef decltype(t) T;
+            if (prepare) return prepare_mfma<T, UP, DOWN>(a, pl, st);
+            if (pl.family == FLRELU_FAMILY_WAVE) return launch_wave<T, UP, DOWN>(a, pl, st);
+            if constexpr (UP == 2) {
+                if (pl.toh == kTallTOH) return launch_mfma_tile<T, UP, DOWN, TOW, kTallTOH>(a, pl, st);
+            }
+            return launch_mfma_tile<T, UP, DOWN, TOW, MfmaTile<UP, DOWN>::TOH>(a, pl, st);
+        };
+        return a->dtype == AFCM_BF16 ? run(bf16_t{}) : run(f16_t{});
+    });
 }
 
 }  // namespace afcm

@@ -4,7 +4,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "flrelu_common.h"
 
 namespace afcm {
 
@@ -111,5 +111,10 @@ __device__ __forceinline__ unsigned signs_pk(unsigned d) {
     return r.u;
 }
 
+// The wave kernels' launchers (filtered_lrelu_wave.hip, one unit per element type), called from filtered_lrelu_mfma.hip
+template <typename T, int UP, int DOWN, int TOW, int TOH>
+int launch_wave_tile(const afcm_filtered_lrelu_args* a, FlreluMfmaParams p, hipStream_t st);
+template <typename T, int UP, int DOWN>
+int prepare_wave(const afcm_filtered_lrelu_args* a, int py0_frag, int dshift, hipStream_t st);
 
 }  // namespace afcm

@@ -59,7 +59,7 @@ class _FilteredLReluPlugin:
         cfg = (int(up), int(down), int(px0), int(px1), int(py0), int(py1), float(gain), float(slope), float(clamp), bool(flip_filter),
                int(sx), int(sy), layout)
         try:
-            y, so, layout, _ = _flr._run(x, fu, fd, b, si, cfg, bool(writeSigns), allow_mfma=True, no_fallback=True)
+            y, so, layout, _ = _flr._run(x, fu, fd, b, si, cfg, bool(writeSigns), no_fallback=True)
         except _flr.NoFusedKernel:
             return torch.empty([0], dtype=x.dtype, device=x.device), empty, -1
         if so is not None and layout:

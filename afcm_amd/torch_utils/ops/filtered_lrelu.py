@@ -92,7 +92,7 @@ def _mfma_workspace(a, fu_t, fd_t, x):
     if x.dtype not in (torch.bfloat16, torch.float16) or fu_t is None or fd_t is None:
         return None
     # a READ call on codes of the wave kernels (layout 2) gets fragments whose rows are moved so that its strips fall on the sign
-    # tensor's row blocks (csrc/filtered_lrelu_mfma.hip wave_read_origin): the shift depends on sy mod 16
+    # tensor's row blocks (flrelu_plan in csrc/filtered_lrelu.hip): the shift depends on sy mod 16
     aligned_read = (a.sy % 16) if (a.sign_mode == _lib.SIGNS_READ and a.sign_layout == 2) else None
     key = (x.device, x.dtype, fu_t.data_ptr(), fu_t._version, fd_t.data_ptr(), fd_t._version, a.fuw, a.fuh, a.fdw, a.fdh,
            a.up, a.down, a.px0, a.py0, a.gain, a.slope, a.flip_filter, aligned_read)
@@ -112,11 +112,26 @@ def _mfma_workspace(a, fu_t, fd_t, x):
     return _workspaces[key][0]
 
 
+def _args(dtype_code, shape, fuw, fuh, fdw, fdh, cfg, sign_mode):
+    """afcm_filtered_lrelu_args with the part filled that fixes the layer configuration: what prepare() keys its fragments on."""
+    up, down, px0, px1, py0, py1, gain, slope, clamp, flip_filter = cfg[:10]
+    a = _lib.FilteredLReluArgs()
+    a.dtype = dtype_code
+    a.n, a.c, a.xh, a.xw = [int(v) for v in shape]
+    a.fuw, a.fuh, a.fdw, a.fdh = fuw, fuh, fdw, fdh
+    a.up, a.down = up, down
+    a.px0, a.px1, a.py0, a.py1 = px0, px1, py0, py1
+    a.gain, a.slope, a.clamp = gain, slope, clamp
+    a.flip_filter = int(flip_filter)
+    a.sign_mode = sign_mode
+    return a
+
+
 class NoFusedKernel(Exception):
     """Raised by _run(no_fallback=True) where the reference plugin returns return_code -1 (filtered_lrelu.cpp:52-56)."""
 
 
-def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, skip=None, oscale2=None, allow_mfma=True, no_fallback=False,
+def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, skip=None, oscale2=None, no_fallback=False,
          pitched_out=False, clamp_flags_out=None):
     """One launch of the op (C ABI afcm_filtered_lrelu, or the generic GPU path when there is no fused kernel).
     Returns (y, signs written or None, sign layout, per-plane output sums or None).  x / skip may be row-pitched views (_rows.py):
@@ -124,7 +139,7 @@ def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, 
     when the selected kernel can write one (callers that hand y to pitch-aware kernels only); ``clamp_flags_out``: a list that
     receives the per-strip "could reach the clamp" flags (int32 [N, C, slots]) of a sign-writing call of the wave kernels (C ABI
     afcm_filtered_lrelu_args.clamp_flags) -- left empty when another kernel family runs."""
-    up, down, px0, px1, py0, py1, gain, slope, clamp, flip_filter, sx, sy, si_layout = cfg
+    sx, sy, si_layout = cfg[10:]
     assert isinstance(x, torch.Tensor) and x.ndim == 4
     _lib.require_gpu(x, fu, fd, b, si)
     lib = _lib.load()
@@ -140,25 +155,17 @@ def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, 
     fu_t, fuw, fuh = _filter_arg(fu, x.device)
     fd_t, fdw, fdh = _filter_arg(fd, x.device)
 
-    a = _lib.FilteredLReluArgs()
-    a.dtype = _lib.dtype_code(x)
-    a.n, a.c, a.xh, a.xw = x.shape
-    a.fuw, a.fuh, a.fdw, a.fdh = fuw, fuh, fdw, fdh
-    a.up, a.down = up, down
-    a.px0, a.px1, a.py0, a.py1 = px0, px1, py0, py1
+    a = _args(_lib.dtype_code(x), x.shape, fuw, fuh, fdw, fdh, cfg,
+              _lib.SIGNS_WRITE if write_signs else (_lib.SIGNS_READ if si is not None else _lib.SIGNS_NONE))
     a.sx, a.sy = sx, sy
-    a.gain, a.slope, a.clamp = gain, slope, clamp
-    a.flip_filter = int(flip_filter)
-    a.sign_mode = _lib.SIGNS_WRITE if write_signs else (_lib.SIGNS_READ if si is not None else _lib.SIGNS_NONE)
+    a.sign_layout = si_layout if si is not None else 0      # (prepare: a READ call's fragments depend on the layout it reads)
     # 16-bit activations: matrix-core kernels (signs in the row-quad layout); a given sign tensor fixes the family
     ws = None
-    a.sign_layout = si_layout if si is not None else 0      # (prepare: a READ call's fragments depend on the layout it reads)
-    if allow_mfma and (si is None or si_layout in (1, 2)):
+    if si is None or si_layout in (1, 2):
         ws = _mfma_workspace(a, fu_t, fd_t, x)
         if si is not None and ws is None:
             raise RuntimeError('filtered_lrelu: sign tensor was written by the matrix-core kernels but this call has none')
     a.workspace = _lib.ptr(ws)
-    a.sign_layout = si_layout if si is not None else 0
     a.b = _lib.ptr(b)                     # the kernel family (and with it the sign layout a WRITE call produces) depends on it
     a.x_pitch = xld if xld != x.shape[3] else 0         # (the kernel family may depend on the plane size in memory)
     _lib.launched(lib.afcm_filtered_lrelu_shapes(a), 'filtered_lrelu')
@@ -180,7 +187,7 @@ def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, 
             raise RuntimeError('signs must be a contiguous uint8 tensor with the same batch & channels as x')
         a.sh, a.swb = si.shape[2], si.shape[3]
         a.signs = si.data_ptr()
-    a.x, a.y, a.b = x.data_ptr(), y.data_ptr(), _lib.ptr(b)
+    a.x, a.y = x.data_ptr(), y.data_ptr()
     if oscale is None and oscale2 is not None:
         oscale, oscale2 = oscale2, None
     if oscale is not None or skip is not None:
@@ -345,14 +352,5 @@ def matrix_core_available(shape, dtype, device, fu, fd, cfg):
     12/24-tap case, even widths): the condition for the epilogue factors of the fused layer op."""
     if dtype not in (torch.bfloat16, torch.float16) or fu is None or fd is None or fu.ndim != 1 or fd.ndim != 1:
         return False
-    up, down, px0, px1, py0, py1, gain, slope, clamp, flip_filter = cfg[:10]
-    a = _lib.FilteredLReluArgs()
-    a.dtype = _lib._DTYPES[dtype]
-    a.n, a.c, a.xh, a.xw = [int(v) for v in shape]
-    a.fuw, a.fuh, a.fdw, a.fdh = int(fu.shape[0]), 0, int(fd.shape[0]), 0
-    a.up, a.down = up, down
-    a.px0, a.px1, a.py0, a.py1 = px0, px1, py0, py1
-    a.gain, a.slope, a.clamp = gain, slope, clamp
-    a.flip_filter = int(flip_filter)
-    a.sign_mode = _lib.SIGNS_WRITE
+    a = _args(_lib._DTYPES[dtype], shape, int(fu.shape[0]), 0, int(fd.shape[0]), 0, cfg, _lib.SIGNS_WRITE)
     return _mfma_workspace(a, fu.contiguous(), fd.contiguous(), torch.empty(0, dtype=dtype, device=device)) is not None

@@ -1,7 +1,7 @@
 """Radial (StyleGAN3-R) filtered_lrelu on the fused tile kernels (run with `-m gpu` on an MI355X).
 
 A radial layer's down filter is a 12 x 12 2-D filter.  Its forward runs the SUFD form (separable up, 2-D down), its backward the FUSD
-form (2-D up, separable down); csrc/filtered_lrelu.hip flrelu_radial_kernel.  Bars: fp32 2e-5 x scale against the float64 oracle or
+form (2-D up, separable down); csrc/filtered_lrelu_tile.hip flrelu_radial_kernel.  Bars: fp32 2e-5 x scale against the float64 oracle or
 the reference's golden vectors (test_gpu_ops.py), 16-bit I/O 4e-3 (f16) / 3e-2 (bf16) as test_filtered_lrelu_16bit_io.
 """
 import warnings

@@ -707,7 +707,7 @@ def test_modulation_bank_is_bit_identical_to_the_layers_one_by_one(n):
 @pytest.mark.parametrize('layer,h,w,flip', [('enc1', 201, 113, False), ('enc1', 97, 50, True), ('enc4', 230, 262, False), ('enc4', 75, 118, True),
                                            ('dec3', 61, 58, False), ('dec3', 120, 27, True)])
 def test_fp32_strip_kernel_on_ragged_planes(layer, h, w, flip):
-    """csrc/filtered_lrelu.hip flrelu_strip_kernel (fp32: one wave marches down a column strip) on plane shapes that are no multiple of
+    """csrc/filtered_lrelu_strip.hip flrelu_strip_kernel (fp32: one wave marches down a column strip) on plane shapes that are no multiple of
     anything: several strips with a ragged last one (48 / 56 / 104 output columns per strip), two or three row segments (96 rows each),
     odd widths and heights, flipped filters -- forward, sign-reading backward and bias gradient against the CPU oracle at 2e-5 of the
     output's scale (the golden fixtures F1-F12 are small: one strip, one segment).  The three generator configurations: up 2 / down 2,
