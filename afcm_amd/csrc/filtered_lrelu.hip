@@ -261,6 +261,10 @@ extern "C" int afcm_filtered_lrelu(const afcm_filtered_lrelu_args* a, void* stre
     AFCM_REQUIRE(mfma || (a->oscale == nullptr && a->oscale2 == nullptr && a->skip == nullptr), "filtered_lrelu: oscale / skip need the matrix-core kernels (16-bit dtype, prepared workspace)");
     if (a->sign_mode == AFCM_SIGNS_READ)
         AFCM_REQUIRE((a->sign_layout != 0) == mfma, "sign tensor layout %d does not match the kernel family selected for this call", a->sign_layout);
+    // the wave kernels address layout 2 in whole column blocks of 16 and row groups of 16 quad-rows (the shape shapes() gives a
+    // sign-writing call): any other shape would be read at the wrong addresses, without a fault
+    if (a->sign_mode == AFCM_SIGNS_READ && a->sign_layout == 2)
+        AFCM_REQUIRE((a->sh & 15) == 0 && (a->swb & 15) == 0, "signs in layout 2 must have multiples of 16 quad-rows and columns, got [%d, %d]", a->sh, a->swb);
     if (mfma) return flrelu_mfma(a, pl, false, st);
 
     FlreluParams p;

@@ -8,6 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from flrelu_read_ref import decode_codes, read_reference
+from flrelu_read_ref import decode_layout2 as _decode_layout2
+
 pytestmark = pytest.mark.gpu
 
 LAYERS = ['encoder_0', 'encoder_1', 'encoder_4', 'encoder_5', 'encoder_7', 'encoder_9', 'encoder_11', 'encoder_12',
@@ -18,17 +21,6 @@ def _layer(name, res=256):
     from oracle import generator as ogen
     pl = ogen.plan(res, 4, 1, {})
     return [l for l in pl['enc'] + pl['dec'] if l['name'] == name][0]
-
-
-def _decode_layout2(s, sh_rows):
-    """uint8 [N, C, shq, swq] buffer in layout 2 -> codes [N, C, 4 shq, swq].  Byte of quad-row q, column c:
-    [c / 16][V / 4][q % 4][c % 16][V % 4] with V = q / 4 (csrc/filtered_lrelu_wave.hip)."""
-    n, c, shq, swq = s.shape
-    assert shq % 16 == 0 and swq % 16 == 0
-    b = s.reshape(n, c, swq // 16, shq // 16, 4, 16, 4)                   # [blk][V4][gq][col in block][V % 4]
-    b = np.transpose(b, (0, 1, 3, 6, 4, 2, 5)).reshape(n, c, shq, swq)    # quad-row = (V4 * 4 + V % 4) * 4 + gq; col = blk * 16 + col in block
-    codes = np.stack([(b >> (2 * r)) & 3 for r in range(4)], axis=3).reshape(n, c, 4 * shq, swq)
-    return codes[:, :, :sh_rows]
 
 
 @pytest.mark.parametrize('dtype,tol', [(torch.float16, 6e-3), (torch.bfloat16, 4e-2)])
@@ -51,9 +43,15 @@ def test_wave_kernels_forward_backward_vs_oracle(lname, dtype, tol):
     assert got.grad_fn.sign_layout == 2, 'expected the wave-autonomous kernels'
     err = (got.float().cpu() - ref).abs().max().item()
     assert err <= tol * max(1.0, ref.abs().max().item()), f'{lname} {dtype} y: {err:.3e}'
+    s = got.grad_fn.saved_tensors[2].cpu().numpy()                        # (before the backward pass frees it)
     ggot, = torch.autograd.grad((got.float() * r.cuda().float()).sum(), xg)
     rel = ((ggot.float().cpu() - gref).norm() / gref.norm()).item()       # 16-bit rounding flips leaky-ReLU branches near 0
     assert rel <= 2 * tol, f'{lname} {dtype} dx: relative L2 {rel:.3e}'
+    # with the codes the kernel read given, no branch can flip: every element of dx at the forward's bound
+    bcfg = flr._backward_cfg((L['up'], L['down'], *L['padding'], kw['gain'], kw['slope'], kw['clamp'], False, 0, 0, 0), L['fu'], L['fd'], x.shape, ref.shape, 2)
+    want = read_reference(r.double().numpy(), L['fd'].numpy(), L['fu'].numpy(), bcfg, decode_codes(s, 2))
+    err = np.abs(ggot.double().cpu().numpy() - want).max()
+    assert err <= tol * max(1.0, np.abs(want).max()), f'{lname} {dtype} dx, given codes: max-abs {err:.3e}'
     # inference mode (no sign tensor) runs the same arithmetic
     with torch.no_grad():
         y2 = flr.filtered_lrelu(x.cuda(), fu=L['fu'].cuda(), fd=L['fd'].cuda(), b=None, **kw)

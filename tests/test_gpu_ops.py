@@ -293,11 +293,17 @@ def test_filtered_lrelu_16bit_matrix_core_path(lname, dtype, tol):
     gbref, = torch.autograd.grad((ref2 * r.float()).sum(), bref)
     assert (gb.float().cpu() - gbref).abs().max().item() <= 4 * tol * max(1.0, gbref.abs().max().item()), 'fused bias gradient'
     _close(got, ref, tol=tol, what=f'{lname} {dtype} y')
+    s = got.grad_fn.saved_tensors[2].cpu().numpy()                        # (before the backward pass frees it)
     ggot, = torch.autograd.grad((got.float() * r.cuda().float()).sum(), xg)
     # leaky-ReLU kinks: 16-bit forward rounding flips the branch of elements near 0, so compare in relative L2
     d = (ggot.float().cpu() - gref)
     rel = (d.norm() / gref.norm()).item()
     assert rel <= 2 * tol, f'{lname} {dtype} dx: relative L2 {rel:.3e}'
+    # with the codes the kernel read given (row-quad layout, decoded), no branch can flip: every element of dx at the forward's bound
+    from flrelu_read_ref import decode_codes, read_reference
+    bcfg = flr._backward_cfg((L['up'], L['down'], *L['padding'], kw['gain'], kw['slope'], kw['clamp'], False, 0, 0, 0), L['fu'], L['fd'], x.shape, ref.shape, 1)
+    want = read_reference(r.double().numpy(), L['fd'].numpy(), L['fu'].numpy(), bcfg, decode_codes(s, 1))
+    _close(ggot, want, tol=tol, what=f'{lname} {dtype} dx, given codes')
 
 
 def test_filtered_lrelu_16bit_odd_width_uses_exact_kernels():
