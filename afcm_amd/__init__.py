@@ -8,6 +8,7 @@ Layout
   networks_stylegan3.py  drop-in generator (same class names, forward() signatures, state-dict keys)
   stylegan3_model.py     the generator part of the training step (run_G, fwd+bwd)
   distributed.py         one-process-per-GPU data parallelism: bucketed RCCL all-reduce of gradients
+  validation.py          the trainer's validation loop; evaluation_device.py: its PSNR / SSIM / MAE from one statistics kernel per batch
 
 There is no CPU fallback in this package: ops raise if the tensors are not on a ROCm device or the
 HIP library is not built.  The CPU restatement used for parity checks lives in the top-level

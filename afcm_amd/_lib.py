@@ -72,7 +72,7 @@ ABI_VERSION = 13
 
 # name -> (restype, argtypes); every symbol include/afcm_hip.h declares must be listed here
 # (tests/test_abi.py cross-checks this table against the header).
-_i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+_i32, _i64, _f32, _f64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 SIGNATURES = {
     'afcm_abi_version': (C.c_int, []),
     'afcm_last_error': (C.c_char_p, []),
@@ -132,6 +132,8 @@ SIGNATURES = {
     'afcm_adam_chunk_elems': (C.c_int32, []),
     'afcm_adam_multi': (C.c_int, [_vp, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
     'afcm_adam_multi_capturable': (C.c_int, [_vp, _i32, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
+    'afcm_plane_metrics_workspace_bytes': (C.c_int64, [_i64, _i32, _i32]),
+    'afcm_plane_metrics': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _vp]),
 }
 
 

@@ -154,3 +154,93 @@ def evaluate_3D(Gimg, Limg):
 def to_unit_range(x):
     """train.py:93-96: [-1, 1] network range -> [0, 1], clipped."""
     return np.clip((np.asarray(x, dtype=np.float32) + 1) / 2, 0, 1)
+
+
+# ---- the same numbers from the per-plane statistics table of the device kernel -------------------------------------------------------
+# afcm_plane_metrics (include/afcm_hip.h; torch_utils/ops/plane_metrics.py) reduces a pair of image stacks to a float64 [planes, 8] table:
+#   0, 1 max / min of the reference   2, 3 max / min of the prediction   4 sum (r - t)^2   5 sum (r / max r - t / max t)^2   6 sum |r - t|
+#   7 sum of the 7 x 7 SSIM map (data range 2) over its (h - 6)(w - 6) valid windows.
+# The finishers below are pure numpy on a host copy of that table and keep the bookkeeping of the functions above: which slices count, the data
+# range of each PSNR, inf for identical images, nan for a prediction whose maximum is zero.  One difference is inherent: the table's arithmetic
+# is float64 throughout, where the functions above follow the dtype of their arrays in three places (psnr_2D's division by the maximum, ThreeD_psnr's
+# joint range and the MAE mean run in float32 on float32 arrays).  On float64 arrays the two agree to rounding; on float32 arrays PSNR moves by up
+# to ~1e-7 dB and MAE by ~1e-7 relative (tests/test_plane_metrics_cpu.py).
+_MAX_R, _MIN_R, _MAX_T, _MIN_T, _SUM_SQ, _SUM_SQ_MAXNORM, _SUM_ABS, _SUM_SSIM = range(8)
+
+
+def _table(table):
+    t = np.asarray(table, dtype=np.float64)
+    if t.ndim != 2 or t.shape[1] != 8:
+        raise ValueError(f'expected a [planes, 8] statistics table, got shape {t.shape}')
+    return t
+
+
+def _psnr_from_sum(data_range, sum_sq, npix):
+    """peak_signal_noise_ratio's last two lines with the squared-error sum in hand."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return float(10 * np.log10((np.float64(data_range) ** 2) / (np.float64(sum_sq) / npix)))
+
+
+def _psnr_2D_from_row(row, npix):
+    """psnr_2D: both images divided by their own maxima, data range from the normalised reference as ``_float_data_range`` picks it."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        lo, hi = float(row[_MIN_R] / row[_MAX_R]), float(row[_MAX_R] / row[_MAX_R])
+    if hi > 1 or lo < -1:
+        raise ValueError('image_true has intensity values outside the range expected for its data type; specify data_range')
+    return _psnr_from_sum(1.0 if lo >= 0 else 2.0, row[_SUM_SQ_MAXNORM], npix)
+
+
+def evaluate_2D_from_stats(table, h, w):
+    """``evaluate_2D`` of a batch from its table ([N, 8], one h x w plane per slice): (PSNR, SSIM, MAE) or None when every target is empty."""
+    t = _table(table)
+    npix, nwin = h * w, (h - 6) * (w - 6)
+    mae = float(t[:, _SUM_ABS].sum() / (t.shape[0] * npix))
+    c_psnr = c_ssim = c_mse = 0.0
+    count = 0
+    for row in t:
+        if row[_MAX_R] <= 0:
+            continue
+        c_psnr += _psnr_2D_from_row(row, npix)
+        c_ssim += float(row[_SUM_SSIM] / nwin)
+        c_mse += mae
+        count += 1
+    if count == 0:
+        return None
+    return c_psnr / count, c_ssim / count, c_mse / count
+
+
+def evaluate_slice_from_stats(table, h, w):
+    """``evaluate_slice`` of a volume from the table of its axial slices ([D, 8], planes h x w)."""
+    t = _table(table)
+    npix, nwin = h * w, (h - 6) * (w - 6)
+    c_psnr = c_ssim = 0.0
+    count = 0
+    for row in t:
+        if row[_MAX_R] <= 0:
+            continue
+        c_psnr += _psnr_2D_from_row(row, npix)
+        c_ssim += float(row[_SUM_SSIM] / nwin)
+        count += 1
+    return c_psnr / count, c_ssim / count, float(t[:, _SUM_ABS].sum() / (t.shape[0] * npix))
+
+
+def evaluate_one_from_stats(tables_by_axis, shape):
+    """``evaluate_one`` of a volume of ``shape`` from the three tables of its slices along axis 0, 1 and 2 ([shape[axis], 8] each)."""
+    tables = [_table(t) for t in tables_by_axis]
+    if len(tables) != 3 or len(shape) != 3 or any(t.shape[0] != n for t, n in zip(tables, shape)):
+        raise ValueError(f'expected three tables of {tuple(shape)} rows, got {[t.shape[0] for t in tables]}')
+    c_psnr = c_ssim = 0.0
+    seen = 0
+    for axis, t in enumerate(tables):
+        h, w = (n for a, n in enumerate(shape) if a != axis)
+        npix, nwin = h * w, (h - 6) * (w - 6)
+        for i, row in enumerate(t):
+            d_range = max(row[_MAX_R], row[_MAX_T]) - min(row[_MIN_R], row[_MIN_T])
+            if d_range == 0:
+                c_psnr += c_psnr / (seen + i + 1)
+            else:
+                c_psnr += _psnr_from_sum(d_range, row[_SUM_SQ], npix)
+            c_ssim += float(row[_SUM_SSIM] / nwin)
+        seen += shape[axis]
+    total = sum(shape)
+    return c_psnr / total, c_ssim / total, float(tables[0][:, _SUM_ABS].sum() / (shape[0] * shape[1] * shape[2]))

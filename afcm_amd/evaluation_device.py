@@ -1,0 +1,50 @@
+"""The validation metrics of ``afcm_amd.evaluation`` for DEVICE tensors: one statistics kernel (torch_utils/ops/plane_metrics.py), one
+device -> host copy of its [planes, 8] float64 table, and the numpy finisher that applies the reference's bookkeeping (util/evaluation.py:92-121).
+
+Argument order follows the reference: (prediction, target).  ``evaluate_3D`` (7^3 window) stays host-only.
+"""
+import torch
+
+from . import evaluation
+from .torch_utils.ops.plane_metrics import plane_stats
+
+
+def as_planes(x):
+    """[N, 1, ..., H, W] -> the [N, H, W] view of it (no copy: the singleton axes are indexed away, strides are kept)."""
+    while x.dim() > 3:
+        if x.shape[1] != 1:
+            raise RuntimeError(f'expected singleton axes between the batch and the image, got shape {tuple(x.shape)}')
+        x = x[:, 0]
+    if x.dim() != 3:
+        raise RuntimeError(f'expected [N, ..., H, W], got shape {tuple(x.shape)}')
+    return x
+
+
+def batch_stats(fake, real, from_network_range=True):
+    """The table of one batch, left on the device (``validation.validate`` gathers these and copies once)."""
+    return plane_stats(as_planes(real), as_planes(fake), unit_map=from_network_range)
+
+
+def evaluate_2D(fake, real, from_network_range=True):
+    """``evaluation.evaluate_2D`` for batches [N, 1, (1,) H, W] on the device.  ``from_network_range`` applies train.py:93-96 (``to_unit_range``)
+    on load; pass False for tensors that are already in [0, 1]."""
+    t = batch_stats(fake, real, from_network_range)
+    h, w = real.shape[-2:]
+    return evaluation.evaluate_2D_from_stats(t.cpu().numpy(), int(h), int(w))
+
+
+def evaluate_slice(fake, real, from_network_range=False):
+    """``evaluation.evaluate_slice`` for volumes [D, H, W] on the device."""
+    t = batch_stats(fake, real, from_network_range)
+    h, w = real.shape[-2:]
+    return evaluation.evaluate_slice_from_stats(t.cpu().numpy(), int(h), int(w))
+
+
+def evaluate_one(fake, real, from_network_range=False):
+    """``evaluation.evaluate_one`` for volumes [D, H, W] on the device: the slices along the three axes are read in place as strided views."""
+    if fake.dim() != 3 or fake.shape != real.shape:
+        raise RuntimeError(f'evaluate_one: expected two [D, H, W] volumes of one shape, got {tuple(fake.shape)} and {tuple(real.shape)}')
+    views = ((0, 1, 2), (1, 0, 2), (2, 0, 1))
+    tables = torch.cat([plane_stats(real.permute(*p), fake.permute(*p), unit_map=from_network_range) for p in views]).cpu().numpy()
+    d, h, w = (int(v) for v in real.shape)
+    return evaluation.evaluate_one_from_stats((tables[:d], tables[d:d + h], tables[d + h:]), (d, h, w))

@@ -21,7 +21,8 @@
  *     falls back to the generic upfirdn2d + act path); AFCM_E_INVALID (-2) = argument check
  *     failed (the reference's TORCH_CHECK); >= 1000 = 1000 + hipError_t of the launch.
  *   - dtype codes: AFCM_F32, AFCM_F16, AFCM_BF16 (bf16 is new capability; the reference
- *     plugin accepts half/float only).  Arithmetic is always fp32 inside the kernels.
+ *     plugin accepts half/float only).  Arithmetic is always fp32 inside the kernels, with ONE exception:
+ *     afcm_plane_metrics (validation metrics, end of this header) computes in float64 after its loads.
  */
 #ifndef AFCM_HIP_H
 #define AFCM_HIP_H
@@ -32,7 +33,7 @@
 extern "C" {
 #endif
 
-#define AFCM_ABI_VERSION 13  /* 13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
+#define AFCM_ABI_VERSION 13  /* 13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
 
 enum { AFCM_F32 = 0, AFCM_F16 = 1, AFCM_BF16 = 2 };
 enum { AFCM_OK = 0, AFCM_E_NOKERNEL = -1, AFCM_E_INVALID = -2 };
@@ -485,6 +486,30 @@ int64_t afcm_mapping_input_bwd_workspace_bytes(int32_t n, int32_t wdim);
  * one row of the intermediate gradient per sample + the ticket by which the last workgroup to finish sums the rows (fixed order: reproducible). */
 int afcm_mapping_input_bwd(float* dew, float* deb, const float* gx0, const float* c, const float* ew, const float* eb, int32_t n, int32_t zdim,
                            int32_t cdim, int32_t wdim, float alpha, float beta, void* workspace, void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Validation metrics (r07): the per-plane statistics from which the host finishes the reference's PSNR / SSIM / MAE
+ * (util/evaluation.py:6-127 behind the validation loop train.py:83-111; the reference computes them with scikit-image on host copies, one
+ * slice at a time).  table [planes][8] float64, for plane p with r / t the loaded values of ref / test:
+ *     0, 1  max r, min r          2, 3  max t, min t
+ *     4     sum (r - t)^2         5     sum (r / max r - t / max t)^2   (psnr_2D's max-normalised pair, util/evaluation.py:31-37; one IEEE
+ *                                       float64 divide per element, so a zero maximum gives inf / nan as numpy does and never traps)
+ *     6     sum |r - t|           7     sum of the SSIM map over the (h - 6)(w - 6) windows that lie inside the plane (7 x 7 uniform window,
+ *                                       sample covariance: ((2 ux uy + c1)(2 vxy + c2)) / ((ux^2 + uy^2 + c1)(vx + vy + c2)); the reference
+ *                                       averages the cropped interior only, so no border mode exists)
+ * ref / test: DEVICE images of dtype_ref / dtype_test (they may differ), element (p, y, x) at p * stride_plane + y * stride_row + x * stride_col
+ * ELEMENTS: any strides, so the three axis-slicings of a volume and a row-pitched generator output are read in place.  unit_map = 1 maps every
+ * loaded value from the network's range first, clip((float(x) + 1.0f) * 0.5f, 0, 1) in fp32 as two separate roundings (train.py:93-96).
+ * PRECISION: this is the exception to "arithmetic is fp32" above -- after the load (and the map) every operation is float64.
+ * Two phases on the stream, no host step between them: the planes' extrema (column 5 needs them), then the sums.  No atomics: tiles store
+ * partials into `workspace` (afcm_plane_metrics_workspace_bytes() bytes, no initialisation needed) and one wave per plane adds them in a fixed
+ * order, so the table is bit-identical from call to call.  h, w >= 7 (AFCM_E_INVALID otherwise); NaN inputs are not supported (the extrema
+ * skip them).
+ * ---------------------------------------------------------------------------------------- */
+int64_t afcm_plane_metrics_workspace_bytes(int64_t planes, int32_t h, int32_t w);
+int afcm_plane_metrics(double* table, const void* ref, const void* test, int32_t dtype_ref, int32_t dtype_test, int64_t planes, int32_t h, int32_t w,
+                       int64_t ref_stride_plane, int64_t ref_stride_row, int64_t ref_stride_col, int64_t test_stride_plane, int64_t test_stride_row,
+                       int64_t test_stride_col, int32_t unit_map, double c1, double c2, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
