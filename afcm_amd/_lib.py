@@ -92,6 +92,8 @@ SIGNATURES = {
     'afcm_conv2d_pack_weights2': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'afcm_conv2d': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'afcm_conv2d_ld': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    'afcm_conv2d_plan': (C.c_int, [_i32] * 11 + [C.POINTER(_i32)]),
+    'afcm_conv2d_wgrad_plan': (C.c_int, [_i32] * 11 + [C.POINTER(_i32)]),
     'afcm_conv2d_wgrad_splits': (C.c_int, [_i32, _i32, _i32, _i32]),
     'afcm_conv2d_wgrad': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     'afcm_conv2d_wgrad_ld': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -1359,14 +1359,67 @@ static int conv_persistent_grid(long long items, int per_cu) {
 }
 
 // conv2d_fwd16x_kernel<.., FASTEPI>: tile widths that are multiples of 16 on output rows whose pitch is a multiple of 8 elements
-static bool conv_fast_epilogue(const ConvParams& p) {
-    return (p.TW & 15) == 0 && (p.ldy & 7) == 0 && (p.Q & 1) == 0;
+static bool conv_fast_epilogue(int TW, int ldy, int Q) {
+    return (TW & 15) == 0 && (ldy & 7) == 0 && (Q & 1) == 0;
 }
 
-// conv2d_fwd16x_kernel<T, BM_O, SPLIT> on `grid` workgroups; the fast epilogue where conv_fast_epilogue allows it (plain outputs only)
+// Which kernel family a stride-1 conv takes, on which tile, over how many work items and workgroups: the ONE place where
+// afcm_conv2d_ld and afcm_conv2d_split decide it, and what afcm_conv2d_plan reports.
+enum { kConvDirect = 0, kConv96 = 1, kConv128p64 = 2, kConv64 = 3, kConv128 = 4 };
+enum { kConvKernelX16 = 0, kConvKernelGeneral16 = 1, kConvKernelF32 = 2, kConvKernelDirect = 3, kConvKernelX16Split = 4 };
+struct ConvPlan {
+    int family;             // kConv*
+    int kernel;             // kConvKernel*
+    int rows;               // output rows per block of the launch that `items` / `grid` describe (128 + 64: the 64-row launch)
+    int big;                // 128 + 64: 128-row blocks in front of the 64-row one (rows [0, 128 big), one item per workgroup)
+    int TH, TW, PWL;        // output tile and LDS patch row (0 for the direct kernel: its tile is fixed, conv2d_direct.hip)
+    long long items;        // tiles x images x row blocks
+    long long grid;         // workgroups: items, or one round of resident workgroups for the persistent launches
+    bool fast;              // conv2d_fwd16x_kernel<.., FASTEPI>
+};
+
+static ConvPlan conv_plan(int dtype, int n, int cin, int cout, int P, int Q, int ks, int rows_pad, int ldy, bool split) {
+    ConvPlan pl;
+    pl.family = kConvDirect; pl.kernel = kConvKernelDirect; pl.rows = 64; pl.big = 0; pl.TH = pl.TW = pl.PWL = 0; pl.items = pl.grid = 0; pl.fast = false;
+    const bool x16 = dtype != AFCM_F32 && ks == 3;
+    if (!split && x16 && cin <= 4 && cout <= 64) {
+        // a handful of input channels: the contraction index is (tap column, channel), no channel padding (conv2d_direct.hip; r06)
+        return pl;
+    }
+    choose_tile(P, Q, ks, &pl.TH, &pl.TW, &pl.PWL, x16 ? kPatchMaxX16 : kPatchMax);
+    const long long tiles = (long long)cdiv(Q, pl.TW) * cdiv(P, pl.TH) * n;
+    pl.kernel = split ? kConvKernelX16Split : x16 ? kConvKernelX16 : dtype == AFCM_F32 ? kConvKernelF32 : kConvKernelGeneral16;
+    pl.fast = !split && x16 && conv_fast_epilogue(pl.TW, ldy, Q);
+    // 64-row blocks when they waste fewer padded rows than 128-row blocks
+    const bool small = (rows_pad % 128 != 0) || cout <= 64;
+    if (!split && x16 && cout > 64 && cout <= 96) {
+        // 65 .. 96 output rows (the 91-channel layers): one 96-row block instead of 128 rows of MFMAs for them.  (129 .. 192 rows as two
+        // 96-row blocks instead of 128 + 64 measured the same: profiles/r05_conv_bm96_ab.txt)
+        pl.family = kConv96; pl.rows = 96;
+        pl.items = tiles * cdiv(cout, 96);
+        pl.grid = conv_persistent_grid(pl.items, 2);
+        return pl;
+    }
+    if (!split && x16 && rows_pad % 128 == 64 && rows_pad > 128) {
+        // ... and both when the rows are 128 k + (1 .. 64) (the 181-channel layers: 192 padded rows): the 128-row kernel moves half the
+        // pixel-fragment bytes per flop of the 64-row one, so rows [0, 128 k) go to it and only the last 64 to the 64-row kernel -- two
+        // launches, disjoint output rows, the same number of passes over x as three 64-row blocks had
+        pl.family = kConv128p64; pl.rows = 64; pl.big = rows_pad / 128;
+        pl.items = tiles;
+        pl.grid = conv_persistent_grid(pl.items, 3);
+        return pl;
+    }
+    pl.family = small ? kConv64 : kConv128; pl.rows = small ? 64 : 128;
+    pl.items = tiles * cdiv(cout, pl.rows);
+    // the 64-row 16x16x32 kernel is persistent: one round of three workgroups per CU; every other kernel takes one item per workgroup
+    pl.grid = (small && (split || x16)) ? conv_persistent_grid(pl.items, 3) : pl.items;
+    return pl;
+}
+
+// conv2d_fwd16x_kernel<T, BM_O, SPLIT> on `grid` workgroups; the fast epilogue where the plan allows it (plain outputs only)
 template <typename T, int BM_O, bool SPLIT>
-static int launch_fwd16x(const ConvParams& p, dim3 grid, hipStream_t st) {
-    if (!SPLIT && conv_fast_epilogue(p)) hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, false, true>), grid, dim3(256), 0, st, p);
+static int launch_fwd16x(const ConvParams& p, dim3 grid, bool fast, hipStream_t st) {
+    if (!SPLIT && fast) hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, false, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((conv2d_fwd16x_kernel<T, BM_O, SPLIT>), grid, dim3(256), 0, st, p);
     return hip_status(hipGetLastError());
 }
@@ -1391,10 +1444,10 @@ static ConvParams conv_params(void* y, const void* x, const void* wp, const floa
     return p;
 }
 
-// o_base / row_blocks: the launch covers output rows [o_base, o_base + row_blocks * BM_O) (16-bit 3x3 16x16x32 kernel only; 0: all rows)
+// `blocks` work items on `pgrid` workgroups (the persistent 64-row 16x16x32 kernel; every other kernel: one workgroup per item); o_base:
+// the launch covers output rows from o_base on (16-bit 3x3 16x16x32 kernel only)
 template <typename T, int BM_O>
-static int launch_conv(ConvParams p, int ks, hipStream_t st, int o_base = 0, int row_blocks = 0) {
-    const long long blocks = (long long)p.tilesX * p.tilesY * p.N * (row_blocks ? row_blocks : cdiv(p.Cout, BM_O));
+static int launch_conv(ConvParams p, int ks, hipStream_t st, long long blocks, long long pgrid, bool fast, int o_base = 0) {
     p.o_base = o_base;
     AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d: grid of %lld blocks is out of range", blocks);
     dim3 grid((unsigned)blocks), block(256);
@@ -1402,7 +1455,7 @@ static int launch_conv(ConvParams p, int ks, hipStream_t st, int o_base = 0, int
     if constexpr (sizeof(T) == 2) {
         // 16-bit: 3x3 on the 16x16x32 kernel (the 64-row kernel is persistent: one round of three workgroups per CU; the 128-row kernel
         // takes one item per workgroup), 1x1 on the general one
-        if (ks == 3) return launch_fwd16x<T, BM_O, false>(p, BM_O == 64 ? dim3((unsigned)conv_persistent_grid(blocks, 3)) : grid, st);
+        if (ks == 3) return launch_fwd16x<T, BM_O, false>(p, BM_O == 64 ? dim3((unsigned)pgrid) : grid, fast, st);
         hipLaunchKernelGGL((conv2d_fwd_kernel<T, BM_O, 1>), grid, block, 0, st, p);
     } else {
         if (ks == 3) hipLaunchKernelGGL((conv2d_fwd_kernel<T, BM_O, 3>), grid, block, 0, st, p);
@@ -1568,38 +1621,30 @@ extern "C" int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const
         AFCM_REQUIRE((long long)cout * P * ldy < (1ll << 30), "conv2d: pitched output image is out of range");
     }
     AFCM_REQUIRE(dtype == AFCM_F32 || ks != 3 || (long long)cout * P * ldy * 2 < (1ll << 30), "conv2d: 16-bit output image of %lld bytes is out of range (< 2^30)", (long long)cout * P * ldy * 2);
-    if (dtype != AFCM_F32 && ks == 3 && cin <= 4 && cout <= 64) {
-        // a handful of input channels: the contraction index is (tap column, channel), no channel padding (conv2d_direct.hip; r06)
+    const ConvPlan pl = conv_plan(dtype, n, cin, cout, P, Q, ks, rows_pad, ldy, false);
+    if (pl.family == kConvDirect)
         return conv2d_direct_small_cin(x, y, wpacked, oscale, obias, dtype, n, cin, cout, h, w, pad, rows_pad, 32, ldx, ldy, (hipStream_t)stream);
-    }
-    int TH, TW, PWL;
-    choose_tile(P, Q, ks, &TH, &TW, &PWL, (dtype != AFCM_F32 && ks == 3) ? kPatchMaxX16 : kPatchMax);
-    ConvParams p = conv_params(y, x, wpacked, oscale, obias, n, cin, cout, h, w, P, Q, pad, ldx, ldy, TH, TW, PWL, rows_pad, cdiv(cin, conv_bk(dtype, ks)));
+    ConvParams p = conv_params(y, x, wpacked, oscale, obias, n, cin, cout, h, w, P, Q, pad, ldx, ldy, pl.TH, pl.TW, pl.PWL, rows_pad, cdiv(cin, conv_bk(dtype, ks)));
     hipStream_t st = (hipStream_t)stream;
-    // 64-row blocks when they waste fewer padded rows than 128-row blocks
-    const bool small = (rows_pad % 128 != 0) || cout <= 64;
-    // ... and both when the rows are 128 k + (1 .. 64) (the 181-channel layers: 192 padded rows): the 128-row kernel moves half the
-    // pixel-fragment bytes per flop of the 64-row one, so rows [0, 128 k) go to it and only the last 64 to the 64-row kernel -- two
-    // launches, disjoint output rows, the same number of passes over x as three 64-row blocks had
-    if (dtype != AFCM_F32 && ks == 3 && cout > 64 && cout <= 96) {
-        // 65 .. 96 output rows (the 91-channel layers): one 96-row block instead of 128 rows of MFMAs for them.  (129 .. 192 rows as two
-        // 96-row blocks instead of 128 + 64 measured the same: profiles/r05_conv_bm96_ab.txt)
-        const long long blocks = (long long)p.tilesX * p.tilesY * p.N * cdiv(cout, 96);
-        AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d: grid of %lld blocks is out of range", blocks);
-        p.total_blocks = (int)blocks;
-        const dim3 g96((unsigned)conv_persistent_grid(blocks, 2));
-        return dtype == AFCM_F16 ? launch_fwd16x<f16_t, 96, false>(p, g96, st) : launch_fwd16x<bf16_t, 96, false>(p, g96, st);
+    if (pl.family == kConv96) {
+        AFCM_REQUIRE(pl.items > 0 && pl.items < (1ll << 31), "conv2d: grid of %lld blocks is out of range", pl.items);
+        p.total_blocks = (int)pl.items;
+        const dim3 g96((unsigned)pl.grid);
+        return dtype == AFCM_F16 ? launch_fwd16x<f16_t, 96, false>(p, g96, pl.fast, st) : launch_fwd16x<bf16_t, 96, false>(p, g96, pl.fast, st);
     }
-    if (dtype != AFCM_F32 && ks == 3 && rows_pad % 128 == 64 && rows_pad > 128) {
-        const int big = rows_pad / 128;
-        const int rc = dtype == AFCM_F16 ? launch_conv<f16_t, 128>(p, ks, st, 0, big) : launch_conv<bf16_t, 128>(p, ks, st, 0, big);
+    if (pl.family == kConv128p64) {
+        const long long items128 = pl.items * pl.big;
+        const int rc = dtype == AFCM_F16 ? launch_conv<f16_t, 128>(p, ks, st, items128, items128, pl.fast)
+                                         : launch_conv<bf16_t, 128>(p, ks, st, items128, items128, pl.fast);
         if (rc != AFCM_OK) return rc;
-        return dtype == AFCM_F16 ? launch_conv<f16_t, 64>(p, ks, st, big * 128, 1) : launch_conv<bf16_t, 64>(p, ks, st, big * 128, 1);
+        return dtype == AFCM_F16 ? launch_conv<f16_t, 64>(p, ks, st, pl.items, pl.grid, pl.fast, pl.big * 128)
+                                 : launch_conv<bf16_t, 64>(p, ks, st, pl.items, pl.grid, pl.fast, pl.big * 128);
     }
+    const bool small = pl.family == kConv64;
     switch (dtype) {
-        case AFCM_F32: return small ? launch_conv<float, 64>(p, ks, st) : launch_conv<float, 128>(p, ks, st);
-        case AFCM_F16: return small ? launch_conv<f16_t, 64>(p, ks, st) : launch_conv<f16_t, 128>(p, ks, st);
-        default: return small ? launch_conv<bf16_t, 64>(p, ks, st) : launch_conv<bf16_t, 128>(p, ks, st);
+        case AFCM_F32: return small ? launch_conv<float, 64>(p, ks, st, pl.items, pl.grid, pl.fast) : launch_conv<float, 128>(p, ks, st, pl.items, pl.grid, pl.fast);
+        case AFCM_F16: return small ? launch_conv<f16_t, 64>(p, ks, st, pl.items, pl.grid, pl.fast) : launch_conv<f16_t, 128>(p, ks, st, pl.items, pl.grid, pl.fast);
+        default: return small ? launch_conv<bf16_t, 64>(p, ks, st, pl.items, pl.grid, pl.fast) : launch_conv<bf16_t, 128>(p, ks, st, pl.items, pl.grid, pl.fast);
     }
 }
 
@@ -1641,22 +1686,40 @@ extern "C" int afcm_conv2d_split(float* y, const void* x_parts, const void* wpac
                  "conv2d_split: part stride %lld out of range", (long long)part_stride);
     const int P = h + 2 * pad - ks + 1, Q = w + 2 * pad - ks + 1;
     AFCM_REQUIRE(P >= 1 && Q >= 1, "output must be at least 1x1");
-    int TH, TW, PWL;
-    choose_tile(P, Q, ks, &TH, &TW, &PWL, kPatchMaxX16);
+    const ConvPlan pl = conv_plan(dtype, n, cin, cout, P, Q, ks, rows_pad, Q, true);
     const int nkc_real = cdiv(cin, conv_bk(dtype, 3));
-    ConvParams p = conv_params(y, x_parts, wpacked, oscale, obias, n, cin, cout, h, w, P, Q, pad, w, Q, TH, TW, PWL, rows_pad, nkc_real);
+    ConvParams p = conv_params(y, x_parts, wpacked, oscale, obias, n, cin, cout, h, w, P, Q, pad, w, Q, pl.TH, pl.TW, pl.PWL, rows_pad, nkc_real);
     p.nkc = terms * p.nkc_real;
     p.magicNK = magic_u32((unsigned)p.nkc_real);
     p.term_parts = term_parts;
     p.part_bytes = (int)(part_stride * 2);
     p.last_part_bytes = max_part * p.part_bytes;
     p.bound_a = (const unsigned*)bound_a; p.bound_b = (const unsigned*)bound_b;
-    const bool small = (rows_pad % 128 != 0) || cout <= 64;
-    const long long blocks = (long long)p.tilesX * p.tilesY * p.N * cdiv(p.Cout, small ? 64 : 128);
+    const bool small = pl.family == kConv64;
+    const long long blocks = pl.items;
     AFCM_REQUIRE(blocks > 0 && blocks < (1ll << 31), "conv2d_split: grid of %lld blocks is out of range", blocks);
     hipStream_t st = (hipStream_t)stream;
     p.total_blocks = (int)blocks;
-    const dim3 pgrid(small ? (unsigned)conv_persistent_grid(blocks, 3) : (unsigned)blocks);
-    if (dtype == AFCM_BF16) return small ? launch_fwd16x<bf16_t, 64, true>(p, pgrid, st) : launch_fwd16x<bf16_t, 128, true>(p, pgrid, st);
-    return small ? launch_fwd16x<f16_t, 64, true>(p, pgrid, st) : launch_fwd16x<f16_t, 128, true>(p, pgrid, st);
+    const dim3 pgrid((unsigned)pl.grid);
+    if (dtype == AFCM_BF16) return small ? launch_fwd16x<bf16_t, 64, true>(p, pgrid, false, st) : launch_fwd16x<bf16_t, 128, true>(p, pgrid, false, st);
+    return small ? launch_fwd16x<f16_t, 64, true>(p, pgrid, false, st) : launch_fwd16x<f16_t, 128, true>(p, pgrid, false, st);
+}
+
+// Pure host: the plan afcm_conv2d_ld (split == 0) / afcm_conv2d_split (split != 0) follow for these arguments, rows_pad = cout rounded up to 64
+extern "C" int afcm_conv2d_plan(int32_t dtype, int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t x_pitch,
+                                int32_t y_pitch, int32_t split, int32_t out[8]) {
+    AFCM_REQUIRE(out != nullptr, "conv2d_plan: null pointer");
+    AFCM_REQUIRE(dtype == AFCM_F32 || dtype == AFCM_F16 || dtype == AFCM_BF16, "x must be float32, float16 or bfloat16");
+    AFCM_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0, "x is empty");
+    AFCM_REQUIRE(ks == 1 || ks == 3, "only 1x1 and 3x3 kernels are supported");
+    AFCM_REQUIRE(pad >= 0 && pad <= ks - 1, "padding must be in [0, k-1]");
+    AFCM_REQUIRE(!split || (ks == 3 && dtype != AFCM_F32), "conv2d_plan: the split route is 3x3 on 16-bit parts");
+    const int P = h + 2 * pad - ks + 1, Q = w + 2 * pad - ks + 1;
+    AFCM_REQUIRE(P >= 1 && Q >= 1, "output must be at least 1x1");
+    (void)x_pitch;                                    // (no decision depends on the input pitch)
+    const ConvPlan pl = conv_plan(dtype, n, cin, cout, P, Q, ks, round_up(cout, 64), (!split && y_pitch) ? y_pitch : Q, split != 0);
+    AFCM_REQUIRE(pl.items < (1ll << 31), "conv2d_plan: grid of %lld blocks is out of range", pl.items);
+    out[0] = pl.family; out[1] = pl.rows; out[2] = pl.TH; out[3] = pl.TW; out[4] = (int32_t)pl.items; out[5] = (int32_t)pl.grid;
+    out[6] = pl.fast ? 1 : 0; out[7] = pl.kernel;
+    return AFCM_OK;
 }

@@ -1128,6 +1128,58 @@ extern "C" int afcm_conv2d_wgrad(float* dw, float* workspace, const void* dy, co
     return afcm_conv2d_wgrad_ld(dw, workspace, dy, x, dtype, n, cin, cout, h, w, ks, pad, 0, 0, stream);
 }
 
+// Which weight-gradient kernel a call takes and how its K range is cut: the ONE place where wgrad_impl decides it, and what
+// afcm_conv2d_wgrad_plan reports.
+enum { kWgF32 = 0, kWgDword = 1, kWgGranule = 2 };
+enum { kWgReduceScalar = 0, kWgReduce4x256 = 1, kWgReduce4x64 = 2, kWgReduce4x16 = 3, kWgReduceDots = 4 };
+struct WgradPlan {
+    int kernel;             // kWg*
+    int pad_odd;            // XOFF of the fp32 and dword kernels (pad & 1)
+    bool x16;               // granule kernel: the 16x16x32 MFMA form (else 32x32x16)
+    bool small;             // granule kernel: one descriptor per tensor (both below 2 GB)
+    int qchunks, rowgroups;
+    int splits, steps_per_split, splits_img;
+    int reduce;             // kWgReduce* (for 16-byte aligned dw / workspace; others take the scalar kernel)
+};
+
+// AFCM_OK, or AFCM_E_NOKERNEL when `dots` asks for image-aligned shares that this shape does not have
+static int wgrad_plan(WgradPlan* pl, int dtype, int n, int cin, int cout, int h, int ldx, int ks, int pad, int P, int Q, int lddy, bool dots) {
+    const int R = wgrad_rows_per_step(dtype);
+    pl->qchunks = cdiv(Q, kWgKQ);
+    pl->rowgroups = cdiv(P, R);
+    const long long ksteps = (long long)n * pl->rowgroups * pl->qchunks;
+    const bool granule = (ks == 3 && pad == 2) || (ks == 1 && pad == 0);     // 16-byte LDS-DMA pieces; other paddings: 4-byte pieces
+    // (16-bit convs that are not granule ones are 3x3 with pad 0 or 1: a 1x1 conv has pad 0)
+    pl->kernel = dtype == AFCM_F32 ? kWgF32 : granule ? kWgGranule : kWgDword;
+    pl->pad_odd = (ks == 3) ? (pad & 1) : 0;
+    pl->splits = wgrad_splits(n, cout, cin, P);
+    if (pl->splits > ksteps) pl->splits = (int)ksteps;
+    pl->steps_per_split = (int)((ksteps + pl->splits - 1) / pl->splits);
+    pl->splits_img = 0;
+    if (dots) {
+        // image-aligned shares: the same number of workgroups, each inside one image (the granule kernel, a split count that is a
+        // multiple of the batch, at most 64 images: what wgrad_reduce_dots_kernel covers) -- else the caller takes its dot products
+        // from the tensors themselves
+        if (pl->kernel != kWgGranule || n > 64 || pl->splits % n != 0 || pl->splits / n < 1) return AFCM_E_NOKERNEL;
+        pl->splits_img = pl->splits / n;
+        const long long per_img = (long long)pl->rowgroups * pl->qchunks;
+        pl->steps_per_split = (int)((per_img + pl->splits_img - 1) / pl->splits_img);
+    }
+    // MFMA shape (template flag X16; profiles/r05_conv_shape_ab.txt): 16x16x32 holds a higher clock on the large layers (+3 .. 6 %), but its K
+    // step is 32 pixels where the 32x32x16 form skips dead 16-pixel groups: rows whose last 64-pixel chunk holds 33 .. 48 pixels (the 38-wide
+    // planes of the 36^2 layers) cost it a whole extra step (-12 % there) -- those keep the 32x32x16 form.
+    const int q_last = Q % 64;
+    pl->x16 = !(q_last > 32 && q_last <= 48);
+    // tensors below 2 GB: one descriptor per tensor; larger ones: a descriptor per LDS-DMA piece (the general form)
+    pl->small = (long long)n * cout * P * lddy * 2 < (1ll << 31) - 65536 &&
+                (long long)n * cin * h * ldx * 2 < (1ll << 31) - 65536;
+    const long long numel = (long long)cout * cin * ks * ks;
+    if (pl->splits_img > 0) pl->reduce = kWgReduceDots;
+    else if ((numel & 3) != 0) pl->reduce = kWgReduceScalar;
+    else pl->reduce = pl->splits >= 64 ? kWgReduce4x16 : pl->splits >= 8 ? kWgReduce4x64 : kWgReduce4x256;
+    return AFCM_OK;
+}
+
 static int wgrad_impl(float* dw, float* workspace, const void* dy, const void* x, int32_t dtype, int32_t n, int32_t cin,
                       int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t dy_pitch, int32_t x_pitch, float* dots, const float* wref, void* stream) {
     AFCM_REQUIRE(dw != nullptr && workspace != nullptr && dy != nullptr && x != nullptr, "conv2d_wgrad: null pointer");
@@ -1143,51 +1195,30 @@ static int wgrad_impl(float* dw, float* workspace, const void* dy, const void* x
     p.lddy = dy_pitch ? dy_pitch : p.Q; p.ldx = x_pitch ? x_pitch : w;
     const bool pitched = p.lddy != p.Q || p.ldx != w;
     AFCM_REQUIRE(!pitched || (p.lddy >= p.Q && p.ldx >= w && ((p.lddy | p.ldx) & 1) == 0), "conv2d_wgrad: row pitches %d / %d must be even and cover the widths %d / %d", p.lddy, p.ldx, p.Q, w);
-    const int R = wgrad_rows_per_step(dtype);
-    p.qchunks = cdiv(p.Q, kWgKQ);
-    p.rowgroups = cdiv(p.P, R);
-    const long long ksteps = (long long)n * p.rowgroups * p.qchunks;
-    const bool granule = (ks == 3 && pad == 2) || (ks == 1 && pad == 0);     // 16-byte LDS-DMA pieces; other paddings: 4-byte pieces
-    p.splits = wgrad_splits(n, cout, cin, p.P);
-    if (p.splits > ksteps) p.splits = (int)ksteps;
-    p.steps_per_split = (int)((ksteps + p.splits - 1) / p.splits);
-    p.splits_img = 0;
-    if (dots != nullptr) {
-        // image-aligned shares: the same number of workgroups, each inside one image (the granule kernel, a split count that is a
-        // multiple of the batch, at most 64 images: what wgrad_reduce_dots_kernel covers) -- else the caller takes its dot products
-        // from the tensors themselves
-        if (!(dtype != AFCM_F32 && granule) || n > 64 || p.splits % n != 0 || p.splits / n < 1) return AFCM_E_NOKERNEL;
-        AFCM_REQUIRE(wref != nullptr, "conv2d_wgrad_dots: the weight tensor the dot products are taken with is missing");
-        p.splits_img = p.splits / n;
-        const long long per_img = (long long)p.rowgroups * p.qchunks;
-        p.steps_per_split = (int)((per_img + p.splits_img - 1) / p.splits_img);
-    }
+    WgradPlan pl;
+    if (wgrad_plan(&pl, dtype, n, cin, cout, h, p.ldx, ks, pad, p.P, p.Q, p.lddy, dots != nullptr) != AFCM_OK) return AFCM_E_NOKERNEL;
+    AFCM_REQUIRE(dots == nullptr || wref != nullptr, "conv2d_wgrad_dots: the weight tensor the dot products are taken with is missing");
+    p.qchunks = pl.qchunks; p.rowgroups = pl.rowgroups;
+    p.splits = pl.splits; p.steps_per_split = pl.steps_per_split; p.splits_img = pl.splits_img;
+    const bool granule = pl.kernel == kWgGranule;
+    const bool wg_x16 = pl.x16, small = pl.small;
     const long long blocks = (long long)cdiv(cout, 64) * cdiv(cin, 64) * p.splits;
     dim3 grid((unsigned)blocks), block(512);
     hipStream_t st = (hipStream_t)stream;
-    // (16-bit convs that are not granule ones are 3x3 with pad 0 or 1: a 1x1 conv has pad 0)
 #define AFCM_WG16(T) do { constexpr int NB = 3; \
-                           if ((pad & 1) == 0) hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 3, 0, NB>), grid, block, 0, st, p); \
+                           if (pl.pad_odd == 0) hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 3, 0, NB>), grid, block, 0, st, p); \
                            else hipLaunchKernelGGL((conv2d_wgrad16_kernel<T, 3, 1, NB>), grid, block, 0, st, p); } while (0)
 #define AFCM_WG16G_(T, X) do { constexpr int NB = kWgradRing; \
                             if (small && ks == 3) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 3, NB, true, X>), grid, block, 0, st, p); \
                             else if (small) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 1, NB, true, X>), grid, block, 0, st, p); \
                             else if (ks == 3) hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 3, NB, false, X>), grid, block, 0, st, p); \
                             else hipLaunchKernelGGL((conv2d_wgrad16g_kernel<T, 1, NB, false, X>), grid, block, 0, st, p); } while (0)
-    // MFMA shape (template flag X16; profiles/r05_conv_shape_ab.txt): 16x16x32 holds a higher clock on the large layers (+3 .. 6 %), but its K
-    // step is 32 pixels where the 32x32x16 form skips dead 16-pixel groups: rows whose last 64-pixel chunk holds 33 .. 48 pixels (the 38-wide
-    // planes of the 36^2 layers) cost it a whole extra step (-12 % there) -- those keep the 32x32x16 form.
-    const int q_last = p.Q % 64;
-    const bool wg_x16 = !(q_last > 32 && q_last <= 48);
 #define AFCM_WG16G(T) do { if (wg_x16) AFCM_WG16G_(T, true); else AFCM_WG16G_(T, false); } while (0)
-    // tensors below 2 GB: one descriptor per tensor; larger ones: a descriptor per LDS-DMA piece (the general form)
-    const bool small = (long long)n * cout * p.P * p.lddy * 2 < (1ll << 31) - 65536 &&
-                       (long long)n * cin * h * p.ldx * 2 < (1ll << 31) - 65536;
     // rows by pitch: the 16-byte LDS-DMA kernel only (a granule straddling x's right edge is zeroed in LDS whatever follows it)
     AFCM_REQUIRE(!pitched || (dtype != AFCM_F32 && granule), "conv2d_wgrad: row pitches need the 16-bit granule kernel (3x3 pad 2 or 1x1 pad 0)");
     switch (dtype) {
         case AFCM_F32:
-            if (ks == 3 && (pad & 1) == 0) hipLaunchKernelGGL((conv2d_wgrad_kernel<3, 0>), grid, block, 0, st, p);
+            if (ks == 3 && pl.pad_odd == 0) hipLaunchKernelGGL((conv2d_wgrad_kernel<3, 0>), grid, block, 0, st, p);
             else if (ks == 3) hipLaunchKernelGGL((conv2d_wgrad_kernel<3, 1>), grid, block, 0, st, p);
             else hipLaunchKernelGGL((conv2d_wgrad_kernel<1, 0>), grid, block, 0, st, p);
             break;
@@ -1212,10 +1243,10 @@ static int wgrad_impl(float* dw, float* workspace, const void* dy, const void* x
     long long rb = (numel + 255) / 256;
     if (rb > 2048) rb = 2048;
     // splits beyond the last populated one were never launched with work: they still wrote zeros (acc = 0)
-    if ((numel & 3) == 0 && (((uintptr_t)dw | (uintptr_t)workspace) & 15) == 0) {
+    if (pl.reduce != kWgReduceScalar && (((uintptr_t)dw | (uintptr_t)workspace) & 15) == 0) {
         const long long n4 = numel / 4;
-        if (p.splits >= 64) hipLaunchKernelGGL(wgrad_reduce4_kernel<16>, dim3((unsigned)cdiv(n4, 16)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
-        else if (p.splits >= 8) hipLaunchKernelGGL(wgrad_reduce4_kernel<64>, dim3((unsigned)cdiv(n4, 64)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
+        if (pl.reduce == kWgReduce4x16) hipLaunchKernelGGL(wgrad_reduce4_kernel<16>, dim3((unsigned)cdiv(n4, 16)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
+        else if (pl.reduce == kWgReduce4x64) hipLaunchKernelGGL(wgrad_reduce4_kernel<64>, dim3((unsigned)cdiv(n4, 64)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
         else hipLaunchKernelGGL(wgrad_reduce4_kernel<256>, dim3((unsigned)cdiv(n4, 256)), dim3(256), 0, st, dw, (const float*)workspace, n4, slabs);
     } else {
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, dw, (const float*)workspace, numel, slabs);
@@ -1233,4 +1264,22 @@ extern "C" int afcm_conv2d_wgrad_dots_ld(float* dw, float* dots, float* workspac
                                          int32_t x_pitch, void* stream) {
     AFCM_REQUIRE(dots != nullptr, "conv2d_wgrad_dots: dots must be non-null");
     return wgrad_impl(dw, workspace, dy, x, dtype, n, cin, cout, h, w, ks, pad, dy_pitch, x_pitch, dots, wref, stream);
+}
+
+// Pure host: the plan afcm_conv2d_wgrad_ld (dots == 0) / afcm_conv2d_wgrad_dots_ld (dots != 0) follow for these arguments
+extern "C" int afcm_conv2d_wgrad_plan(int32_t dtype, int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad,
+                                      int32_t dy_pitch, int32_t x_pitch, int32_t dots, int32_t out[8]) {
+    AFCM_REQUIRE(out != nullptr, "conv2d_wgrad_plan: null pointer");
+    AFCM_REQUIRE(dtype == AFCM_F32 || dtype == AFCM_F16 || dtype == AFCM_BF16, "x must be float32, float16 or bfloat16");
+    AFCM_REQUIRE(n > 0 && cin > 0 && cout > 0 && h > 0 && w > 0, "x is empty");
+    AFCM_REQUIRE(ks == 1 || ks == 3, "only 1x1 and 3x3 kernels are supported");
+    AFCM_REQUIRE(pad >= 0 && pad <= ks - 1, "padding must be in [0, k-1]");
+    const int P = h + 2 * pad - ks + 1, Q = w + 2 * pad - ks + 1;
+    AFCM_REQUIRE(P >= 1 && Q >= 1, "output must be at least 1x1");
+    WgradPlan pl;
+    const int rc = wgrad_plan(&pl, dtype, n, cin, cout, h, x_pitch ? x_pitch : w, ks, pad, P, Q, dy_pitch ? dy_pitch : Q, dots != 0);
+    if (rc != AFCM_OK) return rc;
+    out[0] = pl.kernel; out[1] = pl.pad_odd; out[2] = pl.x16 ? 1 : 0; out[3] = pl.small ? 1 : 0; out[4] = pl.splits; out[5] = pl.steps_per_split;
+    out[6] = pl.reduce; out[7] = pl.splits_img;
+    return AFCM_OK;
 }

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define AFCM_ABI_VERSION 13  /* 13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
+#define AFCM_ABI_VERSION 13  /* 13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
 
 enum { AFCM_F32 = 0, AFCM_F16 = 1, AFCM_BF16 = 2 };
 enum { AFCM_OK = 0, AFCM_E_NOKERNEL = -1, AFCM_E_INVALID = -2 };
@@ -213,6 +213,18 @@ int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const float* osc
                    int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t rows_pad, int32_t x_pitch,
                    int32_t y_pitch, void* stream);
 
+/* Pure host (no device memory, works without a GPU): which kernel afcm_conv2d_ld (split == 0) or afcm_conv2d_split (split != 0: dtype is
+ * the parts' type, ks 3) runs for these arguments with rows_pad = cout rounded up to 64, from the function both entry points dispatch
+ * through.  out[0] family: 0 direct (cin <= 4), 1 96-row blocks, 2 128-row blocks + one 64-row block, 3 64-row blocks, 4 128-row blocks;
+ * out[1] rows per block of the launch that out[4] / out[5] describe (family 2: its 64-row launch; the 128-row launch in front of it
+ * takes one work item per workgroup); out[2], out[3] output tile TH x TW (0 for the direct kernel, whose tile is fixed);
+ * out[4] work items (tiles x images x row blocks); out[5] workgroups -- fewer than out[4] when a persistent launch (64-row and 96-row
+ * 16-bit 3x3) takes more than one round: one round is 3 (2 for 96 rows) workgroups per compute unit of the current device, 256 units
+ * when there is no device; out[6] 1: the 16-byte transposed ("fast") epilogue; out[7] kernel: 0 conv2d_fwd16x (16-bit 3x3), 1 the
+ * general 16-bit kernel (1x1), 2 the fp32 kernel, 3 direct, 4 conv2d_fwd16x on split operands. */
+int afcm_conv2d_plan(int32_t dtype, int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t x_pitch,
+                     int32_t y_pitch, int32_t split, int32_t out[8]);
+
 /* Weight gradient dw[cout][cin][k][k] (fp32) = sum_n sum_pixels dy[n,o,p,q] * x[n,i,p+r-pad,q+s-pad].
  * workspace: fp32 [afcm_conv2d_wgrad_splits(...)][cout][cin][k][k]. */
 int afcm_conv2d_wgrad_splits(int32_t n, int32_t cout, int32_t cin, int32_t p_rows);
@@ -232,6 +244,15 @@ int afcm_conv2d_wgrad_ld(float* dw, float* workspace, const void* dy, const void
 int afcm_conv2d_wgrad_dots_ld(float* dw, float* dots, float* workspace, const void* dy, const void* x, const float* wref, int32_t dtype, int32_t n,
                               int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t dy_pitch, int32_t x_pitch,
                               void* stream);
+
+/* Pure host: the plan of afcm_conv2d_wgrad_ld (dots == 0) or afcm_conv2d_wgrad_dots_ld (dots != 0; AFCM_E_NOKERNEL where that one declines).
+ * out[0] kernel: 0 fp32, 1 16-bit with 4-byte LDS-DMA pieces (3x3 pad 0 / 1), 2 16-bit granule kernel (3x3 pad 2, 1x1 pad 0); out[1] pad
+ * parity of kernels 0 and 1; out[2] granule kernel: 1 the 16x16x32 MFMA form, 0 the 32x32x16 one; out[3] granule kernel: 1 one descriptor
+ * per tensor (both operands below 2 GB); out[4] split count (slabs written); out[5] K macro-steps per split; out[6] the reduction:
+ * 0 scalar (k*k*cout*cin not a multiple of 4), 1 / 2 / 3 the 16-byte one with 256 / 64 / 16 columns per workgroup (splits < 8, 8..63,
+ * >= 64), 4 the image-aligned one that also writes dots; out[7] splits per image (dots) or 0. */
+int afcm_conv2d_wgrad_plan(int32_t dtype, int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad,
+                           int32_t dy_pitch, int32_t x_pitch, int32_t dots, int32_t out[8]);
 
 /* y[plane, :] = x[plane, :] * scale[plane] with dtype conversion (style modulation s[n,i] of NET:46-47 and the
  * demodulation d[n,o] of NET:50-52 applied to activations instead of weights).  scale may be NULL (pure cast). */

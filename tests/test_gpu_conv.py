@@ -1,8 +1,11 @@
 """GPU parity tests of the MFMA convolution path (forward, data gradient, weight gradient, style and
 demodulation gradients) against the CPU oracle and the reference's golden vectors.
 
-fp32 path: the contraction runs on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate), so only the
-summation order differs from aten: tolerance 1e-4 x scale (north-star bar: 1e-3 max-abs).
+fp32 path: 3x3 convs of even width take the split-operand route by default (conv2d.FP32_SPLIT: float16 parts on the 16-bit matrix
+pipe, fp32 accumulate, measured equal to an fp32 dot product of the same length); odd widths, oversize parts, 1x1 kernels and
+FP32_SPLIT = None run the native kernels on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32 accumulate).  Either way only the
+summation order differs from aten: tolerance 1e-4 x scale (north-star bar: 1e-3 max-abs).  Both routes are held to exact integer
+arithmetic in test_gpu_conv_exact.py.
 bf16/f16 path: operands rounded to 16 bit, fp32 accumulate; compared with the fp32 oracle at 2e-2 x scale.
 """
 import numpy as np
