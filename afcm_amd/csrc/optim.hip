@@ -20,13 +20,15 @@ __device__ __forceinline__ float scrub(float g, float posinf, float neginf) {
 
 __global__ __launch_bounds__(256) void adam_multi_kernel(const afcm_adam_entry* __restrict__ table, int n, float step_size, float beta1,
                                                          float beta2, float w1, float w2, float bc2_sqrt, float eps, float grad_scale, int do_scrub,
-                                                         float posinf, float neginf, int write_grad, const float* __restrict__ step_dev, float lr) {
+                                                         float posinf, float neginf, int write_grad, const float* __restrict__ step_dev, double lr,
+                                                         double beta1_d, double beta2_d) {
     // capturable form (step_dev != NULL): the step count lives on the device (adam_step_inc_kernel advances it), the bias corrections are
-    // formed here -- a launch captured into a hipGraph then replays with the right corrections at every step
+    // formed here, in double from the betas in double as the host forms them for afcm_adam_multi -- a launch captured into a hipGraph then
+    // replays with the right corrections at every step
     if (step_dev != nullptr) {
         const double t = (double)step_dev[0];
-        const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-        step_size = (float)((double)lr / bc1);
+        const double bc1 = 1.0 - pow(beta1_d, t), bc2 = 1.0 - pow(beta2_d, t);
+        step_size = (float)(lr / bc1);
         bc2_sqrt = (float)sqrt(bc2);
     }
     // which tensor does this chunk belong to: binary search over the chunk prefix (wave-uniform)
@@ -47,8 +49,9 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const afcm_adam_entry* 
         float gr = gg * grad_scale;
         if (do_scrub) gr = scrub(gr, posinf, neginf);
         gg = gr;
-        // torch.lerp(m, g, 1 - beta1)
-        mm = (w1 < 0.5f) ? mm + w1 * (gr - mm) : gr - (gr - mm) * (1.f - w1);
+        // torch.lerp(m, g, 1 - beta1), with the product fused into the sum as torch's kernels have it: where m and w1 * (g - m) nearly cancel, a
+        // rounded product leaves an error of half an ulp of the PRODUCT in a much smaller m (seen at 4.6 ulp of m against float64)
+        mm = (w1 < 0.5f) ? __builtin_fmaf(w1, gr - mm, mm) : __builtin_fmaf(-(gr - mm), 1.f - w1, gr);
         vv = vv * beta2 + (w2 * gr) * gr;
         const float denom = sqrtf(vv) / bc2_sqrt + eps;
         pp = pp + (-step_size) * (mm / denom);
@@ -58,9 +61,10 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const afcm_adam_entry* 
         for (long long i = base + 4 * threadIdx.x; i < end; i += 4 * 256) {
             if (i + 4 <= end) {
                 // (beta1 = 0, the reference's setting: the first moment is the scrubbed gradient itself -- lerp(m, g, 1) = g for every finite m,
-                // and m is finite: it is a scrubbed gradient -- so its old value is not read: 234 of the step's 1,638 MB)
+                // and m is finite: it is a scrubbed gradient -- so its old value is not read: 234 of the step's 1,638 MB.  Without the scrub
+                // m may be inf or NaN, which lerp keeps as NaN: then it is read, as the scalar loops below read it)
                 float4 pp = *(float4*)(p + i), gg = *(const float4*)(g + i), vv = *(float4*)(v + i);
-                float4 mm = w1 == 1.f ? make_float4(0.f, 0.f, 0.f, 0.f) : *(float4*)(m + i);
+                float4 mm = (w1 == 1.f && do_scrub) ? make_float4(0.f, 0.f, 0.f, 0.f) : *(float4*)(m + i);
                 update(pp.x, gg.x, mm.x, vv.x); update(pp.y, gg.y, mm.y, vv.y);
                 update(pp.z, gg.z, mm.z, vv.z); update(pp.w, gg.w, mm.w, vv.w);
                 *(float4*)(p + i) = pp; *(float4*)(m + i) = mm; *(float4*)(v + i) = vv;
@@ -97,22 +101,39 @@ extern "C" int afcm_adam_multi(const afcm_adam_entry* table_dev, int32_t n, int6
     AFCM_REQUIRE(bias_correction2_sqrt > 0.f, "adam_multi: bias_correction2_sqrt must be positive");
     hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, n, step_size, beta1,
                        beta2, one_minus_beta1, one_minus_beta2, bias_correction2_sqrt, eps, grad_scale, scrub, posinf, neginf, write_grad,
-                       (const float*)nullptr, 0.f);
+                       (const float*)nullptr, 0.0, 0.0, 0.0);
     return hip_status(hipGetLastError());
 }
 
 namespace afcm { __global__ void adam_step_inc_kernel(float* step) { step[0] += 1.f; } }
 
+namespace afcm {
+static int adam_multi_capturable(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, double lr, double beta1, double beta2,
+                                 float w1, float w2, float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad, void* stream) {
+    AFCM_REQUIRE(table_dev != nullptr && n > 0 && step_dev != nullptr, "adam_multi_capturable: empty table or no step counter");
+    AFCM_REQUIRE(total_chunks > 0 && total_chunks < (1ll << 31), "adam_multi: %lld chunks is out of range", (long long)total_chunks);
+    AFCM_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_multi_capturable: betas must lie in [0, 1)");
+    hipLaunchKernelGGL(adam_step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
+    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, n, 0.f, (float)beta1,
+                       (float)beta2, w1, w2, 1.f, eps, grad_scale, scrub, posinf, neginf, write_grad, (const float*)step_dev, lr, beta1, beta2);
+    return hip_status(hipGetLastError());
+}
+}  // namespace afcm
+
+// (lr and the betas arrive as floats: 1 - beta is all this entry point can form, and 1.f - 0.999f is 1.7e-5 away from 0.001 -- the moments
+// then follow an Adam whose beta2 is the rounded one.  afcm_adam_multi_capturable_d takes doubles and is what afcm_amd calls.)
 extern "C" int afcm_adam_multi_capturable(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, float lr, float beta1,
                                           float beta2, float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad,
                                           void* stream) {
-    using namespace afcm;
-    AFCM_REQUIRE(table_dev != nullptr && n > 0 && step_dev != nullptr, "adam_multi_capturable: empty table or no step counter");
-    AFCM_REQUIRE(total_chunks > 0 && total_chunks < (1ll << 31), "adam_multi: %lld chunks is out of range", (long long)total_chunks);
-    hipLaunchKernelGGL(adam_step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, n, 0.f, beta1,
-                       beta2, 1.f - beta1, 1.f - beta2, 1.f, eps, grad_scale, scrub, posinf, neginf, write_grad, (const float*)step_dev, lr);
-    return hip_status(hipGetLastError());
+    return afcm::adam_multi_capturable(table_dev, n, total_chunks, step_dev, (double)lr, (double)beta1, (double)beta2, 1.f - beta1, 1.f - beta2, eps, grad_scale,
+                                       scrub, posinf, neginf, write_grad, stream);
+}
+
+extern "C" int afcm_adam_multi_capturable_d(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, double lr, double beta1,
+                                            double beta2, float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad,
+                                            void* stream) {
+    return afcm::adam_multi_capturable(table_dev, n, total_chunks, step_dev, lr, beta1, beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, grad_scale,
+                                       scrub, posinf, neginf, write_grad, stream);
 }
 
 

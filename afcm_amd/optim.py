@@ -4,7 +4,8 @@ The reference's G update is ``nan_to_num`` on every gradient followed by ``torch
 (models/stylegan3_model.py:122-124,132-135; models/comodgan_model.py:19-20).  Run eagerly that is ~110 tiny launches plus
 seven multi-tensor passes over the 234 MB of parameters; here one HIP launch reads p, g, m, v and writes p, m, v once for
 every tensor.  State layout (``step``, ``exp_avg``, ``exp_avg_sq`` per parameter) and the update arithmetic are
-torch.optim.Adam's, so ``state_dict()`` round-trips with it.
+torch.optim.Adam's, so ``state_dict()`` round-trips with it -- also for a capturable optimizer whose captured step has been
+replayed: ``state_dict()`` reads the step count back from the device, ``load_state_dict()`` re-creates it from the loaded state.
 """
 import ctypes
 import math
@@ -15,6 +16,11 @@ from . import _lib
 
 
 class FusedScrubAdam(torch.optim.Optimizer):
+    """``g * grad_scale`` -> ``nan_to_num`` -> Adam, one launch per parameter group.  One step count per group (the largest in the group
+    + 1; a parameter without a gradient is left alone).  ``capturable=True`` keeps that count on the device so that ``step()`` can be
+    captured into a graph: replays advance the device count only, ``device_step()`` reads it, and ``state_dict()`` writes it into
+    ``state[p]['step']`` of the parameters the captured step updates, so a checkpoint taken after replays resumes at the right step."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, write_grad=False, capturable=False):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
             raise ValueError('invalid Adam hyper-parameters')
@@ -22,10 +28,10 @@ class FusedScrubAdam(torch.optim.Optimizer):
         self.scrub, self.posinf, self.neginf, self.write_grad = bool(scrub), float(posinf), float(neginf), bool(write_grad)
         self._tables = {}          # (group index, device) -> (rows, device table, pinned host copy)
         # capturable: the step count is a device scalar per group and the bias corrections are formed in the kernel (C ABI
-        # afcm_adam_multi_capturable), so the launch can be captured into a hipGraph and replayed (bench.py --graph); state['step'] then
-        # stays where it was at capture time -- `device_step()` is the count
+        # afcm_adam_multi_capturable_d), so the launch can be captured into a hipGraph and replayed (bench.py --graph).  Replays advance the
+        # device scalar only: `device_step()` is the count, and `state_dict()` copies it into state['step'] (see there)
         self.capturable = bool(capturable)
-        self._step_dev = {}
+        self._step_dev = {}        # (group index, device) -> the count, a float32 device scalar; made at the group's first step from state['step']
 
     def _state(self, p):
         st = self.state[p]
@@ -107,7 +113,7 @@ class FusedScrubAdam(torch.optim.Optimizer):
                 sd = self._step_dev.get(key)
                 if sd is None:
                     sd = self._step_dev[key] = torch.full([1], float(step_t - 1), dtype=torch.float32, device=dev)
-                _lib.launched(lib.afcm_adam_multi_capturable(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, ctypes.c_void_p(sd.data_ptr()), group['lr'],
+                _lib.launched(lib.afcm_adam_multi_capturable_d(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, ctypes.c_void_p(sd.data_ptr()), group['lr'],
                                                              beta1, beta2, group['eps'], float(grad_scale), int(self.scrub), self.posinf, self.neginf,
                                                              int(self.write_grad), _lib.stream_ptr(table)), 'adam_multi_capturable')
                 torch.autograd.graph.increment_version(touched)
@@ -123,6 +129,33 @@ class FusedScrubAdam(torch.optim.Optimizer):
             torch.autograd.graph.increment_version(touched)
         return loss
 
+
+    def _pull_device_steps(self):
+        """state['step'] <- the device count, for the parameters of each capturable group's current pointer table: the ones the last step
+        updated, eagerly or in the capture, and so the ones every replay updates.  One synchronising read per group."""
+        for key, sd in self._step_dev.items():
+            ent = self._tables.get(key)
+            if ent is None:
+                continue
+            count = float(sd.item())
+            stepped = {row[0] for row in ent[0]}
+            for p in self.param_groups[key[0]]['params']:
+                st = self.state.get(p)
+                if st and p.data_ptr() in stepped:
+                    st['step'].fill_(count)
+
+    def state_dict(self):
+        """torch.optim.Adam's layout.  A capturable optimizer first brings state['step'] up to the device count, which replays of a captured
+        step advance without the host: the checkpoint, and the optimizer itself from here on, carry the number of steps that ran."""
+        self._pull_device_steps()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        """The next step starts from the loaded state: the device count is made anew from the loaded state['step'], the pointer tables from
+        the loaded moments.  A graph captured before the load still points at the old ones: capture again."""
+        super().load_state_dict(state_dict)
+        self._step_dev = {}
+        self._tables = {}
 
     def device_step(self, group=0):
         """The step count of a capturable optimizer (a device scalar; reading it synchronises)."""

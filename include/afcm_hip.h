@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define AFCM_ABI_VERSION 13  /* 13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
+#define AFCM_ABI_VERSION 13  /* 13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
 
 enum { AFCM_F32 = 0, AFCM_F16 = 1, AFCM_BF16 = 2 };
 enum { AFCM_OK = 0, AFCM_E_NOKERNEL = -1, AFCM_E_INVALID = -2 };
@@ -333,6 +333,11 @@ int afcm_adam_multi(const afcm_adam_entry* table, int32_t n, int64_t total_chunk
  * `lr` is the plain learning rate.  Same update arithmetic otherwise. */
 int afcm_adam_multi_capturable(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, float lr, float beta1, float beta2,
                                float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad, void* stream);
+/* The same with lr and the betas in double: one_minus_beta* = (float)(1.0 - beta*) and the bias corrections come from the betas as given, as
+ * in afcm_adam_multi, so m and v agree with it (and with torch) to the last bit or two.  The float entry point above can only form
+ * 1.f - beta*, which moves exp_avg_sq by 1.7e-5 relative at beta2 = 0.999 and by 9e-7 at 0.99; it stays for its callers. */
+int afcm_adam_multi_capturable_d(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, double lr, double beta1, double beta2,
+                                 float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The style affine layers of all SynthesisLayers at once (NET:349-352 `styles = self.affine(cat(w, global_w))`, FullyConnectedLayer
