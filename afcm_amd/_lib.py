@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get('AFCM_HIP_LIB') or os.path.join(_HERE, 'libafcm_hip.so
 F32, F16, BF16 = 0, 1, 2
 E_NOKERNEL, E_INVALID = -1, -2
 SIGNS_NONE, SIGNS_WRITE, SIGNS_READ = 0, 1, 2
+SRC_U8, SRC_I16, SRC_F32, SRC_F64 = 0, 1, 2, 3
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
@@ -137,6 +138,8 @@ SIGNATURES = {
     'afcm_adam_multi_capturable_d': (C.c_int, [_vp, _i32, _i64, _vp, C.c_double, C.c_double, C.c_double, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
     'afcm_plane_metrics_workspace_bytes': (C.c_int64, [_i64, _i32, _i32]),
     'afcm_plane_metrics': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _vp]),
+    'afcm_slice_assemble': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _vp]),
+    'afcm_halo_accumulate': (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _i32] + [_i32] * 17 + [_vp]),
 }
 
 

@@ -68,6 +68,14 @@ class StyleGAN3GeneratorStep:
         self.gen_z = torch.randn([real_A.shape[0], self.netG.z_dim], device=dev) if gen_z is None else gen_z.to(dev)
         self.gen_c = gen_c.to(dev) if gen_c is not None else torch.zeros([real_A.shape[0], self.netG.c_dim], device=dev)
 
+    def set_test_input(self, real_A, slice_idx):
+        """models/pix2pix_model.py:115-117 + models/comodgan_model.py:101-108: the test loader's item -- a fresh ``gen_z``, the label from
+        ``slice_idx`` [B, 1] (zeros for an unconditional generator); ``real_B`` is left as it is, as in the reference."""
+        dev = next(self.netG.parameters()).device
+        self.real_A = real_A.to(dev)
+        self.gen_z = torch.randn([real_A.shape[0], self.netG.z_dim], device=dev)
+        self.gen_c = slice_idx.to(dev) if self.netG.c_dim > 0 else torch.zeros([real_A.shape[0], 1], device=dev)
+
     def run_G(self, cond_img, update_emas=False, noise_mode='random'):
         ref_img = self.real_B
         ws = self.G_mapping(z=self.gen_z, c=self.gen_c, img_in=ref_img, update_emas=False)

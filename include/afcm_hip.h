@@ -21,8 +21,9 @@
  *     falls back to the generic upfirdn2d + act path); AFCM_E_INVALID (-2) = argument check
  *     failed (the reference's TORCH_CHECK); >= 1000 = 1000 + hipError_t of the launch.
  *   - dtype codes: AFCM_F32, AFCM_F16, AFCM_BF16 (bf16 is new capability; the reference
- *     plugin accepts half/float only).  Arithmetic is always fp32 inside the kernels, with ONE exception:
- *     afcm_plane_metrics (validation metrics, end of this header) computes in float64 after its loads.
+ *     plugin accepts half/float only).  Arithmetic is always fp32 inside the kernels, with TWO exceptions:
+ *     afcm_plane_metrics (validation metrics, end of this header) computes in float64 after its loads; afcm_slice_assemble
+ *     (after it) normalises in the type numpy gives the loader's expression, float64 for every source but float32.
  */
 #ifndef AFCM_HIP_H
 #define AFCM_HIP_H
@@ -33,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AFCM_ABI_VERSION 13  /* 13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
+#define AFCM_ABI_VERSION 13  /* 13: + afcm_slice_assemble, afcm_halo_accumulate (whole-volume inference; additions only, so the number stays).  13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
 
 enum { AFCM_F32 = 0, AFCM_F16 = 1, AFCM_BF16 = 2 };
 enum { AFCM_OK = 0, AFCM_E_NOKERNEL = -1, AFCM_E_INVALID = -2 };
@@ -536,6 +537,53 @@ int64_t afcm_plane_metrics_workspace_bytes(int64_t planes, int32_t h, int32_t w)
 int afcm_plane_metrics(double* table, const void* ref, const void* test, int32_t dtype_ref, int32_t dtype_test, int64_t planes, int32_t h, int32_t w,
                        int64_t ref_stride_plane, int64_t ref_stride_row, int64_t ref_stride_col, int64_t test_stride_plane, int64_t test_stride_row,
                        int64_t test_stride_col, int32_t unit_map, double c1, double c2, void* workspace, void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Whole-volume inference (r08): the two ends of the reference's volume loop (evaluate.py -> StandardPredictor.__call__, models/predictor.py:106-202)
+ * on the device -- the loader's item for a run of target slices, and the halo-cropped accumulation of a batch of predictions.  Both validate on
+ * the host (AFCM_E_INVALID before any launch), launch on `stream`, never synchronise, use no atomics and form every volume offset in 64 bits.
+ * ---------------------------------------------------------------------------------------- */
+enum { AFCM_SRC_U8 = 0, AFCM_SRC_I16 = 1, AFCM_SRC_F32 = 2, AFCM_SRC_F64 = 3 };
+
+/* data/cmsr_dataset.py:98-155 (__getitem__ of the test phase) behind transforms.py:250-275 (CropToFixed, centred) and :609-616 (Normalize), for the
+ * target slices [first, first + count) of ONE source volume src [depth][hs][ws] of src_dtype (AFCM_SRC_*): element (z, y, x) at
+ * z * src_stride_z + y * ws + x ELEMENTS (rows contiguous, any stride in z).  Writes a [count][k][h][w] of out_dtype (AFCM_F32 / F16 / BF16, contiguous)
+ * and slice_idx [count] float32.
+ *   planes   k = 4: source slices idx_a - t, idx_a, idx_a + t, idx_a + 2t with idx_a = (idx / t) * t, t = thickness >= 1; k = 1: slice idx itself.
+ *            A position outside [0, depth - 1] is a plane of float64 zeros BEFORE normalisation.
+ *   crop/pad per axis: want < have reads from offset (have - want) / 2; otherwise (want - have) / 2 pixels of padding before and the rest after.
+ *            A padded pixel is a zero OF THE SOURCE DTYPE before normalisation.
+ *   value    clip(2 * ((m - min) / (max - min)) - 1, -1, 1), each operation rounded on its own, in the type numpy gives the expression: float64 for
+ *            u8 / i16 / f64 sources and for the zero planes, FLOAT32 for an f32 source (numpy keeps the array's type against Python scalars:
+ *            min and max - min are rounded to float32 first).  Then one rounding to float32, and one more to a 16-bit out_dtype.
+ *   label    slice_idx[i] = float32(idx - idx_a) / float32(thickness), one IEEE division (k = 1: idx_a = idx; the loader's "no thickness" is
+ *            thickness = -1, which gives -0.0f).
+ * One thread per output element, consecutive lanes along x.  AFCM_E_INVALID: null pointers, unknown dtypes, depth / hs / ws / h / w < 1, a slice
+ * range outside [0, depth], k not 1 or 4, thickness 0 (or < 1 with k = 4), src_stride_z < 0, max_value <= min_value, more than 2^31 - 1 workgroups. */
+int afcm_slice_assemble(void* a, float* slice_idx, const void* src, int32_t src_dtype, int32_t out_dtype, int32_t depth, int32_t hs, int32_t ws,
+                        int64_t src_stride_z, int32_t first, int32_t count, int32_t k, int32_t thickness, int32_t h, int32_t w, double min_value,
+                        double max_value, void* stream);
+
+/* The per-batch body of StandardPredictor.__call__ (models/predictor.py:173-200) with remove_halo (:17-51): for the patches
+ * [first, first + count) of the DEVICE table origins [table_len][3] int32 (z, y, x of each patch's first voxel), add sample i of
+ * pred [count][channels][pd][ph][pw] (dtype AFCM_F32 / F16 / BF16, element (i, c, z, y, x) at i * stride_b + c * stride_c + z * stride_d + y * stride_h +
+ * x * stride_w ELEMENTS: read as it lies) into map [map_channels][D][H][W] float32 and add 1 to mask (same shape, uint8, wraps at 256 as numpy's does).
+ * prediction_channel >= 0: map_channels = 1 and that channel of pred is the source; -1: map channel c takes pred channel c (channels = map_channels).
+ * Crop per axis, patch [o, o + p) in a volume of n with halo a: the covered voxels are [o + (o == 0 ? 0 : a), o + p == n ? n : o + p - a), read
+ * from patch coordinate v - o -- EXCEPT on an interior stop side with a == 0, where the reference takes patch[..., :1] and numpy broadcasts it:
+ * there every covered voxel reads patch coordinate 0 (models/predictor.py:34; reproduced, not repaired).
+ * Gather form: one thread per (map channel, voxel) of the box [z0, z1) x [y0, y1) x [x0, x1) -- any box inside the volume that contains the
+ * batch's patches; the host knows it from its own index list -- walks the patches in ASCENDING order and, for each that covers its voxel, does one
+ * float32 add and one uint8 increment in registers, then stores once.  That is the host's order (sample by sample, batches in launch order), so
+ * the map is bit-identical to the host's and the same from run to run.  A thread writes its own voxel only and reads pred only at coordinates
+ * inside the patch, whatever the table holds.  AFCM_E_INVALID: null pointers, unknown dtype, a non-positive shape, patch larger than the volume,
+ * negative halo or one above the patch extent, [first, first + count) outside the table, a box outside the volume or empty, prediction_channel outside [-1, channels),
+ * channels != map_channels without a prediction channel, map_channels != 1 with one, more than 2^31 - 1 workgroups. */
+int afcm_halo_accumulate(float* map, uint8_t* mask, const void* pred, int32_t dtype, int64_t stride_b, int64_t stride_c, int64_t stride_d,
+                         int64_t stride_h, int64_t stride_w, int32_t channels, const int32_t* origins, int32_t table_len, int32_t first, int32_t count,
+                         int32_t pd, int32_t ph, int32_t pw, int32_t halo_z, int32_t halo_y, int32_t halo_x, int32_t D, int32_t H, int32_t W,
+                         int32_t map_channels, int32_t prediction_channel, int32_t z0, int32_t z1, int32_t y0, int32_t y1, int32_t x0, int32_t x1,
+                         void* stream);
 
 #ifdef __cplusplus
 }
