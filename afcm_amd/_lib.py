@@ -138,6 +138,8 @@ SIGNATURES = {
     'afcm_adam_multi_capturable_d': (C.c_int, [_vp, _i32, _i64, _vp, C.c_double, C.c_double, C.c_double, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
     'afcm_plane_metrics_workspace_bytes': (C.c_int64, [_i64, _i32, _i32]),
     'afcm_plane_metrics': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _vp]),
+    'afcm_volume_ssim_workspace_bytes': (C.c_int64, [_i64, _i32, _i32, _i32]),
+    'afcm_volume_ssim': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i32] + [_i64] * 8 + [_i32, _f64, _f64, _vp, _vp]),
     'afcm_slice_assemble': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _vp]),
     'afcm_halo_accumulate': (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _i32] + [_i32] * 17 + [_vp]),
 }

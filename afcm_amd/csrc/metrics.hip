@@ -11,6 +11,13 @@
 // Every sum is taken in an order that depends on the shape only, so a table is bit-identical from call to call.
 // After the load (and the optional fp32 unit-range map) every operation is float64: the SSIM variance cancels against c2 = 3.6e-3 on flat
 // regions, where fp32 moments lose the digits the keep-best comparison looks at (DESIGN.md "Validation metrics").
+//
+// Volume SSIM (evaluate_3D's 7 x 7 x 7 window, util/evaluation.py:123-127): afcm_volume_ssim, the plane walk with one stage in front.  Two launches:
+//   1. volume_ssim_kernel    one workgroup per (volume, z origin, 16 x 64 tile of window origins): every thread sums the seven z-neighbours of its
+//                            voxels (x, y, xx, yy, xy; float64, straight from global memory) into LDS, then the thread-per-column walk of (2)
+//                            above over those z-sums                                                       -> workspace [volume][z origin][tile]
+//   2. volume_ssim_finish_kernel  one wave per (volume, z origin) sums that layer's partials in a fixed order -> layers [volume][d - 6]
+// Every window is a direct sum of its 343 terms (7 along z, then 7 along x, then 7 along y): no running sums, whose rounding grows with depth.
 #include "common.h"
 
 namespace afcm {
@@ -201,7 +208,101 @@ __global__ __launch_bounds__(64) void plane_finish_kernel(double* __restrict__ t
     }
 }
 
+// ---- volume SSIM: 7 x 7 x 7 window ------------------------------------------------------------------------------------------------------------
+constexpr int VS_TILE_Y = 16, VS_TILE_X = 64;           // window origins per tile: rows x columns (columns = lanes of a wave)
+constexpr int VS_LDS_Y = VS_TILE_Y + PM_APRON, VS_LDS_X = VS_TILE_X + PM_APRON;     // 5 x 22 x 70 float64 z-sums: 61.6 KB, two workgroups per CU
+constexpr int VS_ROWS_PER_WAVE = VS_TILE_Y / (PM_THREADS / 64);
+constexpr double VS_NPIX = 343.0;
+
+// A volume as pm_load reads it: `planes` has a plane stride of ONE element, so the "plane" handed to pm_load is the 64-bit element offset of
+// voxel (volume, z, 0, 0) itself, which lets the volume and z strides be arbitrary and pm_load stay as it is.
+struct volume_view {
+    plane_view planes;
+    long long stride_volume, stride_z;
+};
+
+__global__ __launch_bounds__(PM_THREADS) void volume_ssim_kernel(double* __restrict__ partials, volume_view ref, volume_view test, int layers, int h,
+                                                                 int w, int tiles_x, int tiles, int unit_map, double c1, double c2) {
+    __shared__ double zs[5][VS_LDS_Y][VS_LDS_X];
+    __shared__ double red[PM_THREADS / 64];
+    const long long layer = blockIdx.x / tiles;                                        // volume * layers + z origin
+    const int tile = blockIdx.x % tiles;
+    const long long volume = layer / layers;
+    const int z0 = (int)(layer % layers);
+    const int y0 = (tile / tiles_x) * VS_TILE_Y, x0 = (tile % tiles_x) * VS_TILE_X;
+    const int nwy = min(VS_TILE_Y, h - PM_APRON - y0), nwx = min(VS_TILE_X, w - PM_APRON - x0);    // window origins this tile owns: >= 1 each
+    const int lh = nwy + PM_APRON, lw = nwx + PM_APRON;                                // the voxels under them: all inside the volume
+    const long long rbase = volume * ref.stride_volume + z0 * ref.stride_z, tbase = volume * test.stride_volume + z0 * test.stride_z;
+
+    // stage A: the seven z-neighbours of every staged voxel, consecutive lanes along x
+    for (int i = threadIdx.x; i < lh * VS_LDS_X; i += PM_THREADS) {
+        const int y = i / VS_LDS_X, x = i % VS_LDS_X;
+        double ax = 0.0, ay = 0.0, axx = 0.0, ayy = 0.0, axy = 0.0;
+        if (x < lw) {
+#pragma unroll
+            for (int k = 0; k < PM_WIN; ++k) {
+                const double r = (double)pm_load(ref.planes, rbase + k * ref.stride_z, y0 + y, x0 + x, unit_map);
+                const double t = (double)pm_load(test.planes, tbase + k * test.stride_z, y0 + y, x0 + x, unit_map);
+                ax += r; ay += t; axx += r * r; ayy += t * t; axy += r * t;
+            }
+        }
+        zs[0][y][x] = ax; zs[1][y][x] = ay; zs[2][y][x] = axx; zs[3][y][x] = ayy; zs[4][y][x] = axy;
+    }
+    __syncthreads();
+
+    // stage B: plane_sums_kernel's column walk over the z-sums -- this wave's rows of window origins, lane = column
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int oy0 = wave * VS_ROWS_PER_WAVE;
+    double s_ssim = 0.0;
+    if (oy0 < nwy && lane < nwx) {
+        double hs[PM_WIN][5];
+        const int rows = min(VS_ROWS_PER_WAVE, nwy - oy0) + PM_APRON;                  // staged rows this wave walks: all inside lh
+        for (int base = 0; base < rows; base += PM_WIN) {
+#pragma unroll
+            for (int k = 0; k < PM_WIN; ++k) {
+                const int rr = base + k;
+                if (rr < rows) {
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) {
+                        double a = zs[q][oy0 + rr][lane];
+#pragma unroll
+                        for (int j = 1; j < PM_WIN; ++j) a += zs[q][oy0 + rr][lane + j];
+                        hs[k][q] = a;
+                    }
+                    if (rr >= PM_APRON) {
+                        double v[5];
+#pragma unroll
+                        for (int q = 0; q < 5; ++q) {
+                            double a = hs[0][q];
+#pragma unroll
+                            for (int m = 1; m < PM_WIN; ++m) a += hs[m][q];
+                            v[q] = a / VS_NPIX;
+                        }
+                        const double ux = v[0], uy = v[1];
+                        const double cov = VS_NPIX / (VS_NPIX - 1.0);                  // sample covariance
+                        const double vx = cov * (v[2] - ux * ux), vy = cov * (v[3] - uy * uy), vxy = cov * (v[4] - ux * uy);
+                        s_ssim += ((2.0 * ux * uy + c1) * (2.0 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2));
+                    }
+                }
+            }
+        }
+    }
+    s_ssim = wave_sum(s_ssim);
+    if (lane == 0) red[wave] = s_ssim;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(64) void volume_ssim_finish_kernel(double* __restrict__ out, const double* __restrict__ partials, int tiles) {
+    const double* p = partials + (long long)blockIdx.x * tiles;
+    double a = 0.0;
+    for (int k = threadIdx.x; k < tiles; k += 64) a += p[k];
+    a = wave_sum(a);
+    if (threadIdx.x == 0) out[blockIdx.x] = a;
+}
+
 static inline long long pm_tiles(int h, int w) { return (long long)cdiv(h, PM_TILE) * cdiv(w, PM_TILE); }
+static inline long long vs_tiles(int h, int w) { return (long long)cdiv(h - PM_APRON, VS_TILE_Y) * cdiv(w - PM_APRON, VS_TILE_X); }
 
 }  // namespace afcm
 
@@ -232,6 +333,35 @@ extern "C" int afcm_plane_metrics(double* table, const void* ref, const void* te
     hipLaunchKernelGGL(plane_sums_kernel, dim3((unsigned)blocks), dim3(PM_THREADS), 0, (hipStream_t)stream, sums, (const double*)ext, r, t, h, w,
                        tiles_x, (int)tiles, unit_map, c1, c2);
     hipLaunchKernelGGL(plane_finish_kernel, dim3((unsigned)planes), dim3(64), 0, (hipStream_t)stream, table, (const double*)ext, (const double*)sums,
+                       (int)tiles);
+    return hip_status(hipGetLastError());
+}
+
+extern "C" int64_t afcm_volume_ssim_workspace_bytes(int64_t volumes, int32_t d, int32_t h, int32_t w) {
+    if (volumes <= 0 || d < afcm::PM_WIN || h < afcm::PM_WIN || w < afcm::PM_WIN) return 0;
+    return volumes * (d - afcm::PM_APRON) * afcm::vs_tiles(h, w) * (int64_t)sizeof(double);       // [volume][z origin][tile]
+}
+
+extern "C" int afcm_volume_ssim(double* layers, const void* ref, const void* test, int32_t dtype_ref, int32_t dtype_test, int64_t volumes, int32_t d,
+                                int32_t h, int32_t w, int64_t ref_stride_volume, int64_t ref_stride_z, int64_t ref_stride_y, int64_t ref_stride_x,
+                                int64_t test_stride_volume, int64_t test_stride_z, int64_t test_stride_y, int64_t test_stride_x, int32_t unit_map,
+                                double c1, double c2, void* workspace, void* stream) {
+    using namespace afcm;
+    AFCM_REQUIRE(volumes > 0, "volume_ssim: %lld volumes", (long long)volumes);
+    AFCM_REQUIRE(d >= PM_WIN && h >= PM_WIN && w >= PM_WIN, "volume_ssim: a %d x %d x %d volume is smaller than the 7 x 7 x 7 SSIM window", d, h, w);
+    AFCM_REQUIRE(layers != nullptr && ref != nullptr && test != nullptr && workspace != nullptr, "volume_ssim: null layers, volume or workspace");
+    AFCM_REQUIRE(dtype_ref >= AFCM_F32 && dtype_ref <= AFCM_BF16 && dtype_test >= AFCM_F32 && dtype_test <= AFCM_BF16,
+                 "volume_ssim: dtypes %d / %d are not AFCM_F32 / AFCM_F16 / AFCM_BF16", dtype_ref, dtype_test);
+    const long long tiles = vs_tiles(h, w), nlayers = volumes * (d - PM_APRON);
+    AFCM_REQUIRE(volumes < (1ll << 31) && nlayers < (1ll << 31) && nlayers * tiles < (1ll << 31),
+                 "volume_ssim: %lld volumes of %d layers of %lld tiles exceed the grid", (long long)volumes, d - PM_APRON, tiles);
+    const volume_view r = {{ref, 1, ref_stride_y, ref_stride_x, dtype_ref}, ref_stride_volume, ref_stride_z};
+    const volume_view t = {{test, 1, test_stride_y, test_stride_x, dtype_test}, test_stride_volume, test_stride_z};
+    double* partials = (double*)workspace;
+    hipLaunchKernelGGL(volume_ssim_kernel, dim3((unsigned)(nlayers * tiles)), dim3(PM_THREADS), 0, (hipStream_t)stream, partials, r, t,
+                       d - PM_APRON, h, w, cdiv(w - PM_APRON, VS_TILE_X), (int)tiles,
+                       unit_map, c1, c2);
+    hipLaunchKernelGGL(volume_ssim_finish_kernel, dim3((unsigned)nlayers), dim3(64), 0, (hipStream_t)stream, layers, (const double*)partials,
                        (int)tiles);
     return hip_status(hipGetLastError());
 }

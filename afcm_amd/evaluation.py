@@ -160,6 +160,7 @@ def to_unit_range(x):
 # afcm_plane_metrics (include/afcm_hip.h; torch_utils/ops/plane_metrics.py) reduces a pair of image stacks to a float64 [planes, 8] table:
 #   0, 1 max / min of the reference   2, 3 max / min of the prediction   4 sum (r - t)^2   5 sum (r / max r - t / max t)^2   6 sum |r - t|
 #   7 sum of the 7 x 7 SSIM map (data range 2) over its (h - 6)(w - 6) valid windows.
+# afcm_volume_ssim adds the one statistic the table cannot hold: the 7 x 7 x 7 SSIM map's sum per z-layer of window origins ([d - 6] per volume).
 # The finishers below are pure numpy on a host copy of that table and keep the bookkeeping of the functions above: which slices count, the data
 # range of each PSNR, inf for identical images, nan for a prediction whose maximum is zero.  One difference is inherent: the table's arithmetic
 # is float64 throughout, where the functions above follow the dtype of their arrays in three places (psnr_2D's division by the maximum, ThreeD_psnr's
@@ -244,3 +245,24 @@ def evaluate_one_from_stats(tables_by_axis, shape):
         seen += shape[axis]
     total = sum(shape)
     return c_psnr / total, c_ssim / total, float(tables[0][:, _SUM_ABS].sum() / (shape[0] * shape[1] * shape[2]))
+
+
+def evaluate_3D_from_stats(axial_table, ssim_layers, shape):
+    """``evaluate_3D`` of a volume of ``shape`` (d, h, w) from the table of its axial slices ([d, 8]) and the layer sums of its 7 x 7 x 7 SSIM
+    map ([d - 6], afcm_volume_ssim: torch_utils/ops/volume_metrics.py).  PSNR is ``compare_psnr(Limg, Gimg)``: data range 1 for a non-negative
+    target, else 2 (``_float_data_range``, with its ValueError for a target that leaves [-1, 1]); inf for identical volumes."""
+    t = _table(axial_table)
+    layers = np.asarray(ssim_layers, dtype=np.float64)
+    d, h, w = (int(n) for n in shape)
+    if t.shape[0] != d or layers.shape != (d - 6,) or min(d, h, w) < 7:
+        raise ValueError(f'expected a table of {d} rows and {d - 6} layer sums for a volume {(d, h, w)} of at least 7 voxels a side, '
+                         f'got {t.shape[0]} rows and layer sums of shape {layers.shape}')
+    lo, hi = float(t[:, _MIN_R].min()), float(t[:, _MAX_R].max())
+    if hi > 1 or lo < -1:
+        raise ValueError('image_true has intensity values outside the range expected for its data type; specify data_range')
+    npix = d * h * w
+    psnr = _psnr_from_sum(1.0 if lo >= 0 else 2.0, t[:, _SUM_SQ].sum(), npix)
+    c_ssim = 0.0
+    for layer in layers:                                   # index order: the sum is the same on every host
+        c_ssim += float(layer)
+    return psnr, c_ssim / ((d - 6) * (h - 6) * (w - 6)), float(t[:, _SUM_ABS].sum() / npix)

@@ -1,12 +1,14 @@
 """The validation metrics of ``afcm_amd.evaluation`` for DEVICE tensors: one statistics kernel (torch_utils/ops/plane_metrics.py), one
-device -> host copy of its [planes, 8] float64 table, and the numpy finisher that applies the reference's bookkeeping (util/evaluation.py:92-121).
+device -> host copy of its [planes, 8] float64 table, and the numpy finisher that applies the reference's bookkeeping (util/evaluation.py:92-127).
 
-Argument order follows the reference: (prediction, target).  ``evaluate_3D`` (7^3 window) stays host-only.
+Argument order follows the reference: (prediction, target).  ``evaluate_3D`` (7^3 window) adds the layer sums of the volume SSIM kernel
+(torch_utils/ops/volume_metrics.py) to the axial table, in the same single copy.
 """
 import torch
 
 from . import evaluation
 from .torch_utils.ops.plane_metrics import plane_stats
+from .torch_utils.ops.volume_metrics import volume_ssim_layers
 
 
 def as_planes(x):
@@ -48,3 +50,15 @@ def evaluate_one(fake, real, from_network_range=False):
     tables = torch.cat([plane_stats(real.permute(*p), fake.permute(*p), unit_map=from_network_range) for p in views]).cpu().numpy()
     d, h, w = (int(v) for v in real.shape)
     return evaluation.evaluate_one_from_stats((tables[:d], tables[d:d + h], tables[d + h:]), (d, h, w))
+
+
+def evaluate_3D(fake, real, from_network_range=False):
+    """``evaluation.evaluate_3D`` for volumes [D, H, W] on the device: volume PSNR, SSIM with the 7 x 7 x 7 window, MAE.  The axial table
+    ([D, 8]) and the layer sums of the SSIM map ([D - 6]) go to the host flattened into one tensor: one copy."""
+    if fake.dim() != 3 or fake.shape != real.shape:
+        raise RuntimeError(f'evaluate_3D: expected two [D, H, W] volumes of one shape, got {tuple(fake.shape)} and {tuple(real.shape)}')
+    d, h, w = (int(v) for v in real.shape)
+    table = plane_stats(real, fake, unit_map=from_network_range)
+    layers = volume_ssim_layers(real[None], fake[None], unit_map=from_network_range)
+    flat = torch.cat([table.reshape(-1), layers.reshape(-1)]).cpu().numpy()
+    return evaluation.evaluate_3D_from_stats(flat[:d * 8].reshape(d, 8), flat[d * 8:], (d, h, w))

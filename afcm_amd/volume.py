@@ -13,6 +13,7 @@ from . import evaluation
 from .data import SliceDataset, open_volumes
 from .predictor import SlidingWindowPredictor, patch_indices, validate_halo
 from .torch_utils.ops.plane_metrics import plane_stats
+from .torch_utils.ops.volume_metrics import volume_ssim_layers
 from .torch_utils.ops.volume_ops import assemble_slices, halo_accumulate
 
 
@@ -179,15 +180,36 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     return {head: predictors[head].finish() for head in heads}
 
 
-def evaluate_volume(step, source, target, *, from_network_range=True, **predict_kwargs):
+def volume_metrics(fake, target, *, from_network_range=True, with_3d=False):
+    """The metric half of ``evaluate_volume`` for a predicted volume ``fake`` and its ``target`` ([D, H, W] device tensors of one shape): the three
+    axes' statistics tables (and, ``with_3d``, the d - 6 layer sums of ``afcm_volume_ssim`` behind them) gathered on the device and copied to the host
+    ONCE, then the numpy finishers.  The axial table serves 'slice', 'one' and '3d' alike.  Returns {'slice': ..., 'one': ...[, '3d': ...]}."""
+    d, h, w = (int(v) for v in fake.shape)
+    views = ((0, 1, 2), (1, 0, 2), (2, 0, 1))
+    tables = [plane_stats(target.permute(*p), fake.permute(*p), unit_map=from_network_range) for p in views]
+    if not with_3d:
+        tables = torch.cat(tables).cpu().numpy()
+    else:                                                  # one flat tensor, one copy: the three tables, then the layer sums
+        layers = volume_ssim_layers(target[None], fake[None], unit_map=from_network_range)
+        flat = torch.cat([t.reshape(-1) for t in tables] + [layers.reshape(-1)]).cpu().numpy()
+        tables, layers = flat[:(d + h + w) * 8].reshape(d + h + w, 8), flat[(d + h + w) * 8:]
+    by_axis = (tables[:d], tables[d:d + h], tables[d + h:])
+    out = {'slice': evaluation.evaluate_slice_from_stats(by_axis[0], h, w), 'one': evaluation.evaluate_one_from_stats(by_axis, (d, h, w))}
+    if with_3d:
+        out['3d'] = evaluation.evaluate_3D_from_stats(by_axis[0], layers, (d, h, w))
+    return out
+
+
+def evaluate_volume(step, source, target, *, from_network_range=True, with_3d=False, **predict_kwargs):
     """``predict_volume(where='device')`` followed by the reference's per-volume metrics (evaluate.py:73-87) without leaving the device:
     ``evaluation_device.evaluate_slice`` (the per-slice means evaluate.py reports as psnr_slice / ssim_slice) and ``evaluate_one`` (slices along all
     three axes) of channel 0 of the prediction against ``target`` [D, H, W], a device tensor.  With ``from_network_range`` (the default) both are
     mapped to [0, 1] on load by ``to_unit_range``, evaluate.py:76-77's ``(clip(x, -1, 1) + 1) / 2`` for the prediction, so ``target`` is expected in the
     network's range, normalised as the loader normalises its volumes; pass False when both already are in [0, 1].  The three statistics tables
     are gathered on the device and copied once: that copy is the only device -> host transfer and the only synchronise of the whole call.
-    ``evaluate_3D`` (7^3 window SSIM over the volume, evaluate.py:81) is not offered on the device: it stays ``evaluation.evaluate_3D`` on host arrays.
-    Returns {'slice': (psnr, ssim, mae), 'one': (psnr, ssim, mae), 'prediction': [C, D, H, W] device tensor}."""
+    ``with_3d=True`` adds ``evaluate_3D`` (volume PSNR and the 7^3-window SSIM evaluate.py:81 reports first) as ``'3d'``: the layer sums of
+    ``afcm_volume_ssim`` travel in that same copy, behind the three tables.
+    Returns {'slice': (psnr, ssim, mae), 'one': (psnr, ssim, mae), 'prediction': [C, D, H, W] device tensor} and, on request, '3d': (psnr, ssim, mae)."""
     if predict_kwargs.get('where', 'device') != 'device':
         raise ValueError("evaluate_volume runs on the device; for host arrays use predict_volume(where='host') and afcm_amd.evaluation")
     predict_kwargs['heads'] = ('prediction',)
@@ -197,9 +219,4 @@ def evaluate_volume(step, source, target, *, from_network_range=True, **predict_
         raise RuntimeError('evaluate_volume: the target must be a tensor on the prediction\'s device (upload it once, outside the loop)')
     if target.shape != fake.shape:
         raise RuntimeError(f'evaluate_volume: the target is {tuple(target.shape)}, the predicted volume {tuple(fake.shape)}')
-    d, h, w = (int(v) for v in fake.shape)
-    views = ((0, 1, 2), (1, 0, 2), (2, 0, 1))
-    tables = torch.cat([plane_stats(target.permute(*p), fake.permute(*p), unit_map=from_network_range) for p in views]).cpu().numpy()
-    by_axis = (tables[:d], tables[d:d + h], tables[d + h:])
-    return {'slice': evaluation.evaluate_slice_from_stats(by_axis[0], h, w), 'one': evaluation.evaluate_one_from_stats(by_axis, (d, h, w)),
-            'prediction': prediction}
+    return dict(volume_metrics(fake, target, from_network_range=from_network_range, with_3d=with_3d), prediction=prediction)

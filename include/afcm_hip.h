@@ -22,7 +22,7 @@
  *     failed (the reference's TORCH_CHECK); >= 1000 = 1000 + hipError_t of the launch.
  *   - dtype codes: AFCM_F32, AFCM_F16, AFCM_BF16 (bf16 is new capability; the reference
  *     plugin accepts half/float only).  Arithmetic is always fp32 inside the kernels, with TWO exceptions:
- *     afcm_plane_metrics (validation metrics, end of this header) computes in float64 after its loads; afcm_slice_assemble
+ *     afcm_plane_metrics / afcm_volume_ssim (validation metrics, end of this header) compute in float64 after their loads; afcm_slice_assemble
  *     (after it) normalises in the type numpy gives the loader's expression, float64 for every source but float32.
  */
 #ifndef AFCM_HIP_H
@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AFCM_ABI_VERSION 13  /* 13: + afcm_slice_assemble, afcm_halo_accumulate (whole-volume inference; additions only, so the number stays).  13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
+#define AFCM_ABI_VERSION 13  /* 13: + afcm_volume_ssim, afcm_volume_ssim_workspace_bytes (the 7^3-window SSIM map's layer sums; additions only, so the number stays).  13: + afcm_slice_assemble, afcm_halo_accumulate (whole-volume inference; additions only, so the number stays).  13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
 
 enum { AFCM_F32 = 0, AFCM_F16 = 1, AFCM_BF16 = 2 };
 enum { AFCM_OK = 0, AFCM_E_NOKERNEL = -1, AFCM_E_INVALID = -2 };
@@ -584,6 +584,26 @@ int afcm_halo_accumulate(float* map, uint8_t* mask, const void* pred, int32_t dt
                          int32_t pd, int32_t ph, int32_t pw, int32_t halo_z, int32_t halo_y, int32_t halo_x, int32_t D, int32_t H, int32_t W,
                          int32_t map_channels, int32_t prediction_channel, int32_t z0, int32_t z1, int32_t y0, int32_t y1, int32_t x0, int32_t x1,
                          void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Volume SSIM (r09): the sum of the 3-D SSIM map behind evaluate_3D (util/evaluation.py:123-127, evaluate.py:81), layer by layer.
+ * layers [volumes][d - 6] float64: layers[v][z] is the sum of the SSIM map of volume v over the (h - 6)(w - 6) windows whose origin lies in
+ * z-layer z -- uniform 7 x 7 x 7 window, means = sums / 343.0, sample covariance (factor 343 / 342), the formula of column 7 of
+ * afcm_plane_metrics, valid windows only (the reference averages the cropped interior).  The host adds the d - 6 layers in index order and divides
+ * by (d - 6)(h - 6)(w - 6); every other number of evaluate_3D comes from the axial table of afcm_plane_metrics.
+ * ref / test: DEVICE volumes of dtype_ref / dtype_test (they may differ), element (v, z, y, x) at v * stride_volume + z * stride_z + y * stride_y +
+ * x * stride_x ELEMENTS, offsets formed in 64 bits: any strides, read as they lie.  unit_map as in afcm_plane_metrics.  After the load every
+ * operation is float64.  Every window sum is a direct sum of its terms (seven z-neighbours per voxel, seven columns, seven rows): no running sums.
+ * Two launches on the stream: one workgroup per (volume, z origin, 16 x 64 tile of window origins) stores one partial into `workspace`
+ * (afcm_volume_ssim_workspace_bytes() bytes, no initialisation needed), then one wave per (volume, z origin) adds that layer's partials in a fixed
+ * order.  No atomics: the result is bit-identical from call to call.  A NaN voxel makes exactly the layers whose windows contain it NaN.
+ * AFCM_E_INVALID: null pointers, unknown dtypes, volumes < 1, d / h / w < 7, more than 2^31 - 1 workgroups.
+ * ---------------------------------------------------------------------------------------- */
+int64_t afcm_volume_ssim_workspace_bytes(int64_t volumes, int32_t d, int32_t h, int32_t w);
+int afcm_volume_ssim(double* layers, const void* ref, const void* test, int32_t dtype_ref, int32_t dtype_test, int64_t volumes, int32_t d, int32_t h,
+                     int32_t w, int64_t ref_stride_volume, int64_t ref_stride_z, int64_t ref_stride_y, int64_t ref_stride_x,
+                     int64_t test_stride_volume, int64_t test_stride_z, int64_t test_stride_y, int64_t test_stride_x, int32_t unit_map, double c1,
+                     double c2, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
