@@ -1,0 +1,174 @@
+// Training batches on the device: the train-phase loader item (data/cmsr_dataset.py:98-152) for a batch of unrelated (subject, slice, thickness)
+// rows of a DEVICE item table, over a pool that holds every volume of the training set.
+//   batch_assemble_kernel   A [count, k, h, w], B [count, 1, h, w] and the labels in one launch; a thread produces a run of RUN consecutive x of one
+//                           output row (item, plane and row decoding, the table reads and the guards happen once per run) and stores it at once
+//   cursor_advance_kernel   cursor[0] += by, one thread: the table position of a captured graph moves on the device
+// The tables cannot be checked on the host, so the kernel checks every row before it reads the pool; an invalid item reads nothing and comes out as
+// NaN.  No LDS, no atomics; every pool offset is 64-bit.  See include/afcm_hip.h for the semantics kept.
+#include "common.h"
+#include "volume_common.h"
+
+// bytes of one thread's run along x (one store); 0: one element per thread, the form of slice_assemble_kernel (tools/bench_train_feed.py builds both)
+#ifndef AFCM_BATCH_RUN_BYTES
+#define AFCM_BATCH_RUN_BYTES 16
+#endif
+
+namespace afcm {
+
+template <typename T>
+constexpr int batch_run() { return AFCM_BATCH_RUN_BYTES > 0 ? AFCM_BATCH_RUN_BYTES / (int)sizeof(T) : 1; }
+
+template <typename T, int RUN>
+struct alignas(sizeof(T) * RUN) run_of {
+    T v[RUN];
+};
+
+// [offset, offset + depth hs ws) inside [0, pool_elems) with positive extents, without forming a product that could overflow
+__device__ __forceinline__ bool descriptor_ok(long long off, long long depth, long long hs, long long ws, long long pool_elems) {
+    if (depth <= 0 || hs <= 0 || ws <= 0 || ws > pool_elems || hs > pool_elems / ws) return false;
+    const long long plane = hs * ws;
+    if (depth > pool_elems / plane) return false;
+    return off >= 0 && off <= pool_elems - depth * plane;
+}
+
+template <typename S, typename T, int RUN>
+__global__ __launch_bounds__(VOL_THREADS) void batch_assemble_kernel(T* __restrict__ a, T* __restrict__ b, float* __restrict__ slice_idx,
+                                                                     const S* __restrict__ pool, long long pool_elems,
+                                                                     const long long* __restrict__ vols, int n_vols, const int* __restrict__ items,
+                                                                     int n_items, const long long* __restrict__ cursor, int first, int k, int h, int w,
+                                                                     int runs, long long total, double lo, double range) {
+    const long long e = (long long)blockIdx.x * VOL_THREADS + threadIdx.x;
+    if (e >= total) return;
+    const int x0 = (int)(e % runs) * RUN;
+    long long r = e / runs;
+    const int y = (int)(r % h);
+    r /= h;
+    const int plane = (int)(r % (k + 1));                                      // plane k: the target B
+    const int i = (int)(r / (k + 1));
+
+    // the item's row and its two volumes, checked before anything is read from the pool
+    const long long c0 = cursor != nullptr ? cursor[0] : 0;
+    bool valid = c0 >= 0 && c0 < n_items;
+    const long long row = valid ? c0 + first + i : 0;
+    valid = valid && row < n_items;
+    int va = 0, vb = 0, idx = 0, t = 1;
+    if (valid) {
+        va = items[row * 4 + 0], vb = items[row * 4 + 1], idx = items[row * 4 + 2], t = items[row * 4 + 3];
+        valid = va >= 0 && va < n_vols && vb >= 0 && vb < n_vols && t != 0 && (k == 1 || t >= 1);
+    }
+    long long off_a = 0, off_b = 0, depth = 1, hs = 1, ws = 1;
+    if (valid) {
+        const long long* da = vols + (long long)va * 4;
+        const long long* db = vols + (long long)vb * 4;
+        off_a = da[0], depth = da[1], hs = da[2], ws = da[3], off_b = db[0];
+        valid = descriptor_ok(off_a, depth, hs, ws, pool_elems) && descriptor_ok(off_b, db[1], db[2], db[3], pool_elems) && db[1] == depth &&
+                db[2] == hs && db[3] == ws && idx >= 0 && idx < depth;
+    }
+    const int idx_a = valid && k == 4 ? (idx / t) * t : idx;
+    if (plane == 0 && y == 0 && x0 == 0) slice_idx[i] = valid ? (float)(idx - idx_a) / (float)t : __builtin_nanf("");
+
+    float v[RUN];
+    if (!valid) {
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) v[j] = __builtin_nanf("");
+    } else {
+        const long long pos = plane < k && k == 4 ? (long long)idx_a + (long long)(plane - 1) * t : idx;
+        if (pos < 0 || pos > depth - 1) {
+            const float z = normalised<double>(nullptr, 0, false, lo, range);  // a plane of float64 zeros before normalisation
+#pragma unroll
+            for (int j = 0; j < RUN; ++j) v[j] = z;
+        } else {
+            const long long ys = y + crop_offset(hs, h), xs0 = x0 + crop_offset(ws, w);   // crop offset (> 0) or minus the leading pad
+            const bool row_inside = ys >= 0 && ys < hs;
+            const long long at = (plane < k ? off_a : off_b) + (pos * hs + ys) * ws + xs0;
+#pragma unroll
+            for (int j = 0; j < RUN; ++j) {
+                const bool inside = row_inside && xs0 + j >= 0 && xs0 + j < ws && x0 + j < w;
+                v[j] = normalised<S>(pool, at + j, inside, lo, range);
+            }
+        }
+    }
+
+    T* out = (plane < k ? a + (((long long)i * k + plane) * h + y) * w : b + ((long long)i * h + y) * w) + x0;
+    if (RUN > 1 && x0 + RUN <= w && (uintptr_t)out % (sizeof(T) * RUN) == 0) {
+        run_of<T, RUN> pack;
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) pack.v[j] = (T)v[j];
+        *reinterpret_cast<run_of<T, RUN>*>(out) = pack;
+    } else {                                                                   // the tail of a row, or a row that does not start on a run boundary
+#pragma unroll
+        for (int j = 0; j < RUN; ++j)
+            if (x0 + j < w) out[j] = (T)v[j];
+    }
+}
+
+__global__ void cursor_advance_kernel(long long* __restrict__ cursor, long long by) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) cursor[0] += by;
+}
+
+template <typename S, typename T>
+static int launch_batch(void* a, void* b, float* slice_idx, const void* pool, long long pool_elems, const int64_t* vols, int n_vols, const int32_t* items,
+                        int n_items, const int64_t* cursor, int first, int count, int k, int h, int w, double lo, double range, hipStream_t stream) {
+    constexpr int RUN = batch_run<T>();
+    const int runs = cdiv(w, RUN);
+    const double threads = (double)count * (k + 1) * h * runs;                 // checked before the product is formed in 64 bits
+    AFCM_REQUIRE(threads / VOL_THREADS < 2147483647.0, "batch_assemble: %.0f workgroups exceed the grid", threads / VOL_THREADS);
+    const long long total = (long long)count * (k + 1) * h * runs;
+    const long long groups = (total + VOL_THREADS - 1) / VOL_THREADS;
+    hipLaunchKernelGGL((batch_assemble_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, stream, (T*)a, (T*)b, slice_idx, (const S*)pool,
+                       pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items, (const long long*)cursor, first, k, h, w, runs, total, lo,
+                       range);
+    return hip_status(hipGetLastError());
+}
+
+template <typename S>
+static int launch_batch_out(int out_dtype, void* a, void* b, float* slice_idx, const void* pool, long long pool_elems, const int64_t* vols, int n_vols,
+                            const int32_t* items, int n_items, const int64_t* cursor, int first, int count, int k, int h, int w, double lo, double range,
+                            hipStream_t stream) {
+    if (out_dtype == AFCM_F32)
+        return launch_batch<S, float>(a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w, lo, range, stream);
+    if (out_dtype == AFCM_F16)
+        return launch_batch<S, f16_t>(a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w, lo, range, stream);
+    return launch_batch<S, bf16_t>(a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w, lo, range, stream);
+}
+
+}  // namespace afcm
+
+extern "C" int afcm_batch_assemble(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                                   int32_t n_vols, const int32_t* items, int32_t n_items, const int64_t* cursor, int32_t first, int32_t count, int32_t k,
+                                   int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream) {
+    using namespace afcm;
+    AFCM_REQUIRE(a != nullptr && b != nullptr && slice_idx != nullptr && pool != nullptr && vols != nullptr && items != nullptr,
+                 "batch_assemble: null output, label, pool or table");
+    AFCM_REQUIRE(src_dtype >= AFCM_SRC_U8 && src_dtype <= AFCM_SRC_F64, "batch_assemble: source dtype %d is not AFCM_SRC_U8 / I16 / F32 / F64", src_dtype);
+    AFCM_REQUIRE(out_dtype >= AFCM_F32 && out_dtype <= AFCM_BF16, "batch_assemble: output dtype %d is not AFCM_F32 / AFCM_F16 / AFCM_BF16", out_dtype);
+    AFCM_REQUIRE(count > 0 && h > 0 && w > 0 && n_vols > 0 && n_items > 0 && pool_elems > 0,
+                 "batch_assemble: %d items of [%d, %d] from %d volumes, a table of %d rows, a pool of %lld elements: every extent must be positive", count, h,
+                 w, n_vols, n_items, (long long)pool_elems);
+    AFCM_REQUIRE(first >= 0, "batch_assemble: first row %d is negative", first);
+    AFCM_REQUIRE(k == 1 || k == 4, "batch_assemble: slice number %d is not 1 or 4", k);
+    AFCM_REQUIRE(max_value > min_value, "batch_assemble: max_value %g is not above min_value %g", max_value, min_value);
+    const double range = max_value - min_value;
+    hipStream_t s = (hipStream_t)stream;
+    switch (src_dtype) {
+        case AFCM_SRC_U8:
+            return launch_batch_out<uint8_t>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
+                                             min_value, range, s);
+        case AFCM_SRC_I16:
+            return launch_batch_out<int16_t>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
+                                             min_value, range, s);
+        case AFCM_SRC_F32:
+            return launch_batch_out<float>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
+                                           min_value, range, s);
+        default:
+            return launch_batch_out<double>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
+                                            min_value, range, s);
+    }
+}
+
+extern "C" int afcm_cursor_advance(int64_t* cursor, int64_t by, void* stream) {
+    using namespace afcm;
+    AFCM_REQUIRE(cursor != nullptr, "cursor_advance: null cursor");
+    hipLaunchKernelGGL(cursor_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (long long*)cursor, (long long)by);
+    return hip_status(hipGetLastError());
+}

@@ -5,28 +5,9 @@
 //                           form: one thread per voxel of the batch's bounding box walks the batch's patches in ascending order
 // Neither kernel stages anything in LDS or uses an atomic; every volume offset is 64-bit.  See include/afcm_hip.h for the semantics kept.
 #include "common.h"
+#include "volume_common.h"
 
 namespace afcm {
-
-constexpr int VOL_THREADS = 256;
-
-// One source element normalised as numpy evaluates data.normalize on an array of the source's type: float64 arithmetic for u8 / i16 / f64, float32
-// for f32 (numpy keeps a float32 array's type against Python scalars).  `inside` false: a padded pixel, a zero of the source type.
-// Every operation is rounded on its own (-ffp-contract=off); the clip keeps a NaN, as numpy.clip does.
-template <typename S>
-__device__ __forceinline__ float normalised(const S* __restrict__ src, long long i, bool inside, double lo, double range) {
-    const double m = inside ? (double)src[i] : 0.0;
-    double v = 2.0 * ((m - lo) / range) - 1.0;
-    v = v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v);
-    return (float)v;
-}
-template <>
-__device__ __forceinline__ float normalised<float>(const float* __restrict__ src, long long i, bool inside, double lo, double range) {
-    const float m = inside ? src[i] : 0.0f;
-    float v = 2.0f * ((m - (float)lo) / (float)range) - 1.0f;
-    v = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
-    return v;
-}
 
 template <typename S, typename T>
 __global__ __launch_bounds__(VOL_THREADS) void slice_assemble_kernel(T* __restrict__ a, float* __restrict__ slice_idx, const S* __restrict__ src,
@@ -115,9 +96,6 @@ static int launch_assemble(void* a, int out_dtype, float* slice_idx, const void*
     return hip_status(hipGetLastError());
 }
 
-// transforms.py:250-275 for one axis: the source coordinate of output coordinate 0
-static inline int crop_offset(int have, int want) { return want < have ? (have - want) / 2 : -((want - have) / 2); }
-
 }  // namespace afcm
 
 extern "C" int afcm_slice_assemble(void* a, float* slice_idx, const void* src, int32_t src_dtype, int32_t out_dtype, int32_t depth, int32_t hs,
@@ -137,7 +115,7 @@ extern "C" int afcm_slice_assemble(void* a, float* slice_idx, const void* src, i
     AFCM_REQUIRE(max_value > min_value, "slice_assemble: max_value %g is not above min_value %g", max_value, min_value);
     const long long total = (long long)count * k * h * w;
     AFCM_REQUIRE((total + VOL_THREADS - 1) / VOL_THREADS < (1ll << 31), "slice_assemble: %lld output elements exceed the grid", total);
-    const int oy = crop_offset(hs, h), ox = crop_offset(ws, w);
+    const int oy = (int)crop_offset(hs, h), ox = (int)crop_offset(ws, w);
     const double range = max_value - min_value;
     hipStream_t s = (hipStream_t)stream;
     switch (src_dtype) {

@@ -1,0 +1,76 @@
+"""assemble_batch / advance_cursor: a training batch from a device-resident pool of volumes (C ABI ``afcm_batch_assemble`` / ``afcm_cursor_advance``,
+include/afcm_hip.h; kernels in csrc/batch.hip).
+
+``assemble_batch`` is ``SliceDataset(phase='train').__getitem__`` for ``count`` rows of a device-side item table -- ``A``, ``B`` and ``slice_idx`` in
+one launch, bit-identical to the stacked host items.  The tables live on the device, so the kernel checks every row itself: an invalid row comes out
+as a NaN item and reads nothing.  Both calls are asynchronous on the current stream and can be captured into a graph.
+"""
+import torch
+
+from ... import _lib
+from .volume_ops import _SOURCE_DTYPES
+
+_OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _table(t, what, dtype, cols):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != cols or t.dtype != dtype or not t.is_contiguous() or t.shape[0] < 1:
+        got = f'{t.dtype} {tuple(t.shape)}' if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f'assemble_batch: {what} must be a contiguous {dtype} [n, {cols}] with n >= 1, got {got}')
+
+
+def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_value=0., max_value=255., dtype=torch.float32, out=None, cursor=None):
+    """``pool``: 1-D DEVICE tensor (uint8 / int16 / float32 / float64) holding every volume; ``vols``: DEVICE int64 [n_vols, 4] (element offset into the
+    pool, depth, hs, ws); ``items``: DEVICE int32 [n_items, 4] (vol_a, vol_b, idx, thickness; thickness -1: none, ``slice_num`` 1 only).  Sample ``i`` is
+    table row ``(cursor[0] if cursor is not None else 0) + first + i``.  Returns ``A [count, slice_num, H, W]``, ``B [count, 1, H, W]`` of ``dtype``
+    and ``slice_idx [count, 1]`` float32 with ``patch_hw = (H, W)``: per volume centre crop / constant pad, the thick slices at -1, 0, +1, +2
+    ``thickness`` around the target's own (``slice_num`` 4) or the slice itself (1), ``data.normalize``.  ``out=(A, B, slice_idx)`` writes into existing
+    tensors (a captured graph needs stable addresses); ``cursor``: DEVICE int64 scalar tensor, see ``advance_cursor``."""
+    h, w = (int(v) for v in patch_hw)
+    first, count = int(first), int(count)
+    if slice_num not in (1, 4):
+        raise RuntimeError(f'assemble_batch: slice number {slice_num} not supported (1 or 4)')
+    if not isinstance(pool, torch.Tensor) or pool.dim() != 1 or not pool.is_contiguous() or pool.numel() < 1:
+        raise RuntimeError(f'assemble_batch: the pool must be a non-empty contiguous 1-D tensor, got shape {tuple(getattr(pool, "shape", ()))}')
+    if pool.dtype not in _SOURCE_DTYPES:
+        raise RuntimeError(f'assemble_batch: source volumes are uint8 / int16 / float32 / float64, got {pool.dtype}')
+    _table(vols, 'the volume table', torch.int64, 4)
+    _table(items, 'the item table', torch.int32, 4)
+    if dtype not in _OUT_DTYPES:
+        raise RuntimeError(f'assemble_batch: output dtype float32 / float16 / bfloat16, got {dtype}')
+    if count < 1 or first < 0 or h < 1 or w < 1:
+        raise RuntimeError(f'assemble_batch: {count} items from row {first} at [{h}, {w}]: count and the patch must be positive, first not negative')
+    if cursor is not None and (not isinstance(cursor, torch.Tensor) or cursor.dtype != torch.int64 or cursor.numel() != 1):
+        raise RuntimeError(f'assemble_batch: the cursor must be an int64 tensor of one element, got {getattr(cursor, "dtype", type(cursor).__name__)} '
+                           f'{tuple(getattr(cursor, "shape", ()))}')
+    shapes = ((count, slice_num, h, w), (count, 1, h, w), (count, 1))
+    if out is None:
+        a = torch.empty(shapes[0], dtype=dtype, device=pool.device)
+        b = torch.empty(shapes[1], dtype=dtype, device=pool.device)
+        slice_idx = torch.empty(shapes[2], dtype=torch.float32, device=pool.device)
+    else:
+        if len(out) != 3:
+            raise RuntimeError(f'assemble_batch: out must be (A, B, slice_idx), got {len(out)} values')
+        a, b, slice_idx = out
+        for name, t, shape, want in (('A', a, shapes[0], dtype), ('B', b, shapes[1], dtype), ('slice_idx', slice_idx, shapes[2], torch.float32)):
+            if tuple(t.shape) != shape or t.dtype != want or not t.is_contiguous():
+                raise RuntimeError(f'assemble_batch: out {name} must be a contiguous {want} {shape}, got {t.dtype} {tuple(t.shape)} '
+                                   f'with strides {tuple(t.stride())}')
+    tensors = (pool, vols, items, a, b, slice_idx) + (() if cursor is None else (cursor,))
+    _lib.require_gpu(*tensors)
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError(f'assemble_batch: pool, tables, outputs and cursor must be on one device, got {sorted({str(t.device) for t in tensors})}')
+    rc = _lib.load().afcm_batch_assemble(a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), _SOURCE_DTYPES[pool.dtype],
+                                         vols.data_ptr(), int(vols.shape[0]), items.data_ptr(), int(items.shape[0]), _lib.ptr(cursor), first, count,
+                                         slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
+    _lib.launched(rc, 'batch_assemble')
+    return a, b, slice_idx
+
+
+def advance_cursor(cursor, by):
+    """``cursor[0] += by`` on the device (one thread on the current stream): the table position a captured graph reads moves without the host."""
+    if not isinstance(cursor, torch.Tensor) or cursor.dtype != torch.int64 or cursor.numel() != 1:
+        raise RuntimeError(f'advance_cursor: the cursor must be an int64 tensor of one element, got {getattr(cursor, "dtype", type(cursor).__name__)} '
+                           f'{tuple(getattr(cursor, "shape", ()))}')
+    _lib.require_gpu(cursor)
+    _lib.launched(_lib.load().afcm_cursor_advance(cursor.data_ptr(), int(by), _lib.stream_ptr(cursor)), 'cursor_advance')

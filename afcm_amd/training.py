@@ -1,0 +1,290 @@
+"""The training side of the data path: the training set resident on the device, one launch per batch, and the reference's inner training loop
+(train.py:45-77) on top of it.
+
+``DeviceSliceSet`` uploads every volume of every subject once into one pool tensor and describes an epoch as an int32 table of
+``(vol_a, vol_b, idx, thickness)`` rows; ``afcm_batch_assemble`` (torch_utils/ops/batch_ops.py) turns ``count`` rows of that table into the batch
+``SliceDataset(phase='train')`` items would stack to, bit for bit.  ``train_epoch`` is the loop ``for data in dataset: set_input; optimize_parameters;
+EMA`` with the batches from the device (or, ``where='host'``, from ``SliceDataset``: the comparison arm).  ``TrainingGraph`` is that loop's body as one
+replayed graph that reads its batch through a device-side cursor: no host data work between steps.
+"""
+import numpy as np
+import torch
+
+from .data import SliceDataset, open_volumes
+from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch
+
+_NUMPY_SOURCES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int16): torch.int16, np.dtype(np.float32): torch.float32,
+                  np.dtype(np.float64): torch.float64}
+
+
+class DeviceSliceSet:
+    """All subjects' volumes in one device pool, addressed by a table of training items.
+
+    ``sources``: one mapping ``{internal path: ndarray [D, Hs, Ws]}`` or HDF5 file name per subject, as ``SliceDataset`` takes them.  The volumes of
+    ``raw_internal_path_in[0]`` and of every output modality are uploaded uncropped (the kernel crops / pads each to ``patch_shape[1:]`` from its own
+    extent) into one 1-D tensor of their common dtype; ``vols`` int64 [subjects * modalities, 4] holds (element offset, depth, hs, ws).
+    ``device=None`` builds the host-side tables only (``epoch_items`` and ``host_batch`` work, nothing is uploaded)."""
+
+    def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
+                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda'):
+        if phase not in ('train', 'val', 'test'):
+            raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
+        if cat_inputs:
+            raise RuntimeError('DeviceSliceSet: cat_inputs=True is not supported (no shipped configuration uses it); use SliceDataset for it')
+        patch_shape = tuple(int(v) for v in patch_shape)
+        if len(patch_shape) != 3 or patch_shape[0] != 1 or min(patch_shape) < 1:
+            raise RuntimeError(f'DeviceSliceSet: patch_shape must be (1, H, W), got {patch_shape}')
+        if slice_num not in (1, 4):
+            raise RuntimeError(f'DeviceSliceSet: slice number {slice_num} not supported (1 or 4)')
+        self.phase, self.patch_shape, self.rand_output, self.slice_num = phase, patch_shape, bool(rand_output), int(slice_num)
+        self.raw_internal_path_in, self.raw_internal_path_out = list(raw_internal_path_in), list(raw_internal_path_out)
+        self.thickness = [int(t) for t in thickness]
+        if any(t < 1 for t in self.thickness) or (slice_num == 4 and not self.thickness):
+            raise RuntimeError(f'DeviceSliceSet: thicknesses {self.thickness} with slice number {slice_num}: every thickness must be at least 1, and '
+                               f'slice number 4 needs one')
+        if not max_value > min_value:
+            raise RuntimeError(f'DeviceSliceSet: max_value {max_value} is not above min_value {min_value}')
+        self.min_value, self.max_value = float(min_value), float(max_value)
+        self.paths = list(dict.fromkeys(self.raw_internal_path_in[:1] + self.raw_internal_path_out))
+        self.volumes = [open_volumes(s, self.paths) for s in sources]
+        if not self.volumes:
+            raise RuntimeError('DeviceSliceSet: no subjects')
+        dtypes = sorted({str(v.dtype) for subject in self.volumes for v in subject.values()})
+        if len(dtypes) != 1:
+            raise RuntimeError(f'DeviceSliceSet: mixed source dtypes {dtypes}: the pool holds one dtype, convert the volumes first')
+        self.source_dtype = np.dtype(dtypes[0])
+        if self.source_dtype not in _NUMPY_SOURCES:
+            raise RuntimeError(f'DeviceSliceSet: source volumes are uint8 / int16 / float32 / float64, got {self.source_dtype}')
+        rows, offset, self.depths = [], 0, []
+        for s, subject in enumerate(self.volumes):
+            shapes = {p: tuple(int(n) for n in subject[p].shape) for p in self.paths}
+            if len(set(shapes.values())) != 1 or len(shapes[self.paths[0]]) != 3:
+                raise RuntimeError(f'DeviceSliceSet: subject {s}: the input and output volumes must have one [D, H, W] shape, got {shapes}')
+            d, hs, ws = shapes[self.paths[0]]
+            if min(d, hs, ws) < 1:
+                raise RuntimeError(f'DeviceSliceSet: subject {s}: empty volume {shapes[self.paths[0]]}')
+            self.depths.append(d)
+            for _ in self.paths:
+                rows.append((offset, d, hs, ws))
+                offset += d * hs * ws
+        self.vols_host = np.array(rows, dtype=np.int64)
+        self.pool_elems = offset
+        # (subject, idx) of every slice in serial order, and where each subject's first row lies
+        self._subject = np.repeat(np.arange(len(self.depths), dtype=np.int64), self.depths)
+        self._idx = np.concatenate([np.arange(d, dtype=np.int64) for d in self.depths])
+        self._host_sets = {}
+        self.device = None if device is None else torch.device(device)
+        self.pool = self.vols = self.items = self.cursor = None
+        self.rows = self.position = 0
+        if self.device is not None:
+            if self.device.type != 'cuda':
+                raise RuntimeError(f'DeviceSliceSet needs a ROCm device (got {self.device}); device=None builds the host-side tables only')
+            pool = np.concatenate([np.ascontiguousarray(subject[p]).reshape(-1) for subject in self.volumes for p in self.paths])
+            self.pool = torch.from_numpy(pool).to(self.device)                           # the one upload of the training set
+            self.vols = torch.from_numpy(self.vols_host).to(self.device)
+            # persistent (a captured graph holds their addresses): the epoch's table, refreshed in place, and the row a graph's next batch starts at
+            self.items = torch.full((len(self), 4), -1, dtype=torch.int32, device=self.device)
+            self.cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def __len__(self):
+        return int(self._idx.shape[0])
+
+    def epoch_items(self, seed_or_generator=None, shuffle=None):
+        """The int32 [len(self), 4] table of one epoch, rows (vol_a, vol_b, idx, thickness); every (subject, idx) appears exactly once.  'train':
+        the rows are shuffled (unless ``shuffle`` is False), the thickness is drawn uniformly per row from the list (-1 for an empty list) and,
+        with ``rand_output``, ``vol_b`` uniformly from the output modalities; 'val' / 'test': serial order, ``thickness[0]``, the last output
+        modality.  The draws come from a ``numpy.random.Generator`` (``seed_or_generator``: one, or a seed for ``default_rng``) in a fixed order:
+        the permutation, the thicknesses, the modalities.  The reference's own stream -- ``random.choice`` inside DataLoader workers plus the sampler's
+        permutation -- depends on worker scheduling and cannot be reproduced; the distribution is the same."""
+        rng = seed_or_generator if isinstance(seed_or_generator, np.random.Generator) else np.random.default_rng(seed_or_generator)
+        n, train, m = len(self), self.phase == 'train', len(self.paths)
+        order = rng.permutation(n) if (train if shuffle is None else shuffle) else np.arange(n)
+        subject, idx = self._subject[order], self._idx[order]
+        if not self.thickness:
+            thickness = np.full(n, -1, dtype=np.int64)
+        elif train:
+            thickness = np.asarray(self.thickness, dtype=np.int64)[rng.integers(0, len(self.thickness), n)]
+        else:
+            thickness = np.full(n, self.thickness[0], dtype=np.int64)
+        out_columns = np.array([self.paths.index(p) for p in self.raw_internal_path_out], dtype=np.int64)
+        if train and self.rand_output:
+            column_b = out_columns[rng.integers(0, len(out_columns), n)]
+        else:
+            column_b = np.full(n, out_columns[-1], dtype=np.int64)
+        column_a = self.paths.index(self.raw_internal_path_in[0])
+        return np.stack([subject * m + column_a, subject * m + column_b, idx, thickness], axis=1).astype(np.int32)
+
+    def _checked_items(self, items):
+        items = np.ascontiguousarray(np.asarray(items))
+        if items.ndim != 2 or items.shape[1] != 4 or items.dtype != np.int32 or items.shape[0] < 1:
+            raise RuntimeError(f'DeviceSliceSet: an item table is int32 [n, 4] with n >= 1, got {items.dtype} {items.shape}')
+        return items
+
+    def load_epoch(self, items):
+        """Uploads the table into the persistent device table (rows past it are marked invalid) and puts the cursor back to row 0."""
+        self._need_device('load_epoch')
+        items = self._checked_items(items)
+        if items.shape[0] > self.items.shape[0]:
+            raise RuntimeError(f'DeviceSliceSet.load_epoch: {items.shape[0]} rows do not fit the device table of {self.items.shape[0]} (one per slice)')
+        self.items[:items.shape[0]].copy_(torch.from_numpy(items), non_blocking=False)
+        self.items[items.shape[0]:].fill_(-1)
+        self.rows = int(items.shape[0])
+        self.rewind()
+
+    def rewind(self):
+        self._need_device('rewind')
+        self.cursor.zero_()
+        self.position = 0
+
+    def _need_device(self, what):
+        if self.pool is None:
+            raise RuntimeError(f'DeviceSliceSet.{what}: this set was built with device=None (host-side tables only)')
+
+    def batch(self, first, count, out=None, dtype=torch.float32, use_cursor=False):
+        """``(A, B, slice_idx)`` of the rows ``[first, first + count)`` of the loaded epoch (counted from the cursor with ``use_cursor``)."""
+        self._need_device('batch')
+        first, count = int(first), int(count)
+        if not use_cursor and (count < 1 or first < 0 or first + count > self.rows):
+            raise RuntimeError(f'DeviceSliceSet.batch: rows [{first}, {first + count}) are not inside the loaded epoch of {self.rows} (load_epoch first)')
+        return assemble_batch(self.pool, self.vols, self.items, first, count, self.patch_shape[1:], slice_num=self.slice_num, min_value=self.min_value,
+                              max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None)
+
+    def batches(self, batch_size, drop_last=False, dtype=torch.float32):
+        """The loaded epoch batch by batch; the last batch is partial unless ``drop_last``, as the reference's loader leaves it."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise RuntimeError(f'DeviceSliceSet.batches: batch size {batch_size}')
+        for first in range(0, self.rows, batch_size):
+            count = min(batch_size, self.rows - first)
+            if count < batch_size and drop_last:
+                return
+            yield self.batch(first, count, dtype=dtype)
+
+    def host_batch(self, items, first, count, device=None):
+        """The same batch through ``SliceDataset(phase='train', thickness=[t])`` items, stacked and uploaded: the comparison arm of tests and
+        benchmark.  A row the kernel would refuse raises here."""
+        items = self._checked_items(items)
+        m = len(self.paths)
+        a, b, c = [], [], []
+        for vol_a, vol_b, idx, t in items[first:first + count].tolist():
+            subject, column_b = divmod(vol_b, m)
+            if not (0 <= vol_b < m * len(self.volumes)) or vol_a != subject * m + self.paths.index(self.raw_internal_path_in[0]):
+                raise RuntimeError(f'DeviceSliceSet.host_batch: row ({vol_a}, {vol_b}, {idx}, {t}) does not pair the input and an output of one subject')
+            key = (subject, column_b)
+            if key not in self._host_sets:
+                self._host_sets[key] = SliceDataset(self.volumes[subject], phase='train', patch_shape=self.patch_shape, stride_shape=(1, 1, 1),
+                                                    raw_internal_path_in=self.raw_internal_path_in[:1], raw_internal_path_out=[self.paths[column_b]],
+                                                    slice_num=self.slice_num, min_value=self.min_value, max_value=self.max_value)
+            ds = self._host_sets[key]
+            ds.thickness = [] if t == -1 else [t]
+            if not 0 <= idx < len(ds):
+                raise RuntimeError(f'DeviceSliceSet.host_batch: slice {idx} of a subject of {len(ds)}')
+            item = ds[idx]
+            a.append(item['A'])
+            b.append(item['B'])
+            c.append(torch.from_numpy(item['slice_idx']))
+        device = device if device is not None else (self.device if self.device is not None else 'cpu')
+        return torch.stack(a).to(device), torch.stack(b).to(device), torch.stack(c).to(device)
+
+
+def _label(step, slice_idx):
+    """The label as ``set_test_input`` hands it to the generator: ``slice_idx`` [B, 1], zeros for an unconditional one."""
+    return slice_idx if step.netG.c_dim > 0 else torch.zeros_like(slice_idx)
+
+
+def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None):
+    """The inner loop of the reference's train.py:45-77 over the epoch table ``items`` (``DeviceSliceSet.epoch_items``): per batch
+    ``total_iters += batch_size``, ``step.set_input(A, B, gen_c=slice_idx)``, ``step.optimize_parameters(cur_nimg=total_iters)`` and, when the step
+    has an EMA copy and ``ema_kimgs`` is given, ``step.update_ema(batch_size, total_iters, ema_kimgs, ramp)``.  The last batch is partial, as the
+    reference's loader leaves it.  ``where='device'``: the batches come from ``afcm_batch_assemble``, nothing is read back from the device;
+    ``where='host'``: from ``SliceDataset`` items (``DeviceSliceSet.host_batch``), the same bits.  Both arms draw ``gen_z`` in the same order
+    (``gen_z``: a fixed [batch_size, z_dim] tensor instead of a draw per batch).  Works with ``StyleGAN3GeneratorStep`` and ``StyleGAN3Step`` alike.
+    Returns the new ``total_iters``."""
+    if where not in ('device', 'host'):
+        raise ValueError(f"where must be 'device' or 'host', got {where!r}")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f'batch_size {batch_size}')
+    items = dataset._checked_items(items)
+    n = int(items.shape[0])
+    device = next(step.netG.parameters()).device
+    if where == 'device':
+        dataset.load_epoch(items)
+    for first in range(0, n, batch_size):
+        count = min(batch_size, n - first)
+        a, b, slice_idx = dataset.batch(first, count) if where == 'device' else dataset.host_batch(items, first, count, device=device)
+        total_iters += batch_size
+        step.set_input(a, b, gen_z=None if gen_z is None else gen_z[:count], gen_c=_label(step, slice_idx))
+        step.optimize_parameters(cur_nimg=total_iters)
+        if ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
+            step.update_ema(batch_size, total_iters, ema_kimgs=ema_kimgs, ramp=ramp)
+    return total_iters
+
+
+class TrainingGraph:
+    """One training step fed from the device as ONE graph: ``assemble_batch`` into persistent tensors at the cursor, ``advance_cursor(batch_size)``,
+    ``set_input``, ``optimize_parameters()`` -- ``stylegan3_model.capture_step``'s recipe (a side stream for warm-up and capture, a step built with
+    ``capturable=True`` and without gradient buckets) with the batch inside the graph.  ``dataset`` must have an epoch loaded (``load_epoch``) of at
+    least ``batch_size`` rows.  The warm-up runs real steps on the first rows, as ``capture_step``'s does, and leaves the cursor at row 0.
+
+    ``replay()`` refreshes ``gen_z`` in place (``normal_()``, outside the graph; not with ``fixed_z``) and replays: one asynchronous launch, no
+    synchronise.  It consumes ``batch_size`` rows and raises once fewer remain: the graph has ``drop_last`` geometry, so an epoch table should be a
+    multiple of ``batch_size`` long.  ``load_epoch`` may be called between replays (the table is refreshed in place); ``rewind()`` starts the same
+    table again.  The blur schedule and the EMA update stay on the host between replays, as with ``capture_step``.  ``gen_z``: the
+    initial (with ``fixed_z``: the only) latent batch; drawn when None."""
+
+    def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None):
+        if step.buckets is not None or not step.optimizer_G.capturable or not getattr(getattr(step, 'optimizer_D', None), 'capturable', True):
+            raise RuntimeError('TrainingGraph needs a single-process step built with capturable=True')
+        dataset._need_device('TrainingGraph')
+        batch_size = int(batch_size)
+        if batch_size < 1 or dataset.rows < batch_size:
+            raise RuntimeError(f'TrainingGraph: batch size {batch_size} with a loaded epoch of {dataset.rows} rows (load_epoch first)')
+        self.step, self.dataset, self.batch_size, self.fixed_z = step, dataset, batch_size, bool(fixed_z)
+        device = dataset.device
+        h, w = dataset.patch_shape[1:]
+        self.real_A = torch.empty((batch_size, dataset.slice_num, h, w), dtype=dtype, device=device)
+        self.real_B = torch.empty((batch_size, 1, h, w), dtype=dtype, device=device)
+        self.slice_idx = torch.empty((batch_size, 1), dtype=torch.float32, device=device)
+        self.gen_z = torch.randn([batch_size, step.netG.z_dim], device=device) if gen_z is None else gen_z.to(device).clone()
+        if tuple(self.gen_z.shape) != (batch_size, step.netG.z_dim):
+            raise RuntimeError(f'TrainingGraph: gen_z must be [{batch_size}, {step.netG.z_dim}], got {tuple(self.gen_z.shape)}')
+
+        def one():
+            dataset.batch(0, batch_size, out=(self.real_A, self.real_B, self.slice_idx), use_cursor=True)
+            advance_cursor(dataset.cursor, batch_size)
+            step.set_input(self.real_A, self.real_B, gen_z=self.gen_z, gen_c=_label(step, self.slice_idx))
+            step.optimize_parameters()
+
+        # warm-up and capture on one side stream, the step's first use of autograd: see capture_step
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                if dataset.position + batch_size > dataset.rows:
+                    dataset.rewind()
+                if not self.fixed_z:
+                    self.gen_z.normal_()
+                one()
+                dataset.position += batch_size
+            dataset.rewind()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=side, capture_error_mode='thread_local'):
+            one()
+
+    def load_epoch(self, items):
+        self.dataset.load_epoch(items)
+
+    def rewind(self):
+        self.dataset.rewind()
+
+    def replay(self):
+        if self.dataset.position + self.batch_size > self.dataset.rows:
+            raise RuntimeError(f'TrainingGraph.replay: {self.dataset.rows - self.dataset.position} rows remain of an epoch of {self.dataset.rows}, a batch '
+                               f'needs {self.batch_size}: load_epoch() or rewind()')
+        if not self.fixed_z:
+            self.gen_z.normal_()
+        self.graph.replay()
+        self.dataset.position += self.batch_size

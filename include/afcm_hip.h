@@ -605,6 +605,33 @@ int afcm_volume_ssim(double* layers, const void* ref, const void* test, int32_t 
                      int64_t test_stride_volume, int64_t test_stride_z, int64_t test_stride_y, int64_t test_stride_x, int32_t unit_map, double c1,
                      double c2, void* workspace, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Training batches (r10): data/cmsr_dataset.py:98-152 (__getitem__ of the train phase) for a batch of unrelated items, from a training set that
+ * lives on the device.  pool: every volume, pool_elems elements of src_dtype (AFCM_SRC_*).  vols: DEVICE int64 [n_vols][4] = element offset into
+ * pool, depth, hs, ws (rows contiguous, slices contiguous).  items: DEVICE int32 [n_items][4] = vol_a, vol_b, idx, thickness.  Sample i is table row
+ * r = (cursor ? cursor[0] : 0) + first + i; cursor is a DEVICE scalar, so a captured graph moves through the table with afcm_cursor_advance.
+ *   a [count][k][h][w]  the k planes of volume vol_a: k = 4: slices idx_a - t, idx_a, idx_a + t, idx_a + 2t with idx_a = (idx / t) * t; k = 1: slice idx.
+ *                       A position outside [0, depth - 1] is a plane of float64 zeros BEFORE normalisation.
+ *   b [count][1][h][w]  slice idx of volume vol_b.
+ *   slice_idx [count]   float32(idx - idx_a) / float32(t) (k = 1: idx_a = idx; "no thickness" is t = -1, which gives -0.0f).
+ * Crop / pad (per volume, from its own hs, ws), the normalisation in numpy's type for the source, the roundings and out_dtype are those of
+ * afcm_slice_assemble above; a and b are contiguous and both of out_dtype.
+ * The tables cannot be checked at launch, so the KERNEL checks every row before it reads the pool.  An item is invalid when its row is outside
+ * [0, n_items) (a cursor outside it included); vol_a or vol_b is outside [0, n_vols); a descriptor has a non-positive extent or an
+ * [offset, offset + depth hs ws) outside [0, pool_elems); the two descriptors' (depth, hs, ws) differ; idx is outside [0, depth); thickness is 0, or
+ * below 1 with k = 4.  An invalid item reads nothing from the pool, and every element of its a, its b and its label is NaN: no table content sends an
+ * access outside the pool (the tables themselves must be n_vols and n_items rows long).
+ * One launch covers a, b and the labels; a thread produces 16 bytes of one output row and stores them at once (element by element at the end of a row
+ * whose width is no multiple of the run, and in rows that do not start on a 16-byte boundary).  No atomics, no LDS, no allocation, no synchronise:
+ * both calls launch on `stream` and can be captured.  AFCM_E_INVALID: null pointers (only cursor may be null), unknown dtypes, count / h / w / n_vols /
+ * n_items / pool_elems < 1, first < 0, k not 1 or 4, max_value <= min_value, more than 2^31 - 1 workgroups; afcm_cursor_advance: a null cursor.
+ * ---------------------------------------------------------------------------------------- */
+int afcm_batch_assemble(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                        int32_t n_vols, const int32_t* items, int32_t n_items, const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h,
+                        int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream);
+/* cursor[0] += by, one thread on `stream` */
+int afcm_cursor_advance(int64_t* cursor, int64_t by, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

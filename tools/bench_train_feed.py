@@ -1,0 +1,212 @@
+"""Feeding the training step: what a batch of 16 x (4 + 1) planes at 256^2 costs the host way and the device way, and what the fed graph costs
+against the fixed-input one.  Three steps, each its own process (run each under its own time limit; chain them with && from a script):
+
+    python tools/bench_train_feed.py forms                 # no GPU: compiles csrc/batch.hip in both kernel forms into afcm_amd/csrc/variants/
+    python tools/bench_train_feed.py feed  [--repeats 5]   # (a) host arm against device arm, ms per batch; (b) the launch alone, both forms, device events
+    python tools/bench_train_feed.py step  [--repeats 3]   # TrainingGraph.replay() against capture_step's replay on fixed inputs, full-width bf16
+
+(a) alternates ``DeviceSliceSet.host_batch`` (SliceDataset items in numpy, stacked, uploaded) and ``DeviceSliceSet.batch`` (one launch) over the same
+rows of a synthetic uint8 set after a warm-up of each, the alternation repeated; wall time by a host clock ended by a synchronise.  (b) times
+``afcm_batch_assemble`` in the run form (16 bytes per thread and store) and the element form (one element per thread, as slice_assemble_kernel) from
+two builds of the one source file, per output byte, with ``afcm_slice_assemble`` on 16 x 4 x 256^2 fp32 beside them as the yardstick; the two forms'
+outputs are compared bit for bit.  No timing here is gated by a test; the numbers go to DESIGN section 8i with their spread."""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CSRC = os.path.join(ROOT, 'afcm_amd', 'csrc')
+VARIANTS = os.path.join(CSRC, 'variants')
+FORMS = {'run16': 16, 'element': 0}
+
+
+def forms(args):
+    os.makedirs(VARIANTS, exist_ok=True)
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    for name, run_bytes in FORMS.items():
+        out = os.path.join(VARIANTS, f'libbatch_{name}.so')
+        subprocess.check_call([hipcc, '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-ffp-contract=off', '-shared', f'-DAFCM_BATCH_RUN_BYTES={run_bytes}',
+                               os.path.join(CSRC, 'batch.hip'), os.path.join(CSRC, 'common.hip'), '-o', out])
+        print('built', os.path.relpath(out, ROOT))
+    return 0
+
+
+def synthetic_set(subjects, depth, res, device, **kw):
+    import torch
+    from afcm_amd import synthetic
+    from afcm_amd.training import DeviceSliceSet
+    to_u8 = lambda t: ((t + 1) * 127.5).round().clamp(0, 255).to(torch.uint8).numpy()
+    sources = [{'t1': to_u8(synthetic.mr_like_slices(depth, 1, res, seed=2 * s)[:, 0]), 't2': to_u8(synthetic.mr_like_slices(depth, 1, res, seed=2 * s + 1)[:, 0])}
+               for s in range(subjects)]
+    return DeviceSliceSet(sources, patch_shape=(1, res, res), raw_internal_path_in=['t1'], raw_internal_path_out=['t2'], thickness=[2, 3, 5], device=device, **kw)
+
+
+def spread(v):
+    return max(v) - min(v)
+
+
+def events_us(fn, launches=200):
+    import torch
+    for _ in range(5):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(launches):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / launches
+
+
+def feed(args):
+    import torch
+    from afcm_amd import _lib
+    from afcm_amd.torch_utils.ops.volume_ops import assemble_slices
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_train_feed.py needs a GPU: a time taken without one says nothing')
+    dev = torch.device('cuda:0')
+    ds = synthetic_set(args.subjects, args.depth, args.res, dev)
+    items = ds.epoch_items(0)
+    ds.load_epoch(items)
+    batches = min(args.batches, len(items) // args.batch)
+
+    def clock(arm):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for j in range(batches):
+            out = ds.batch(j * args.batch, args.batch) if arm == 'device' else ds.host_batch(items, j * args.batch, args.batch)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / batches, out
+
+    arms, last = {'host': [], 'device': []}, {}
+    for name in arms:
+        clock(name)
+    for _ in range(args.repeats):
+        for name in arms:
+            ms, last[name] = clock(name)
+            arms[name].append(ms)
+    equal = all(torch.equal(a, b) for a, b in zip(last['host'], last['device']))
+    print(f'training batches of {args.batch} x (4 + 1) planes at {args.res}^2 from {args.subjects} uint8 subjects of ({args.depth}, {args.res}, {args.res}), '
+          f'{batches} batches per pass, {args.repeats} repeats of the alternation after one warm-up pass of each arm')
+    stats = {}
+    for name, v in arms.items():
+        stats[name] = dict(per_repeat_ms=v, mean_ms=sum(v) / len(v), spread_ms=spread(v))
+        print(f'{name:8s} ms/batch per repeat {"  ".join(f"{x:8.4f}" for x in v)}   mean {stats[name]["mean_ms"]:8.4f}   spread {stats[name]["spread_ms"]:.4f}')
+    print(f'the two arms\' last batches are {"bit-identical" if equal else "DIFFERENT"}')
+
+    # the launch alone, both forms: the same call on the same tables through two builds of csrc/batch.hip
+    launches, outputs = {}, {}
+    for out_name, out_dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
+        a = torch.empty((args.batch, 4, args.res, args.res), dtype=out_dtype, device=dev)
+        b = torch.empty((args.batch, 1, args.res, args.res), dtype=out_dtype, device=dev)
+        c = torch.empty((args.batch, 1), dtype=torch.float32, device=dev)
+        out_bytes = a.numel() * a.element_size() + b.numel() * b.element_size()
+        for form in FORMS:
+            path = os.path.join(VARIANTS, f'libbatch_{form}.so')
+            if not os.path.exists(path):
+                raise SystemExit(f'{path} is missing: run `python tools/bench_train_feed.py forms` first')
+            lib = ctypes.CDLL(path)
+            res, argtypes = _lib.SIGNATURES['afcm_batch_assemble']
+            lib.afcm_batch_assemble.restype, lib.afcm_batch_assemble.argtypes = res, argtypes
+            stream = _lib.stream_ptr(a)
+
+            def launch():
+                rc = lib.afcm_batch_assemble(a.data_ptr(), b.data_ptr(), c.data_ptr(), ds.pool.data_ptr(), ds.pool.numel(), _lib.SRC_U8, ds.vols.data_ptr(),
+                                             int(ds.vols.shape[0]), ds.items.data_ptr(), int(ds.items.shape[0]), None, 0, args.batch, 4, args.res, args.res,
+                                             _lib.dtype_code(a), 0., 255., stream)
+                assert rc == 0, rc
+            us = [events_us(launch) for _ in range(args.repeats)]
+            launches[f'{form}_{out_name}'] = dict(per_repeat_us=us, mean_us=sum(us) / len(us), spread_us=spread(us), ns_per_kib=sum(us) / len(us) * 1e3 / (out_bytes / 1024))
+            outputs[(form, out_name)] = (a.clone(), b.clone(), c.clone())
+        same = all(torch.equal(x.view(torch.int16), y.view(torch.int16)) for x, y in zip(outputs[('run16', out_name)], outputs[('element', out_name)]))
+        equal = equal and same
+        print(f'{out_name}: the two forms\' outputs are {"bit-identical" if same else "DIFFERENT"}')
+    volume = ds.pool[:args.depth * args.res * args.res].view(args.depth, args.res, args.res)
+    us = [events_us(lambda: assemble_slices(volume, 0, args.batch, (1, args.res, args.res), thickness=5)) for _ in range(args.repeats)]
+    launches['slice_assemble_fp32'] = dict(per_repeat_us=us, mean_us=sum(us) / len(us), spread_us=spread(us),
+                                           ns_per_kib=sum(us) / len(us) * 1e3 / (args.batch * 4 * args.res * args.res * 4 / 1024))
+    for name, s in launches.items():
+        print(f'{name:22s} us per launch {"  ".join(f"{x:7.2f}" for x in s["per_repeat_us"])}   mean {s["mean_us"]:7.2f}   spread {s["spread_us"]:.2f}   '
+              f'{s["ns_per_kib"]:.3f} ns per KiB of output')
+    print(json.dumps(dict(bench='train_feed', res=args.res, batch=args.batch, arms=stats, launches=launches, equal=equal)))
+    return 0 if equal else 1
+
+
+def step(args):
+    import torch
+    from afcm_amd import layer_schedule as sched
+    from afcm_amd.networks_stylegan3 import Stylegan3Generator
+    from afcm_amd.stylegan3_model import StyleGAN3GeneratorStep, capture_step
+    from afcm_amd.training import TrainingGraph
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_train_feed.py needs a GPU: a time taken without one says nothing')
+    dev = torch.device('cuda:0')
+    ds = synthetic_set(args.subjects, args.depth, args.res, dev)
+    items = ds.epoch_items(0)
+    items = items[:len(items) // args.batch * args.batch]
+    ds.load_epoch(items)
+
+    def make_step():
+        torch.manual_seed(0)
+        G = Stylegan3Generator(z_dim=512, c_dim=1, w_dim=512, img_resolution=args.res, img_channels_in=4, img_channels_out=1, mapping_kwargs=dict(num_layers=8),
+                               synthesis_kwargs=dict(dict(sched.DEFAULT_SYNTHESIS_KWARGS), compute_dtype=torch.bfloat16)).to(dev)
+        return StyleGAN3GeneratorStep(G, capturable=True)
+
+    a, b, c = ds.batch(0, args.batch)
+    fixed = capture_step(make_step(), (a, b, torch.randn(args.batch, 512, device=dev), c), warmup=3)
+    fed = TrainingGraph(make_step(), ds, args.batch, warmup=3)
+
+    def replay_fed():
+        if ds.position + args.batch > ds.rows:
+            fed.rewind()
+        fed.replay()
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / args.steps
+
+    arms, fns = {'fixed': [], 'fed': []}, {'fixed': fixed.replay, 'fed': replay_fed}
+    for name in arms:
+        clock(fns[name])
+    for _ in range(args.repeats):
+        for name in arms:
+            arms[name].append(clock(fns[name]))
+    print(f'one generator step at {args.res}^2, batch {args.batch}, full-width bf16: capture_step replay on fixed inputs against TrainingGraph.replay() '
+          f'(batch assembled inside the graph, gen_z redrawn outside it), {args.steps} steps per pass, {args.repeats} repeats of the alternation after a warm-up pass')
+    stats = {}
+    for name, v in arms.items():
+        stats[name] = dict(per_repeat_ms=v, mean_ms=sum(v) / len(v), spread_ms=spread(v))
+        print(f'{name:6s} ms/step per repeat {"  ".join(f"{x:8.3f}" for x in v)}   mean {stats[name]["mean_ms"]:8.3f}   spread {stats[name]["spread_ms"]:.3f}')
+    diff, box = stats['fed']['mean_ms'] - stats['fixed']['mean_ms'], max(s['spread_ms'] for s in stats.values())
+    print(f'fed - fixed = {diff:+.3f} ms/step ({100 * diff / stats["fixed"]["mean_ms"]:+.2f} %), largest spread of an arm {box:.3f} ms: '
+          f'{"no difference" if abs(diff) <= box else "a difference"}')
+    print(json.dumps(dict(bench='train_feed_step', res=args.res, batch=args.batch, arms=stats, fed_minus_fixed_ms=diff, largest_spread_ms=box)))
+    return 0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('what', choices=['forms', 'feed', 'step'])
+    ap.add_argument('--subjects', type=int, default=4)
+    ap.add_argument('--depth', type=int, default=64)
+    ap.add_argument('--res', type=int, default=256)
+    ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--batches', type=int, default=8)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--repeats', type=int, default=3)
+    args = ap.parse_args()
+    return {'forms': forms, 'feed': feed, 'step': step}[args.what](args)
+
+
+if __name__ == '__main__':
+    sys.exit(main())
