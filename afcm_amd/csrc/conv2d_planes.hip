@@ -8,13 +8,19 @@ namespace afcm {
 // 4 consecutive elements as one vector access (8 B for 16-bit types, 16 B for fp32); planes are 4-element aligned when hw % 4 == 0
 template <typename T> struct Vec4 { T v[4]; } __attribute__((aligned(sizeof(T) * 4)));
 
-// y[plane, :] = x[plane, :] * scale[plane]  (dtype conversion fused).  HBM-bound elementwise pass.
+// An fp32 value the compiler must form as such.  Left alone it folds the float16 conversion of a product into v_fma_mixlo_f16(a, b, +0): ONE
+// rounding of the exact product, not the fp32 product rounded to nearest even (they differ where the fp32 product lands on a float16 tie),
+// and -0 + +0 = +0 loses the sign of a zero.
+__device__ __forceinline__ float formed_f32(float v) { asm("" : "+v"(v)); return v; }
+
+// y[plane, :] = x[plane, :] * scale[plane]: the fp32 product, rounded to nearest even into y's type.  HBM-bound elementwise pass.
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void scale_planes_kernel(TO* __restrict__ y, const TI* __restrict__ x, const float* __restrict__ scale,
                                                            long long planes, int hw) {
     const int per = (hw + 3) >> 2;
     const long long total = planes * per;
-    const bool vec = (hw & 3) == 0;
+    // vector accesses where every plane starts on a vector boundary of BOTH tensors (a contiguous view may sit at any element offset)
+    const bool vec = (hw & 3) == 0 && ((uintptr_t)x & (sizeof(TI) * 4 - 1)) == 0 && ((uintptr_t)y & (sizeof(TO) * 4 - 1)) == 0;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const long long plane = idx / per;
         const int i0 = (int)(idx - plane * per) << 2;
@@ -25,12 +31,12 @@ __global__ __launch_bounds__(256) void scale_planes_kernel(TO* __restrict__ y, c
             const Vec4<TI> in = *(const Vec4<TI>*)xp;
             Vec4<TO> out;
 #pragma unroll
-            for (int e = 0; e < 4; e++) out.v[e] = from_f32<TO>(to_f32(in.v[e]) * sc);
+            for (int e = 0; e < 4; e++) out.v[e] = from_f32<TO>(formed_f32(to_f32(in.v[e]) * sc));
             *(Vec4<TO>*)yp = out;
         } else {
 #pragma unroll
             for (int e = 0; e < 4; e++)
-                if (i0 + e < hw) yp[e] = from_f32<TO>(to_f32(xp[e]) * sc);
+                if (i0 + e < hw) yp[e] = from_f32<TO>(formed_f32(to_f32(xp[e]) * sc));
         }
     }
 }
@@ -381,7 +387,10 @@ __global__ __launch_bounds__(256) void plane_dot_rows_kernel(float* __restrict__
         }
     }
     const int nvec = (w + E - 1) / E, total = h * nvec;
-    const unsigned magic = (unsigned)((0x100000000ull + (unsigned)nvec - 1) / (unsigned)nvec);
+    // row = ic / nvec by the round-up reciprocal ceil(2^32 / nvec): never below the quotient and, ic < 2^31, at most one above it (from
+    // ic * (nvec * magic - 2^32) >= 2^32 on: 257 rows of 4092 vectors) -- a row that starts after ic steps back.  One vector per row
+    // (w == E) has no 32-bit reciprocal: row = ic.
+    const unsigned magic = nvec > 1 ? (unsigned)((0x100000000ull + (unsigned)nvec - 1) / (unsigned)nvec) : 0u;
     const T* ap = a + plane * h * lda;
     const T* bp = b ? b + plane * h * ldb : nullptr;
     float s0 = 0.f, s1 = 0.f;
@@ -392,7 +401,9 @@ __global__ __launch_bounds__(256) void plane_dot_rows_kernel(float* __restrict__
         for (int u = 0; u < 4; u++) {
             const int i = i0 + u * nthr;
             const int ic = i < total ? i : total - 1;
-            const int row = (int)__umulhi((unsigned)ic, magic), col = (ic - row * nvec) * E;
+            int row = nvec > 1 ? (int)__umulhi((unsigned)ic, magic) : ic;
+            row -= row * nvec > ic;
+            const int col = (ic - row * nvec) * E;
             const int colc = col + E <= w ? col : w - E;
             skip[u] = i < total ? col - colc : E;              // leading elements that an earlier vector already counted (E: none live)
             av[u].u = *(const uint4*)(ap + (size_t)row * lda + colc);

@@ -256,14 +256,17 @@ int afcm_conv2d_wgrad_plan(int32_t dtype, int32_t n, int32_t cin, int32_t cout, 
                            int32_t dy_pitch, int32_t x_pitch, int32_t dots, int32_t out[8]);
 
 /* y[plane, :] = x[plane, :] * scale[plane] with dtype conversion (style modulation s[n,i] of NET:46-47 and the
- * demodulation d[n,o] of NET:50-52 applied to activations instead of weights).  scale may be NULL (pure cast). */
+ * demodulation d[n,o] of NET:50-52 applied to activations instead of weights).  scale may be NULL (pure cast).  Every element is
+ * the fp32 product rounded once, to nearest even, into y's type (the sign of a zero kept).  x and y may sit at
+ * any element offset: 4-element vector accesses are taken only when hw % 4 == 0 and both bases are aligned to them. */
 int afcm_scale_planes(void* y, const void* x, const float* scale, int32_t dtype_in, int32_t dtype_out, int64_t planes,
                       int32_t hw, void* stream);
 
 /* out[plane] = sum_i a[plane,i] * b[plane,i]  (b == NULL: plain sum); fp32 accumulation.  Used for the style /
  * demodulation / bias gradients. */
 int afcm_plane_dot(float* out, const void* a, const void* b, int32_t dtype, int64_t planes, int32_t hw, void* stream);
-/* The same over planes of h rows x w columns with row pitches (elements; 0 = dense); padding columns are never read. */
+/* The same over planes of h rows x w columns with row pitches (elements; 0 = dense); padding columns are never read.  Rows of at
+ * least one 16-byte vector (w >= 16 / element size; w equal to it included), starting on 4-byte boundaries, h * max(pitch) < 2^27. */
 int afcm_plane_dot_ld(float* out, const void* a, const void* b, int32_t dtype, int64_t planes, int32_t h, int32_t w,
                       int32_t a_pitch, int32_t b_pitch, void* stream);
 /* The demodulation gradient's dot product by homogeneity (fused layer node, NET:41-57 backward): for a plane whose clamp_flags
