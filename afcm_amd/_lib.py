@@ -11,6 +11,8 @@ F32, F16, BF16 = 0, 1, 2
 E_NOKERNEL, E_INVALID = -1, -2
 SIGNS_NONE, SIGNS_WRITE, SIGNS_READ = 0, 1, 2
 SRC_U8, SRC_I16, SRC_F32, SRC_F64 = 0, 1, 2, 3
+SCHEDULE_SLOTS = 8
+EMA_LERP, EMA_COPY = 0, 1
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
@@ -136,6 +138,7 @@ SIGNATURES = {
     'afcm_adam_multi': (C.c_int, [_vp, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
     'afcm_adam_multi_capturable': (C.c_int, [_vp, _i32, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
     'afcm_adam_multi_capturable_d': (C.c_int, [_vp, _i32, _i64, _vp, C.c_double, C.c_double, C.c_double, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
+    'afcm_adam_multi_capturable_lr': (C.c_int, [_vp, _i32, _i64, _vp, _vp, C.c_double, C.c_double, _f32, _f32, _i32, _f32, _f32, _i32, _vp]),
     'afcm_plane_metrics_workspace_bytes': (C.c_int64, [_i64, _i32, _i32]),
     'afcm_plane_metrics': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _f64, _f64, _vp, _vp]),
     'afcm_volume_ssim_workspace_bytes': (C.c_int64, [_i64, _i32, _i32, _i32]),
@@ -144,6 +147,10 @@ SIGNATURES = {
     'afcm_halo_accumulate': (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _i32] + [_i32] * 17 + [_vp]),
     'afcm_batch_assemble': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp] + [_i32] * 6 + [_f64, _f64, _vp]),
     'afcm_cursor_advance': (C.c_int, [_vp, _i64, _vp]),
+    'afcm_schedule_advance': (C.c_int, [_vp, _i64, _f64, _f64, _f64, _f64, _vp]),
+    'afcm_gauss_blur_rmax': (C.c_int32, []),
+    'afcm_gauss_blur': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _f64, _vp, _vp]),
+    'afcm_ema_multi': (C.c_int, [_vp, _i32, _i64, _f64, _vp, _vp]),
 }
 
 

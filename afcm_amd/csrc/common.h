@@ -37,6 +37,8 @@ void set_error(const char* fmt, ...);
 
 static inline int hip_status(hipError_t e) { return e == hipSuccess ? AFCM_OK : 1000 + (int)e; }
 
+constexpr int kAdamChunk = 16384;      // elements per workgroup of the table-driven multi-tensor kernels (optim.hip, ema.hip)
+
 constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 constexpr int round_up(int a, int b) { return cdiv(a, b) * b; }
 

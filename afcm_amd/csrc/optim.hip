@@ -9,8 +9,6 @@
 
 namespace afcm {
 
-constexpr int kAdamChunk = 16384;      // elements per workgroup
-
 __device__ __forceinline__ float scrub(float g, float posinf, float neginf) {
     if (g != g) return 0.f;
     if (g == __builtin_inff()) return posinf;
@@ -21,11 +19,13 @@ __device__ __forceinline__ float scrub(float g, float posinf, float neginf) {
 __global__ __launch_bounds__(256) void adam_multi_kernel(const afcm_adam_entry* __restrict__ table, int n, float step_size, float beta1,
                                                          float beta2, float w1, float w2, float bc2_sqrt, float eps, float grad_scale, int do_scrub,
                                                          float posinf, float neginf, int write_grad, const float* __restrict__ step_dev, double lr,
-                                                         double beta1_d, double beta2_d) {
+                                                         double beta1_d, double beta2_d, const double* __restrict__ lr_dev) {
     // capturable form (step_dev != NULL): the step count lives on the device (adam_step_inc_kernel advances it), the bias corrections are
     // formed here, in double from the betas in double as the host forms them for afcm_adam_multi -- a launch captured into a hipGraph then
-    // replays with the right corrections at every step
+    // replays with the right corrections at every step.  lr_dev != NULL: the learning rate is a device scalar too (a slot of the schedule block,
+    // schedule.hip), so the same launch follows a learning-rate schedule
     if (step_dev != nullptr) {
+        if (lr_dev != nullptr) lr = lr_dev[0];
         const double t = (double)step_dev[0];
         const double bc1 = 1.0 - pow(beta1_d, t), bc2 = 1.0 - pow(beta2_d, t);
         step_size = (float)(lr / bc1);
@@ -101,7 +101,7 @@ extern "C" int afcm_adam_multi(const afcm_adam_entry* table_dev, int32_t n, int6
     AFCM_REQUIRE(bias_correction2_sqrt > 0.f, "adam_multi: bias_correction2_sqrt must be positive");
     hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, n, step_size, beta1,
                        beta2, one_minus_beta1, one_minus_beta2, bias_correction2_sqrt, eps, grad_scale, scrub, posinf, neginf, write_grad,
-                       (const float*)nullptr, 0.0, 0.0, 0.0);
+                       (const float*)nullptr, 0.0, 0.0, 0.0, (const double*)nullptr);
     return hip_status(hipGetLastError());
 }
 
@@ -109,13 +109,14 @@ namespace afcm { __global__ void adam_step_inc_kernel(float* step) { step[0] += 
 
 namespace afcm {
 static int adam_multi_capturable(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, double lr, double beta1, double beta2,
-                                 float w1, float w2, float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad, void* stream) {
+                                 float w1, float w2, float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad, void* stream,
+                                 const double* lr_dev = nullptr) {
     AFCM_REQUIRE(table_dev != nullptr && n > 0 && step_dev != nullptr, "adam_multi_capturable: empty table or no step counter");
     AFCM_REQUIRE(total_chunks > 0 && total_chunks < (1ll << 31), "adam_multi: %lld chunks is out of range", (long long)total_chunks);
     AFCM_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_multi_capturable: betas must lie in [0, 1)");
     hipLaunchKernelGGL(adam_step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
     hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, table_dev, n, 0.f, (float)beta1,
-                       (float)beta2, w1, w2, 1.f, eps, grad_scale, scrub, posinf, neginf, write_grad, (const float*)step_dev, lr, beta1, beta2);
+                       (float)beta2, w1, w2, 1.f, eps, grad_scale, scrub, posinf, neginf, write_grad, (const float*)step_dev, lr, beta1, beta2, lr_dev);
     return hip_status(hipGetLastError());
 }
 }  // namespace afcm
@@ -136,6 +137,14 @@ extern "C" int afcm_adam_multi_capturable_d(const afcm_adam_entry* table_dev, in
                                        scrub, posinf, neginf, write_grad, stream);
 }
 
+// afcm_adam_multi_capturable_d with the learning rate read from lr_dev[0] by the kernel
+extern "C" int afcm_adam_multi_capturable_lr(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, const double* lr_dev,
+                                             double beta1, double beta2, float eps, float grad_scale, int32_t scrub, float posinf, float neginf,
+                                             int32_t write_grad, void* stream) {
+    AFCM_REQUIRE(lr_dev != nullptr, "adam_multi_capturable_lr: null learning rate");
+    return afcm::adam_multi_capturable(table_dev, n, total_chunks, step_dev, 0.0, beta1, beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, grad_scale,
+                                       scrub, posinf, neginf, write_grad, stream, lr_dev);
+}
 
 // ---- the generator's L1 term (models/stylegan3_model.py:107: criterionL1(fake_B, real_B) * lambda_L1) ------------------------------------
 // torch.nn.L1Loss + the weight is sub, abs, mean, mul forward and four elementwise launches backward over a 4 MB image; here: per-workgroup

@@ -21,7 +21,7 @@ class FusedScrubAdam(torch.optim.Optimizer):
     captured into a graph: replays advance the device count only, ``device_step()`` reads it, and ``state_dict()`` writes it into
     ``state[p]['step']`` of the parameters the captured step updates, so a checkpoint taken after replays resumes at the right step."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, write_grad=False, capturable=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, write_grad=False, capturable=False, lr_dev=None):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
             raise ValueError('invalid Adam hyper-parameters')
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps))
@@ -32,6 +32,22 @@ class FusedScrubAdam(torch.optim.Optimizer):
         # device scalar only: `device_step()` is the count, and `state_dict()` copies it into state['step'] (see there)
         self.capturable = bool(capturable)
         self._step_dev = {}        # (group index, device) -> the count, a float32 device scalar; made at the group's first step from state['step']
+        # lr_dev: the learning rate as a float64 DEVICE scalar (a view of slot 4 or 5 of a DeviceSchedule block, afcm_amd/schedule.py) that the kernel
+        # reads at every launch, so that a captured step follows a learning-rate schedule; param_groups[...]['lr'] is then informational (set_lr)
+        if lr_dev is not None:
+            if not self.capturable:
+                raise ValueError('FusedScrubAdam: lr_dev needs capturable=True')
+            if not isinstance(lr_dev, torch.Tensor) or lr_dev.dtype != torch.float64 or lr_dev.numel() != 1 or lr_dev.device.type != 'cuda':
+                raise ValueError('FusedScrubAdam: lr_dev must be a float64 device tensor of one element')
+            if len(self.param_groups) != 1:
+                raise ValueError('FusedScrubAdam: lr_dev serves one parameter group')
+        self.lr_dev = lr_dev
+
+    def set_lr(self, lr):
+        """param_groups[...]['lr'] <- lr.  With ``lr_dev`` the kernel reads the device scalar, which its owner writes (``DeviceSchedule.set_lr``): this
+        keeps the informational copy in step with it."""
+        for group in self.param_groups:
+            group['lr'] = float(lr)
 
     def _state(self, p):
         st = self.state[p]
@@ -113,6 +129,13 @@ class FusedScrubAdam(torch.optim.Optimizer):
                 sd = self._step_dev.get(key)
                 if sd is None:
                     sd = self._step_dev[key] = torch.full([1], float(step_t - 1), dtype=torch.float32, device=dev)
+                if self.lr_dev is not None:
+                    _lib.launched(lib.afcm_adam_multi_capturable_lr(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, ctypes.c_void_p(sd.data_ptr()),
+                                                                  ctypes.c_void_p(self.lr_dev.data_ptr()), beta1, beta2, group['eps'], float(grad_scale),
+                                                                  int(self.scrub), self.posinf, self.neginf, int(self.write_grad),
+                                                                  _lib.stream_ptr(table)), 'adam_multi_capturable_lr')
+                    torch.autograd.graph.increment_version(touched)
+                    continue
                 _lib.launched(lib.afcm_adam_multi_capturable_d(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, ctypes.c_void_p(sd.data_ptr()), group['lr'],
                                                              beta1, beta2, group['eps'], float(grad_scale), int(self.scrub), self.posinf, self.neginf,
                                                              int(self.write_grad), _lib.stream_ptr(table)), 'adam_multi_capturable')
@@ -156,6 +179,21 @@ class FusedScrubAdam(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         self._step_dev = {}
         self._tables = {}
+
+    def snapshot(self):
+        """Clones of the moments and step counts as they stand (parameters that have not stepped yet have none): for ``restore``."""
+        moments = {p: {k: v.clone() for k, v in self.state[p].items()} for group in self.param_groups for p in group['params'] if p in self.state}
+        return moments, {key: t.clone() for key, t in self._step_dev.items()}
+
+    @torch.no_grad()
+    def restore(self, snapshot):
+        """Puts a ``snapshot`` back IN PLACE, so that pointer tables and a captured step stay valid; state made since the snapshot starts from zero."""
+        moments, counts = snapshot
+        for p, st in self.state.items():
+            for k, v in st.items():
+                v.copy_(moments[p][k]) if p in moments else v.zero_()
+        for key, t in self._step_dev.items():
+            t.copy_(counts[key]) if key in counts else t.zero_()
 
     def device_step(self, group=0):
         """The step count of a capturable optimizer (a device scalar; reading it synchronises)."""

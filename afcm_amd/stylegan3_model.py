@@ -21,13 +21,22 @@ import torch
 
 from .distributed import GradientBuckets
 from .torch_utils.ops import upfirdn2d
+from .torch_utils.ops.ema_ops import EmaTable
+from .torch_utils.ops.gauss_blur import gauss_blur
 from .optim import FusedScrubAdam, weighted_l1
 
 
 class StyleGAN3GeneratorStep:
     def __init__(self, netG, lr_G=0.0025, lambda_L1=100.0, distributed=False, bucket_bytes=25 * 1024 * 1024, style_mixing_prob=0,
-                 force_collectives=False, blur_init_sigma=0.0, blur_fade_kimg=0.0, ema=False, comm_dtype=None, eval_dtype='auto', capturable=False):
+                 force_collectives=False, blur_init_sigma=0.0, blur_fade_kimg=0.0, ema=False, comm_dtype=None, eval_dtype='auto', capturable=False, schedule=None):
         self.netG = netG
+        # `schedule`: a DeviceSchedule (afcm_amd/schedule.py).  The blur sigma, the EMA beta and the learning rates then live in its device block: _blur
+        # is gauss_blur(img, schedule=...), the optimizers read their rate from the block, optimize_parameters() ignores cur_nimg (the caller advances
+        # the schedule once per step) and update_ema() without arguments is one launch -- a captured step stays right while all three change
+        self.schedule = schedule
+        if schedule is not None and not capturable:
+            raise ValueError('a step with a schedule reads its learning rate on the device: build it with capturable=True')
+        self._ema_table = None
         # `ema`: keep the evaluation copy the reference creates unconditionally (models/comodgan_model.py:16-17); off by default
         # because the throughput path never reads it (234 MB)
         self.model_names = ['G']
@@ -51,7 +60,8 @@ class StyleGAN3GeneratorStep:
         self.G_synthesis = netG.synthesis
         # nan_to_num of every gradient + Adam(betas=(0, 0.99)) (stylegan3_model.py:132-135, comodgan_model.py:19-20) as one HIP launch
         # (capturable: step count and bias corrections on the device, so that optimize_parameters() can be captured into a hipGraph: capture_step())
-        self.optimizer_G = FusedScrubAdam(netG.parameters(), lr=lr_G, betas=(0.0, 0.99), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, capturable=capturable)
+        self.optimizer_G = FusedScrubAdam(netG.parameters(), lr=lr_G, betas=(0.0, 0.99), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, capturable=capturable,
+                                          lr_dev=None if schedule is None else schedule.lr_G_dev)
         self.criterionL1 = torch.nn.L1Loss()
         self.lambda_L1 = lambda_L1
         self.style_mixing_prob = style_mixing_prob
@@ -60,6 +70,17 @@ class StyleGAN3GeneratorStep:
         self.buckets = GradientBuckets(netG.parameters(), bucket_bytes=bucket_bytes, force=force_collectives, comm_dtype=comm_dtype) if distributed else None
         if self.buckets is not None:
             self.buckets.broadcast_parameters(netG)
+
+    def set_lr(self, lr_G, lr_D=None):
+        """The learning rates from here on (the reference's ``update_learning_rate``, once per epoch; ``lr_D`` defaults to ``lr_G``).  With a schedule
+        they are written into its device block, which the optimizer kernels read -- between replays, never inside a capture; without one into
+        ``param_groups``, which a graph captured earlier does not see."""
+        lr_D = lr_G if lr_D is None else lr_D
+        if self.schedule is not None:
+            self.schedule.set_lr(lr_G, lr_D)
+        self.optimizer_G.set_lr(lr_G)
+        if getattr(self, 'optimizer_D', None) is not None:
+            self.optimizer_D.set_lr(lr_D)
 
     def set_input(self, real_A, real_B, gen_z=None, gen_c=None):
         dev = next(self.netG.parameters()).device
@@ -99,8 +120,15 @@ class StyleGAN3GeneratorStep:
         """models/comodgan_model.py:118-126: evaluation forward under no_grad."""
         self.forward_ema()
 
-    def update_ema(self, batch_size, total_iters, ema_kimgs=10.0, ramp=None):
-        """The G_ema update of the reference's train loop (train.py:67-77)."""
+    def update_ema(self, batch_size=None, total_iters=None, ema_kimgs=10.0, ramp=None):
+        """The G_ema update of the reference's train loop (train.py:67-77).  Without arguments, on a step with a schedule: one launch over every
+        parameter and buffer with the beta of the schedule block (torch_utils/ops/ema_ops.py); it can be captured once it has run eagerly."""
+        if batch_size is None and total_iters is None:
+            if self.schedule is None or self.netG_ema is None:
+                raise RuntimeError('update_ema() without arguments needs a step built with schedule=... and ema=True')
+            if self._ema_table is None:                      # (update() itself refuses tensors that have moved)
+                self._ema_table = EmaTable(self.netG_ema, self.netG)
+            return self._ema_table.update(schedule=self.schedule)
         return update_ema(self.netG_ema, self.netG, batch_size, total_iters, ema_kimgs, ramp)
 
     def save_networks(self, epoch, save_dir):
@@ -126,7 +154,9 @@ class StyleGAN3GeneratorStep:
 
     def _blur(self, img):
         """Gaussian blur of the loss inputs while blur_sigma > 0 (models/stylegan3_model.py:97-103): 2*floor(3 sigma)+1 taps,
-        separable, through the HIP upfirdn2d kernel (filter2d)."""
+        separable, through the HIP upfirdn2d kernel (filter2d).  With a schedule: the blur kernels, sigma from the device block."""
+        if self.schedule is not None:
+            return gauss_blur(img, schedule=self.schedule)
         blur_size = np.floor(self.blur_sigma * 3)
         if blur_size <= 0:
             return img
@@ -141,8 +171,8 @@ class StyleGAN3GeneratorStep:
 
     def optimize_parameters(self, cur_nimg=None):
         """G half of models/stylegan3_model.py:113-135.  `cur_nimg` drives the blur fade as in the reference (:115-116);
-        None keeps the current blur_sigma."""
-        if cur_nimg is not None:
+        None keeps the current blur_sigma.  A step with a schedule ignores it: sigma is the schedule block's."""
+        if cur_nimg is not None and self.schedule is None:
             self.blur_sigma = (max(1 - cur_nimg / (self.blur_fade_kimg * 1e3), 0) * self.blur_init_sigma) if self.blur_fade_kimg > 0 else 0.0
         ev = getattr(self, 'phase_events', None)      # a dict: record CUDA events at the phase boundaries of THIS step (bench.py's bucket timeline)
         mark = (lambda k: ev.__setitem__(k, _recorded_event())) if ev is not None else (lambda k: None)
@@ -229,7 +259,8 @@ class StyleGAN3Step(StyleGAN3GeneratorStep):
         self.lambda_r1 = float(lambda_r1)
         self.combine_ab = bool(combine_ab)
         self.optimizer_D = FusedScrubAdam(netD.parameters(), lr=lr_D, betas=(0.0, 0.99), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5,
-                                          capturable=kw.get('capturable', False))
+                                          capturable=kw.get('capturable', False),
+                                          lr_dev=None if kw.get('schedule') is None else kw['schedule'].lr_D_dev)
         self.buckets_D = None
         if self.buckets is not None:
             self.buckets_D = GradientBuckets(netD.parameters(), bucket_bytes=kw.get('bucket_bytes', 25 * 1024 * 1024),
@@ -265,7 +296,7 @@ class StyleGAN3Step(StyleGAN3GeneratorStep):
         super().backward_G(extra_loss=self.loss_G_GAN if extra_loss is None else self.loss_G_GAN + extra_loss)
 
     def optimize_parameters(self, cur_nimg=None):
-        if cur_nimg is not None:
+        if cur_nimg is not None and self.schedule is None:
             self.blur_sigma = (max(1 - cur_nimg / (self.blur_fade_kimg * 1e3), 0) * self.blur_init_sigma) if self.blur_fade_kimg > 0 else 0.0
         # update D
         self.optimizer_D.zero_grad(set_to_none=True)

@@ -210,13 +210,19 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     device = next(step.netG.parameters()).device
     if where == 'device':
         dataset.load_epoch(items)
+    schedule = getattr(step, 'schedule', None) if where == 'device' else None
     for first in range(0, n, batch_size):
         count = min(batch_size, n - first)
         a, b, slice_idx = dataset.batch(first, count) if where == 'device' else dataset.host_batch(items, first, count, device=device)
         total_iters += batch_size
+        if schedule is not None:                            # the two calls TrainingGraph captures, eagerly: total_iters, sigma and beta are the block's
+            schedule.advance(batch_size)
         step.set_input(a, b, gen_z=None if gen_z is None else gen_z[:count], gen_c=_label(step, slice_idx))
         step.optimize_parameters(cur_nimg=total_iters)
-        if ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
+        if schedule is not None:
+            if schedule.ema_kimgs is not None and step.netG_ema is not None:
+                step.update_ema()
+        elif ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
             step.update_ema(batch_size, total_iters, ema_kimgs=ema_kimgs, ramp=ramp)
     return total_iters
 
@@ -230,10 +236,14 @@ class TrainingGraph:
     ``replay()`` refreshes ``gen_z`` in place (``normal_()``, outside the graph; not with ``fixed_z``) and replays: one asynchronous launch, no
     synchronise.  It consumes ``batch_size`` rows and raises once fewer remain: the graph has ``drop_last`` geometry, so an epoch table should be a
     multiple of ``batch_size`` long.  ``load_epoch`` may be called between replays (the table is refreshed in place); ``rewind()`` starts the same
-    table again.  The blur schedule and the EMA update stay on the host between replays, as with ``capture_step``.  ``gen_z``: the
-    initial (with ``fixed_z``: the only) latent batch; drawn when None."""
+    table again.  The blur schedule and the EMA update stay on the host between replays, as with ``capture_step`` -- unless the step was built with
+    a ``DeviceSchedule`` (afcm_amd/schedule.py): then the captured body begins with ``schedule.advance(batch_size)`` and, when the step has an EMA copy
+    and the schedule an ``ema_kimgs``, ends with ``step.update_ema()``; sigma, beta and the learning rates are read from the schedule block at every
+    replay, and the warm-up leaves the block as it found it.  ``undo_warmup=True`` puts the networks' parameters and buffers and the optimizers' state
+    back as well (in place: the graph keeps pointing at them), so that the warm-up's real steps leave no trace; the default keeps them, as
+    ``capture_step`` does.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None."""
 
-    def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None):
+    def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None, undo_warmup=False):
         if step.buckets is not None or not step.optimizer_G.capturable or not getattr(getattr(step, 'optimizer_D', None), 'capturable', True):
             raise RuntimeError('TrainingGraph needs a single-process step built with capturable=True')
         dataset._need_device('TrainingGraph')
@@ -250,12 +260,24 @@ class TrainingGraph:
         if tuple(self.gen_z.shape) != (batch_size, step.netG.z_dim):
             raise RuntimeError(f'TrainingGraph: gen_z must be [{batch_size}, {step.netG.z_dim}], got {tuple(self.gen_z.shape)}')
 
+        schedule = getattr(step, 'schedule', None)
+        ema_inside = schedule is not None and schedule.ema_kimgs is not None and step.netG_ema is not None
+
         def one():
+            if schedule is not None:
+                schedule.advance(batch_size)
             dataset.batch(0, batch_size, out=(self.real_A, self.real_B, self.slice_idx), use_cursor=True)
             advance_cursor(dataset.cursor, batch_size)
             step.set_input(self.real_A, self.real_B, gen_z=self.gen_z, gen_c=_label(step, self.slice_idx))
             step.optimize_parameters()
+            if ema_inside:
+                step.update_ema()
 
+        saved = None if schedule is None else schedule.block.clone()
+        optimizers = [opt for opt in (step.optimizer_G, getattr(step, 'optimizer_D', None)) if opt is not None]
+        if undo_warmup:
+            tensors = [t for name in step.model_names for net in [getattr(step, 'net' + name)] for t in list(net.parameters()) + list(net.buffers())]
+            before = [t.detach().clone() for t in tensors], [opt.snapshot() for opt in optimizers]
         # warm-up and capture on one side stream, the step's first use of autograd: see capture_step
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -268,6 +290,14 @@ class TrainingGraph:
                 one()
                 dataset.position += batch_size
             dataset.rewind()
+            if saved is not None:
+                schedule.block.copy_(saved)               # the warm-up's steps are real ones, but total_iters stays where it was
+            if undo_warmup:
+                with torch.no_grad():
+                    for t, v in zip(tensors, before[0]):
+                        t.copy_(v)
+                for opt, state in zip(optimizers, before[1]):
+                    opt.restore(state)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -288,3 +318,46 @@ class TrainingGraph:
             self.gen_z.normal_()
         self.graph.replay()
         self.dataset.position += self.batch_size
+
+
+def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True, on_epoch=None, gen_z=None):
+    """The outer loop of the reference's train.py:38-45 for a step built with a ``DeviceSchedule``.  ``epochs``: an iterable of epoch numbers
+    (``range(epoch_count, n_epochs + n_epochs_decay + 1)``).  Per epoch: ``step.set_lr(lr_schedule.lr_at(k))`` for G and D, k = 1 for the first
+    (``update_learning_rate()`` at the top of every epoch); ``dataset.epoch_items(rng)`` and ``load_epoch``; then replays of ONE ``TrainingGraph``
+    built in the first epoch (``graph=False``: eager steps, the same kernels) until fewer than ``batch_size`` rows remain; ``on_epoch(epoch, step)``
+    -- validation and checkpoints are the caller's, through ``validation.validate`` and ``step.save_networks``.  ``rng``: a seed or a
+    ``numpy.random.Generator``; an int seeds one generator for the whole run.  ``gen_z``: one fixed [batch_size, z_dim] latent batch for every step
+    instead of a draw per step.  The graph is built with ``undo_warmup=True``, so the run is the same steps on the same rows with and
+    without the graph.  Returns the number of steps run."""
+    schedule = getattr(step, 'schedule', None)
+    if schedule is None:
+        raise RuntimeError('train_epochs needs a step built with schedule=DeviceSchedule(...)')
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f'batch_size {batch_size}')
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    ema = schedule.ema_kimgs is not None and step.netG_ema is not None
+    runner, steps = None, 0
+    for k, epoch in enumerate(epochs, start=1):
+        lr = lr_schedule.lr_at(k)
+        step.set_lr(lr, lr)
+        items = dataset.epoch_items(rng)
+        dataset.load_epoch(items)
+        if dataset.rows < batch_size:
+            raise RuntimeError(f'train_epochs: an epoch of {dataset.rows} rows is shorter than a batch of {batch_size}')
+        if graph and runner is None:
+            runner = TrainingGraph(step, dataset, batch_size, fixed_z=gen_z is not None, gen_z=gen_z, undo_warmup=True)
+        for first in range(0, dataset.rows - batch_size + 1, batch_size):
+            if graph:
+                runner.replay()
+            else:
+                schedule.advance(batch_size)
+                a, b, slice_idx = dataset.batch(first, batch_size)
+                step.set_input(a, b, gen_z=gen_z, gen_c=_label(step, slice_idx))
+                step.optimize_parameters()
+                if ema:
+                    step.update_ema()
+            steps += 1
+        if on_epoch is not None:
+            on_epoch(epoch, step)
+    return steps

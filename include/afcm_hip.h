@@ -342,6 +342,10 @@ int afcm_adam_multi_capturable(const afcm_adam_entry* table_dev, int32_t n, int6
  * 1.f - beta*, which moves exp_avg_sq by 1.7e-5 relative at beta2 = 0.999 and by 9e-7 at 0.99; it stays for its callers. */
 int afcm_adam_multi_capturable_d(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, double lr, double beta1, double beta2,
                                  float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad, void* stream);
+/* The same with the learning rate on the DEVICE: the kernel reads lr_dev[0] (a double: slot 4 or 5 of the schedule block below), so one captured launch
+ * follows a learning-rate schedule.  Everything else is afcm_adam_multi_capturable_d, bit for bit.  AFCM_E_INVALID: as there, and a null lr_dev. */
+int afcm_adam_multi_capturable_lr(const afcm_adam_entry* table_dev, int32_t n, int64_t total_chunks, float* step_dev, const double* lr_dev, double beta1,
+                                  double beta2, float eps, float grad_scale, int32_t scrub, float posinf, float neginf, int32_t write_grad, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The style affine layers of all SynthesisLayers at once (NET:349-352 `styles = self.affine(cat(w, global_w))`, FullyConnectedLayer
@@ -634,6 +638,51 @@ int afcm_batch_assemble(void* a, void* b, float* slice_idx, const void* pool, in
                         int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream);
 /* cursor[0] += by, one thread on `stream` */
 int afcm_cursor_advance(int64_t* cursor, int64_t by, void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * The training loop's time-dependent scalars on the device (r11), so that ONE captured graph stays right for a whole run.
+ * The schedule block is a DEVICE array of 8 doubles:
+ *   [0] total_iters  images seen: the reference's total_iters / cur_nimg (train.py:50-53), exact in a double
+ *   [1] blur_sigma   models/stylegan3_model.py:115-116: max(1 - cur_nimg / (blur_fade_kimg * 1e3), 0) * blur_init_sigma, 0 when blur_fade_kimg <= 0
+ *   [2] blur_radius  floor(3 * blur_sigma) (models/stylegan3_model.py:97-98)
+ *   [3] ema_beta     train.py:67-77: 0.5 ** (batch / max(ema_nimg, 1e-8)), ema_nimg = ema_kimgs * 1000, with a ramp min(ema_nimg, total_iters * ramp)
+ *   [4] lr_G  [5] lr_D   written by the host only (models/utils.py:43-69: one scheduler step per epoch, train.py:44)
+ *   [6] [7]          spare, kept zero
+ * afcm_schedule_advance: one thread; total_iters += batch, then slots 1-3 from the new total_iters in that order.  ema_ramp < 0: no ramp.  Slots 1 and 2
+ * use + - x / floor max in double only (the library is built without contraction): bit-equal to the Python expressions; pow may differ from the
+ * host's by rounding.  AFCM_E_INVALID: a null block, batch < 1.
+ *
+ * afcm_gauss_blur: the blur of models/stylegan3_model.py:24-30, 97-103 on fp32 planes x [planes][h][w] -> y, same size: f = exp2(-(i / sigma)^2) for i in
+ * [-r, r], r = floor(3 sigma), normalised by its sum (taps formed in fp32 in the kernel: the division by (float)sigma, exp2f, a sum), applied along x
+ * into `scratch` (planes * h * w floats, the caller's) and then along y, zero padding r on each side (upfirdn2d.filter2d with a 1-D filter).  block
+ * == NULL: sigma is the argument; otherwise sigma and radius are slots 1 and 2 of the block when the kernels RUN and the argument is ignored.  The
+ * two launches' geometry depends on neither.  Radius 0: y = x bit for bit, nothing is divided by sigma.  A block radius outside
+ * [0, afcm_gauss_blur_rmax()] cannot be raised from the device: every element of y is NaN.  A NaN input reaches its (2r + 1)^2 window and nothing else.
+ * No atomics.  scratch may be null where the host sigma has radius 0.  AFCM_E_INVALID: null y / x / scratch or two of them equal, extents < 1, a host sigma that is negative, NaN or whose radius exceeds
+ * the cap, more than 2^31 - 1 workgroups.
+ *
+ * afcm_ema_multi: train.py:74-77 for every tensor of the generator in one launch.  `table` is a DEVICE array of n rows sorted by chunk0, chunks of
+ * afcm_adam_chunk_elems() units as in afcm_adam_multi.  AFCM_EMA_LERP: dst = p_ema, src = p, fp32, numel elements: p_ema <- p.lerp(p_ema, beta) in
+ * torch's form -- w = (float)beta, d = p_ema - p: w < 0.5f ? fmaf(w, d, p) : fmaf(-d, 1.f - w, p_ema).  AFCM_EMA_COPY: numel BYTES from src to dst (a
+ * buffer of any dtype).  16-byte accesses when both pointers of a row are 16-byte aligned, element by element otherwise and at a row's tail.  beta is
+ * the argument or, with a block, its slot 3 when the kernel runs.  AFCM_E_INVALID: an empty table, total_chunks outside [1, 2^31), a host beta
+ * outside [0, 1].
+ * ---------------------------------------------------------------------------------------- */
+#define AFCM_SCHEDULE_SLOTS 8
+#define AFCM_EMA_LERP 0
+#define AFCM_EMA_COPY 1
+typedef struct afcm_ema_entry {
+    void*       dst;
+    const void* src;
+    int64_t     numel;     /* elements (AFCM_EMA_LERP) or bytes (AFCM_EMA_COPY), > 0 */
+    int64_t     chunk0;
+    int32_t     kind;
+    int32_t     reserved;
+} afcm_ema_entry;
+int afcm_schedule_advance(double* block, int64_t batch, double blur_init_sigma, double blur_fade_kimg, double ema_kimgs, double ema_ramp, void* stream);
+int32_t afcm_gauss_blur_rmax(void);
+int afcm_gauss_blur(float* y, const float* x, float* scratch, int64_t planes, int32_t h, int32_t w, double sigma, const double* block, void* stream);
+int afcm_ema_multi(const afcm_ema_entry* table, int32_t n, int64_t total_chunks, double beta, const double* block, void* stream);
 
 #ifdef __cplusplus
 }
