@@ -151,6 +151,9 @@ SIGNATURES = {
     'afcm_gauss_blur_rmax': (C.c_int32, []),
     'afcm_gauss_blur': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _f64, _vp, _vp]),
     'afcm_ema_multi': (C.c_int, [_vp, _i32, _i64, _f64, _vp, _vp]),
+    'afcm_rescale_plan': (C.c_int, [_i64, _i32, C.POINTER(_i32)]),
+    'afcm_rescale_workspace_bytes': (C.c_int64, [_i64, _i32]),
+    'afcm_rescale_intensity': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _f64, _f64, _vp]),
 }
 
 

@@ -11,7 +11,9 @@ import numpy as np
 import torch
 
 from .data import SliceDataset, open_volumes
+from .intensity import rescale_intensity_host
 from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch
+from .torch_utils.ops.intensity_ops import percentile_fractions, rescale_intensity
 
 _NUMPY_SOURCES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int16): torch.int16, np.dtype(np.float32): torch.float32,
                   np.dtype(np.float64): torch.float64}
@@ -23,10 +25,13 @@ class DeviceSliceSet:
     ``sources``: one mapping ``{internal path: ndarray [D, Hs, Ws]}`` or HDF5 file name per subject, as ``SliceDataset`` takes them.  The volumes of
     ``raw_internal_path_in[0]`` and of every output modality are uploaded uncropped (the kernel crops / pads each to ``patch_shape[1:]`` from its own
     extent) into one 1-D tensor of their common dtype; ``vols`` int64 [subjects * modalities, 4] holds (element offset, depth, hs, ws).
-    ``device=None`` builds the host-side tables only (``epoch_items`` and ``host_batch`` work, nothing is uploaded)."""
+    ``device=None`` builds the host-side tables only (``epoch_items`` and ``host_batch`` work, nothing is uploaded).
+    ``rescale=(q_lo, q_hi)``: the sources are raw scanner volumes; each is uploaded as it is and passed through ``rescale_intensity`` with those
+    percentiles into a uint8 pool, volume by volume, so the subjects' raw dtypes may differ; ``host_batch`` rescales with
+    ``rescale_intensity_host``, the same bits.  None: the volumes are pooled as they are."""
 
     def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
-                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda'):
+                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None):
         if phase not in ('train', 'val', 'test'):
             raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
         if cat_inputs:
@@ -49,12 +54,16 @@ class DeviceSliceSet:
         self.volumes = [open_volumes(s, self.paths) for s in sources]
         if not self.volumes:
             raise RuntimeError('DeviceSliceSet: no subjects')
+        self.rescale = None if rescale is None else tuple(float(q) for q in rescale)
+        if self.rescale is not None:
+            percentile_fractions(self.rescale, 'DeviceSliceSet: rescale')
         dtypes = sorted({str(v.dtype) for subject in self.volumes for v in subject.values()})
-        if len(dtypes) != 1:
+        if self.rescale is None and len(dtypes) != 1:
             raise RuntimeError(f'DeviceSliceSet: mixed source dtypes {dtypes}: the pool holds one dtype, convert the volumes first')
-        self.source_dtype = np.dtype(dtypes[0])
-        if self.source_dtype not in _NUMPY_SOURCES:
-            raise RuntimeError(f'DeviceSliceSet: source volumes are uint8 / int16 / float32 / float64, got {self.source_dtype}')
+        for name in dtypes:
+            if np.dtype(name) not in _NUMPY_SOURCES:
+                raise RuntimeError(f'DeviceSliceSet: source volumes are uint8 / int16 / float32 / float64, got {name}')
+        self.source_dtype = np.dtype(np.uint8) if self.rescale is not None else np.dtype(dtypes[0])
         rows, offset, self.depths = [], 0, []
         for s, subject in enumerate(self.volumes):
             shapes = {p: tuple(int(n) for n in subject[p].shape) for p in self.paths}
@@ -72,15 +81,22 @@ class DeviceSliceSet:
         # (subject, idx) of every slice in serial order, and where each subject's first row lies
         self._subject = np.repeat(np.arange(len(self.depths), dtype=np.int64), self.depths)
         self._idx = np.concatenate([np.arange(d, dtype=np.int64) for d in self.depths])
-        self._host_sets = {}
+        self._host_sets, self._host_rescaled = {}, {}
         self.device = None if device is None else torch.device(device)
         self.pool = self.vols = self.items = self.cursor = None
         self.rows = self.position = 0
         if self.device is not None:
             if self.device.type != 'cuda':
                 raise RuntimeError(f'DeviceSliceSet needs a ROCm device (got {self.device}); device=None builds the host-side tables only')
-            pool = np.concatenate([np.ascontiguousarray(subject[p]).reshape(-1) for subject in self.volumes for p in self.paths])
-            self.pool = torch.from_numpy(pool).to(self.device)                           # the one upload of the training set
+            if self.rescale is None:
+                pool = np.concatenate([np.ascontiguousarray(subject[p]).reshape(-1) for subject in self.volumes for p in self.paths])
+                self.pool = torch.from_numpy(pool).to(self.device)                       # the one upload of the training set
+            else:
+                self.pool = torch.empty(self.pool_elems, dtype=torch.uint8, device=self.device)
+                raw = [subject[p] for subject in self.volumes for p in self.paths]
+                for (at, d, hs, ws), v in zip(rows, raw):                                # each volume raw, rescaled into its place in the pool
+                    rescale_intensity(torch.from_numpy(np.ascontiguousarray(v)).to(self.device), self.rescale,
+                                      out=self.pool[at:at + d * hs * ws].view(d, hs, ws))
             self.vols = torch.from_numpy(self.vols_host).to(self.device)
             # persistent (a captured graph holds their addresses): the epoch's table, refreshed in place, and the row a graph's next batch starts at
             self.items = torch.full((len(self), 4), -1, dtype=torch.int32, device=self.device)
@@ -160,6 +176,14 @@ class DeviceSliceSet:
                 return
             yield self.batch(first, count, dtype=dtype)
 
+    def _host_volumes(self, subject):
+        """The subject's volumes as the pool holds them: as given, or rescaled by the host function."""
+        if self.rescale is None:
+            return self.volumes[subject]
+        if subject not in self._host_rescaled:
+            self._host_rescaled[subject] = {p: rescale_intensity_host(v, self.rescale)[0] for p, v in self.volumes[subject].items()}
+        return self._host_rescaled[subject]
+
     def host_batch(self, items, first, count, device=None):
         """The same batch through ``SliceDataset(phase='train', thickness=[t])`` items, stacked and uploaded: the comparison arm of tests and
         benchmark.  A row the kernel would refuse raises here."""
@@ -172,7 +196,7 @@ class DeviceSliceSet:
                 raise RuntimeError(f'DeviceSliceSet.host_batch: row ({vol_a}, {vol_b}, {idx}, {t}) does not pair the input and an output of one subject')
             key = (subject, column_b)
             if key not in self._host_sets:
-                self._host_sets[key] = SliceDataset(self.volumes[subject], phase='train', patch_shape=self.patch_shape, stride_shape=(1, 1, 1),
+                self._host_sets[key] = SliceDataset(self._host_volumes(subject), phase='train', patch_shape=self.patch_shape, stride_shape=(1, 1, 1),
                                                     raw_internal_path_in=self.raw_internal_path_in[:1], raw_internal_path_out=[self.paths[column_b]],
                                                     slice_num=self.slice_num, min_value=self.min_value, max_value=self.max_value)
             ds = self._host_sets[key]

@@ -11,7 +11,9 @@ import torch
 
 from . import evaluation
 from .data import SliceDataset, open_volumes
+from .intensity import rescale_intensity_host
 from .predictor import SlidingWindowPredictor, patch_indices, validate_halo
+from .torch_utils.ops.intensity_ops import percentile_fractions, rescale_intensity
 from .torch_utils.ops.plane_metrics import plane_stats
 from .torch_utils.ops.volume_metrics import volume_ssim_layers
 from .torch_utils.ops.volume_ops import assemble_slices, halo_accumulate
@@ -118,13 +120,16 @@ def _input_head(real_A):
 
 @torch.no_grad()
 def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4, patch_hw, batch_size, patch_halo=(0, 8, 8), heads=('prediction',),
-                   where='device', min_value=0., max_value=255.):
+                   where='device', min_value=0., max_value=255., rescale=None):
     """One subject through the EMA generator: ``source`` (a mapping {internal path: array [D, Hs, Ws]} or an HDF5 file name) -> {head: [C, D, H, W]}
     with ``heads`` out of 'prediction' (``fake_B``) and 'input' (the thick slice each target falls into).  ``step`` needs
     ``set_test_input(real_A, slice_idx)``, ``test()``, ``real_A`` and ``fake_B`` [B, C, H, W] (``StyleGAN3GeneratorStep`` built with ``ema=True``).
     ``patch_hw`` = (H, W): every slice is centre-cropped / padded to it, so the volume is (D, H, W) and a patch is one whole slice; ``thickness`` is
     the slice thickness of the input (None only with ``slice_num`` 1).  ``where='device'`` returns device tensors and reads nothing back inside the
-    loop; ``where='host'`` returns CPU tensors, the same bits.  Both arms draw ``gen_z`` batch by batch in the same order."""
+    loop; ``where='host'`` returns CPU tensors, the same bits.  Both arms draw ``gen_z`` batch by batch in the same order.
+    ``rescale=(q_lo, q_hi)``: the source is a raw scanner volume and goes through ``intensity.rescale_intensity`` with those percentiles first -- on
+    the device after the upload (``where='device'``, still no host read) or through ``rescale_intensity_host`` -- so the loop sees a uint8 volume, the
+    same one in both arms.  None: the source is taken as it is."""
     if where not in ('device', 'host'):
         raise ValueError(f"where must be 'device' or 'host', got {where!r}")
     heads = tuple(heads)
@@ -136,12 +141,16 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
         raise ValueError(f'batch_size {batch_size}')
     patch_shape, stride_shape = (1, int(patch_hw[0]), int(patch_hw[1])), (1, 1, 1)      # one patch per slice: the y / x strides never come into play
     validate_halo(patch_halo, patch_shape, stride_shape)
+    if rescale is not None:
+        percentile_fractions(rescale, 'predict_volume: rescale')
     out_channels = {}
 
     def channels(head, t):                                    # the map's channel count is the head's, known at the first batch
         return out_channels.setdefault(head, int(t.shape[1]))
 
     if where == 'host':
+        if rescale is not None:
+            source = {path: rescale_intensity_host(open_volumes(source, [path])[path], rescale)[0]}
         ds = SliceDataset(source, phase='test', patch_shape=patch_shape, stride_shape=stride_shape, raw_internal_path_in=[path], raw_internal_path_out=[path],
                           thickness=[] if thickness is None else [thickness], slice_num=slice_num, min_value=min_value, max_value=max_value)
         volume_shape = tuple(ds.raw[path].shape)
@@ -163,6 +172,8 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     device = next(step.netG.parameters()).device if hasattr(step, 'netG') else torch.device('cuda')
     src = open_volumes(source, [path])[path]
     volume = torch.from_numpy(np.ascontiguousarray(src)).to(device)                    # the loop's one upload of the subject
+    if rescale is not None:
+        volume = rescale_intensity(volume, rescale)[0]
     volume_shape = (int(volume.shape[0]),) + patch_shape[1:]
     plan = PatchPlan(volume_shape, patch_indices(volume_shape, patch_shape, stride_shape))
     predictors = {}
@@ -208,7 +219,8 @@ def evaluate_volume(step, source, target, *, from_network_range=True, with_3d=Fa
     network's range, normalised as the loader normalises its volumes; pass False when both already are in [0, 1].  The three statistics tables
     are gathered on the device and copied once: that copy is the only device -> host transfer and the only synchronise of the whole call.
     ``with_3d=True`` adds ``evaluate_3D`` (volume PSNR and the 7^3-window SSIM evaluate.py:81 reports first) as ``'3d'``: the layer sums of
-    ``afcm_volume_ssim`` travel in that same copy, behind the three tables.
+    ``afcm_volume_ssim`` travel in that same copy, behind the three tables.  ``rescale=(q_lo, q_hi)`` (a ``predict_volume`` keyword) takes a raw
+    scanner volume as the source and rescales it on the device after the upload, still without a host read.
     Returns {'slice': (psnr, ssim, mae), 'one': (psnr, ssim, mae), 'prediction': [C, D, H, W] device tensor} and, on request, '3d': (psnr, ssim, mae)."""
     if predict_kwargs.get('where', 'device') != 'device':
         raise ValueError("evaluate_volume runs on the device; for host arrays use predict_volume(where='host') and afcm_amd.evaluation")

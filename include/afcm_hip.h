@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AFCM_ABI_VERSION 13  /* 13: + afcm_volume_ssim, afcm_volume_ssim_workspace_bytes (the 7^3-window SSIM map's layer sums; additions only, so the number stays).  13: + afcm_slice_assemble, afcm_halo_accumulate (whole-volume inference; additions only, so the number stays).  13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
+#define AFCM_ABI_VERSION 13  /* 13: + afcm_rescale_intensity, afcm_rescale_workspace_bytes, afcm_rescale_plan (intensity rescaling; additions only, so the number stays).  13: + afcm_volume_ssim, afcm_volume_ssim_workspace_bytes (the 7^3-window SSIM map's layer sums; additions only, so the number stays).  13: + afcm_slice_assemble, afcm_halo_accumulate (whole-volume inference; additions only, so the number stays).  13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
 
 enum { AFCM_F32 = 0, AFCM_F16 = 1, AFCM_BF16 = 2 };
 enum { AFCM_OK = 0, AFCM_E_NOKERNEL = -1, AFCM_E_INVALID = -2 };
@@ -683,6 +683,39 @@ int afcm_schedule_advance(double* block, int64_t batch, double blur_init_sigma, 
 int32_t afcm_gauss_blur_rmax(void);
 int afcm_gauss_blur(float* y, const float* x, float* scratch, int64_t planes, int32_t h, int32_t w, double sigma, const double* block, void* stream);
 int afcm_ema_multi(const afcm_ema_entry* table, int32_t n, int64_t total_chunks, double beta, const double* block, void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Intensity rescaling: rescale_intensity of data/prepare_h5.py:9-26 with the around / clip / uint8 of its caller (:38-41; evaluate.py:23-40 repeats
+ * it) for one volume [depth][h][w] of src_dtype (AFCM_SRC_*) that lives on the device: element (z, y, x) at z * src_stride_z + y * w + x ELEMENTS
+ * (rows contiguous, any stride in z, any element offset in the pointer).  N = depth * h * w < 2^31.
+ *   foreground   v > 0, decided from the bit pattern: NaN, -inf, -0.0, 0 and negatives are background, +inf and positive denormals foreground,
+ *                whatever the denormal mode.  n = the foreground count.
+ *   percentiles  for q in (q_lo, q_hi), FRACTIONS in [0, 1] (the percentile / 100, formed by the caller): vi = q * (n - 1), i = floor(vi), g = vi - i,
+ *                a = s[i], b = s[min(i + 1, n - 1)] of the sorted foreground s widened exactly to double, d = b - a, p = g >= 0.5 ? b - d * (1 - g) :
+ *                a + d * g -- numpy's `linear` method with its _lerp; every operation double and rounded on its own.
+ *   map          foreground: clip(rint(((double)v - lo) / (hi - lo) * 255), 1, 255), rint to even, a NaN result (hi == lo at v == lo, inf / inf)
+ *                is 1; background: 0.
+ * Arithmetic is float64 for EVERY source type.  numpy computes a float32 volume in float32, so for float32 sources the reference's grey level can
+ * differ by one at a few voxels in 10^5; for uint8 / int16 / float64 sources the two agree bit for bit.
+ * out: uint8 [depth][h][w], contiguous.  stats: DEVICE double[3] = lo, hi, (double)n; n == 0: out is all zeros, lo = hi = NaN.
+ * The four order statistics (i and i + 1 of both percentiles) come from ONE most-significant-digit-first radix select over the raw bit patterns
+ * (positive values order as their bits do): afcm_rescale_plan's `passes` digits, each pass a histogram launch -- every workgroup counts its share in
+ * LDS (integer adds; in the first pass of 8-bit digits each wave has a histogram of its own, since a float's top digit is its exponent) and stores
+ * the counts into its own slot of `workspace` -- and a one-workgroup launch that adds the slots, scans, picks each rank's bin and carries prefix and
+ * residual rank forward.  n is the first pass's total and the ranks are formed from it on the device.  Then the map: 16 voxels per thread, 16-byte
+ * loads where the run lies inside one slice on a 16-byte boundary and a 16-byte store where the output run does, element by element otherwise.
+ * No global atomic, no host read, no allocation, no synchronise; `workspace` needs afcm_rescale_workspace_bytes() bytes, 8-byte aligned, and no
+ * initialisation.  Bit-identical from call to call.
+ * afcm_rescale_plan (pure host): plan[0] = histogram workgroups, plan[1] = voxels of one workgroup per round of the grid (workgroup g counts voxels
+ * [(r * plan[0] + g) * plan[1], + plan[1]) in round r), plan[2] = passes, plan[3 + p] = bits of digit p for p < passes (most significant first; the
+ * rest 0): 11 values.  afcm_rescale_workspace_bytes (pure host): 0 for arguments afcm_rescale_plan refuses.
+ * AFCM_E_INVALID: null pointers, an unknown dtype, extents < 1, N >= 2^31, a negative z stride, fractions outside 0 <= q_lo <= q_hi <= 1 (NaN
+ * included), a workspace or stats pointer that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int afcm_rescale_plan(int64_t n, int32_t src_dtype, int32_t* plan);
+int64_t afcm_rescale_workspace_bytes(int64_t n, int32_t src_dtype);
+int afcm_rescale_intensity(uint8_t* out, double* stats, void* workspace, const void* volume, int32_t src_dtype, int32_t depth, int32_t h, int32_t w,
+                           int64_t src_stride_z, double q_lo, double q_hi, void* stream);
 
 #ifdef __cplusplus
 }
