@@ -180,6 +180,9 @@ __global__ __launch_bounds__(256) void upfirdn2d_tile_kernel(UpfirdnParams p, co
 // per lane and instruction through LDS: 1.3 TB/s on the discriminator's 256^2 blur); the rows above / below are the neighbouring thread's
 // in L1 / L2.  Outputs leave as one 16-byte store per row.  The taps meet every output in the tile kernel's order (ky, then kx), so both
 // kernels produce the same bits.
+// Preconditions (launch_rows checks them; the tile kernel takes what it refuses): x and y on 4-byte boundaries, xw and yw even, fewer than
+// 2^31 input bytes and output elements, padx0 <= 3 (UP 1) / 6 (UP 2), and xw + a0 >= 0 for the first group's a0 (below; -2 or -4 with left
+// padding) -- i.e. xw >= 4 where padx0 is 3 (UP 1) / 6 (UP 2).
 //   XODD: the first input column of a group is odd (UP 1: padx0 odd; UP 2: the zero-inserted origin x0 - padx0 is odd);  YODD (UP 2): the
 //   zero-inserted origin row is odd.  Both are uniform over the launch (x0 is a multiple of 8, the first row of a strip a multiple of RPT).
 template <int UP, int DOWN> struct UpfRows {
@@ -243,7 +246,9 @@ __global__ __launch_bounds__(256) void upfirdn2d_rows_kernel(UpfirdnParams p, co
     }
     if (plane_el + a0 < 0) {
         // the tensor's very first group: row 0 would start at a negative offset, which the range check answers with zeros for the whole
-        // vector, not only for the dwords before the buffer -- read it from offset 0 and move the dwords up (a0 = -2 or -4: 1 or 2 dwords)
+        // vector, not only for the dwords before the buffer -- read it from offset 0 and move the dwords up (a0 = -2 or -4: 1 or 2 dwords).
+        // Every other row of the tensor starts at xw + a0 >= 0 or later (launch_rows refuses a plane 2 columns wide with a0 = -4: row 1 of
+        // plane 0 would start at -2 and read as zeros too, and plane 1 of one-row planes would come here and be given plane 0's row)
         const int sh = (-a0) >> 1;
 #pragma unroll
         for (int r = 0; r < NIN; r++) {
@@ -350,6 +355,13 @@ static bool launch_rows(const UpfirdnParams& p, const float* f, hipStream_t st) 
         const int up = p.upx, down = p.downx;
         if (!((up == 1 && (down == 1 || down == 2)) || (up == 2 && down == 1))) return false;
         if (p.padx0 > (up == 1 ? 3 : 6)) return false;                      // the first group starts at most 4 columns left of the plane (kernel: sh <= 2)
+        // ... and no further left than one row is wide: the kernel repairs only row 0 of the tensor's very first group, so the tensor's
+        // second row (row 1 of plane 0, or plane 1 of one-row planes) must start at a non-negative offset, xw + a0 >= 0 (a0 as in the
+        // kernel).  Refused: xw == 2 with a0 == -4 (padx0 3 at up 1, 6 at up 2); the tile kernel takes those.
+        if (p.padx0 > 0) {
+            const int c0 = up == 1 ? -p.padx0 : (-p.padx0 + (p.padx0 & 1)) / 2;
+            if (p.xw + c0 - (c0 & 1) < 0) return false;
+        }
         const int rpt = up == 2 ? UpfRows<2, 1>::RPT : down == 2 ? UpfRows<1, 2>::RPT : UpfRows<1, 1>::RPT;
         const int ncg = (p.yw + 7) / 8, nstrips = (p.yh + rpt - 1) / rpt;
         const long long total = (long long)ncg * nstrips * p.planes;
