@@ -281,29 +281,52 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
     constexpr int ABYTES = 2 * G::IWSTEP;                                  // bytes the window advances per group (32 / 16)
     constexpr int PGRP = 64 / ABYTES;                                      // groups per piece
     static_assert(64 % ABYTES == 0 && PGRP >= 2, "pieces of 64 bytes, at least two groups each");
-    auto load_piece = [&](int k, u32x4 (&raw)[G::NMB]) __attribute__((always_inline)) {
+    // A piece that crosses the plane's left or right edge is requested by the SAME 16-byte loads, and put right when it is parked:
+    // (r02-r06 fetched it dword by dword, 4 NMB loads in a branch of their own.  A wait names the number of younger operations
+    // on the path that has the fewest, and the compiler's count across that branch came out as if the piece had not been requested
+    // at all: the wait for codes at the top of the next group drained the piece with them -- ISA: vmcnt(6) / (4) instead of (9) / (7).)
+    //   * a lane whose 8 columns lie wholly outside the row, or in a row above the plane, asks beyond the descriptor (zeros);
+    //   * a lane whose 8 columns straddle column 0 asks for the row's first 16 bytes instead and shifts them into place later;
+    //   * a lane whose 8 columns straddle the row's end asks for them as they are: what follows is the next row's head or its padding,
+    //     or lies behind the plane (16-byte buffer loads are range-checked dword by dword: tools/ubench/oob_probe.hip);
+    //   * fix_piece(), called with the data in hand, zeroes every dword outside [0, xw) (even widths: a dword is in or out whole).
+    auto piece_edge = [&](int k) __attribute__((always_inline)) -> bool {
         const int c0 = S0x + 32 * k;                                      // wave-uniform
-        if (__builtin_expect(c0 >= 0 && c0 + 32 <= p.xw, 1)) {
+        return !(c0 >= 0 && c0 + 32 <= p.xw);
+    };
+    auto load_piece = [&](int k, u32x4 (&raw)[G::NMB]) __attribute__((always_inline)) {
+        unsigned off[G::NMB];
+        if (__builtin_expect(!piece_edge(k), 1)) {
+#pragma unroll
+            for (int mb = 0; mb < G::NMB; mb++) off[mb] = (unsigned)(xoff0 + 64 * k + mb * xrow16);
+        } else {
+            const int col = S0x + 32 * k + 8 * lchk;                      // this lane's first column
+            const bool gone = col + 8 <= 0 || col >= p.xw;
+            const int back = (col < 0 && !gone) ? -2 * col : 0;           // bytes from the lane's first column to column 0
 #pragma unroll
             for (int mb = 0; mb < G::NMB; mb++)
-                raw[mb] = __builtin_amdgcn_raw_buffer_load_b128(rsx, (unsigned)(xoff0 + 64 * k + mb * xrow16), 0, kLoadAux);
-        } else {
-            // the piece crosses the left or right edge of the plane: dword by dword, columns outside it read as zero
-            // (even plane widths: the two elements of a dword are in or out together; rows outside: as above, except that a
-            // negative row offset plus the marker must not wrap back into range)
-            const int col = c0 + 8 * lchk;
-            unsigned cofs[4];
+                off[mb] = (gone || I0y + 16 * mb + lrow < 0) ? kOut : (unsigned)(xoff0 + 64 * k + mb * xrow16 + back);
+        }
 #pragma unroll
-            for (int w = 0; w < 4; w++) cofs[w] = (unsigned)(col + 2 * w) < (unsigned)p.xw ? (unsigned)(64 * k + 4 * w) : kOut;
+        for (int mb = 0; mb < G::NMB; mb++) raw[mb] = __builtin_amdgcn_raw_buffer_load_b128(rsx, off[mb], 0, kLoadAux);
+    };
+    auto fix_piece = [&](int k, u32x4 (&raw)[G::NMB]) __attribute__((always_inline)) {
+        const int col = S0x + 32 * k + 8 * lchk;
+        const int sh = (col < 0 && col + 8 > 0) ? (-col) >> 1 : 0;         // dwords the loaded 16 bytes lie left of their place (0 .. 3)
 #pragma unroll
-            for (int mb = 0; mb < G::NMB; mb++) {
-                const unsigned ro = (I0y + 16 * mb + lrow < 0) ? kOut : (unsigned)(xoff0 + mb * xrow16);
+        for (int mb = 0; mb < G::NMB; mb++) {
+            const u32x4 v = raw[mb];
+            u32x4 r;
+            r[0] = sh == 0 ? v[0] : 0u;
+            r[1] = sh == 0 ? v[1] : (sh == 1 ? v[0] : 0u);
+            r[2] = sh == 0 ? v[2] : (sh == 1 ? v[1] : (sh == 2 ? v[0] : 0u));
+            r[3] = sh == 0 ? v[3] : (sh == 1 ? v[2] : (sh == 2 ? v[1] : v[0]));
 #pragma unroll
-                for (int w = 0; w < 4; w++) raw[mb][w] = __builtin_amdgcn_raw_buffer_load_b32(rsx, ro + cofs[w], 0, 0);
-            }
+            for (int w = 0; w < 4; w++) raw[mb][w] = (unsigned)(col + 2 * w) < (unsigned)p.xw ? r[w] : 0u;
         }
     };
-    auto park_piece = [&](int k, const u32x4 (&raw)[G::NMB]) __attribute__((always_inline)) {
+    auto park_piece = [&](int k, u32x4 (&raw)[G::NMB]) __attribute__((always_inline)) {
+        if (__builtin_expect(piece_edge(k), 0)) fix_piece(k, raw);
 #pragma unroll
         for (int mb = 0; mb < G::NMB; mb++) *(u32x4*)(ring + (unsigned)((16 * mb + lrow) * IPITCH + (k & 1) * 64 + 16 * lchk)) = raw[mb];
     };
@@ -345,6 +368,15 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
     const bool rows_inside = Q0 >= 0 && (((Q0 + 4) >> 2) >> 2) + NA + 1 <= nV4;
     // RA: dwords per column block -- code bytes sl .. sl + NVB - 1 of the lane's dword run (sl = (first row block) & 3, wave-uniform)
     constexpr int NL = RA ? cdiv(3 + G::NVB, 4) : NA + 1;
+    // Groups between the request for a group's codes and their use.  vmcnt is ONE in-order counter: the wait for codes requested a
+    // group ago also drains everything older -- the input piece requested in that same group, whose own park is a further group
+    // away (ISA of the one-set build: s_waitcnt vmcnt(0) at the top of every group, the piece's two-group lead cut to one).  The
+    // aligned up-2 / down-2 kernels (two groups per loop iteration, a piece every other group: which groups request one is static)
+    // keep TWO register sets of codes, one per group parity, each refilled for group gi + 2 right after group gi took its bytes
+    // out: the wait at the top of a group then leaves the younger piece and the other set in flight (vmcnt(NMB + 2 NL)) and every
+    // stream has its two groups.  (2 NL = 4 registers more.)  Where a group requests a piece by a run-time condition (up 4, the
+    // rolled down-4 loop) the count of a wait is that of the path without it and a second set would not keep the piece in flight.
+    constexpr int SLEAD = (RA && G::NHIST == 1 && PGRP == 2) ? 2 : 1;
     // READ: the sign dwords of a group's two column blocks, fetched one group ahead like the input window (consumed right after
     // the up-y products: fetched in place, every column block exposed a full memory round trip)
     auto load_signs = [&](int nb, unsigned (&sg)[RA ? 1 : 2][NL]) __attribute__((always_inline)) {
@@ -505,10 +537,14 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
         // first, so that the registers can take the next group's request below and nothing younger than the codes is waited for
         unsigned four[G::NBG][NA] = {};
         if (RA) {
+            // (the "any clamp code" bits of this group's dwords in a register of their own, pinned with the shifts: folded into anyc
+            // one by one the compiler was free to sink the ORs, the dwords stayed live past the request that refills their registers,
+            // and the refill went to other registers and back by copies at the loop's end -- behind a vmcnt(0))
+            unsigned anyg = 0;
 #pragma unroll
             for (int nbl = 0; nbl < G::NBG; nbl++) {
 #pragma unroll
-                for (int i = 0; i < NL; i++) anyc |= sg[nbl][0][i];
+                for (int i = 0; i < NL; i++) anyg |= sg[nbl][0][i];
 #pragma unroll
                 for (int k = 0; k < NA; k++)
                     four[nbl][k] = __builtin_amdgcn_alignbyte(k + 1 < NL ? sg[nbl][0][k + 1] : 0u, sg[nbl][0][k], sgr_sl);
@@ -521,11 +557,34 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
             for (int nbl = 0; nbl < G::NBG; nbl++)
 #pragma unroll
                 for (int k = 0; k < NA; k++) asm volatile("" : "+v"(four[nbl][k]) : : "memory");
+            asm volatile("" : "+v"(anyg) : : "memory");
+            anyc |= anyg;
             __builtin_amdgcn_sched_barrier(0);
         }
         // the window of group PGRP (k - 1) + 1 is the first to reach into piece k: park it (requested PGRP groups ago, or before
         // the loop) and request piece k + 1 into the same registers; then this group's fragments; then the stores of the 64-column
         // output group the previous down-x pass may have completed
+        auto flush_prev = [&]() __attribute__((always_inline)) {
+            const int gp = gi - 1;
+            const bool prv_b = gp >= G::NDVK - 1 && (gp - (G::NDVK - 1)) % (DOWN / 2) == 0;
+            const int cb_p = (gp - (G::NDVK - 1)) / (DOWN / 2);
+            if (prv_b && ((cb_p & 3) == 3 || cb_p == ncb - 1)) flush(cb_p);
+        };
+        // Two sets of codes: the flush goes AHEAD of the piece request.  The wait for codes at the top of the next group may leave the piece and the
+        // other set of codes in flight; stores between those two would, on the groups that have them, take four of those places and
+        // the piece would be drained after all.  Ahead of the piece they are the oldest of the group and a group old when waited for.
+        if (SLEAD == 2) flush_prev();
+        if (EPI & 2) {
+            // this group's down-x pass opens a column-block pair: its skip rows were requested at the top of the group before -- park
+            // them; the NEXT group opens one: request its rows.  Both AHEAD of the piece: parked behind the piece request (r03-r06) the
+            // wait for the rows named the piece's loads as the only younger operations, and on a group with a flush (4 stores behind
+            // the piece) drained the piece as well; requested behind it they had 0.7 of a group.
+            if (has_b && (cb_b & 1) == 0) park_skip(skw);
+            const int gn = gi + 1;
+            const bool nxt_b = gn >= G::NDVK - 1 && (gn - (G::NDVK - 1)) % (DOWN / 2) == 0;
+            const int cb_n = (gn - (G::NDVK - 1)) / (DOWN / 2);
+            if (nxt_b && (cb_n & 1) == 0 && cb_n < ncb) load_skip(cb_n, skw);
+        }
         if (gi % PGRP == 1) {
             const int k = (gi - 1) / PGRP + 1;
             park_piece(k, raw);
@@ -533,26 +592,12 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
         }
         frag a_in[G::NMB];
         frags(gi, a_in);
-        {
-            const int gp = gi - 1;
-            const bool prv_b = gp >= G::NDVK - 1 && (gp - (G::NDVK - 1)) % (DOWN / 2) == 0;
-            const int cb_p = (gp - (G::NDVK - 1)) / (DOWN / 2);
-            if (prv_b && ((cb_p & 3) == 3 || cb_p == ncb - 1)) flush(cb_p);
-        }
-        if (EPI & 2) {
-            // this group's down-x pass opens a column-block pair: its skip rows were requested a group ago (older than the window
-            // that the group waited for) -- park them; the NEXT group opens one: request its rows, ahead of the next window
-            if (has_b && (cb_b & 1) == 0) park_skip(skw);
-            const int gn = gi + 1;
-            const bool nxt_b = gn >= G::NDVK - 1 && (gn - (G::NDVK - 1)) % (DOWN / 2) == 0;
-            const int cb_n = (gn - (G::NDVK - 1)) / (DOWN / 2);
-            if (nxt_b && (cb_n & 1) == 0 && cb_n < ncb) load_skip(cb_n, skw);
-        }
+        if (SLEAD != 2) flush_prev();
         if (RA) {
             // (unconditional: past the last group the blocks lie outside the tensor and read as zero; a condition here costs
             // register copies that wait for the window just requested)
-            load_signs((gi + 1) * G::NBG, sg[0]);
-            load_signs((gi + 1) * G::NBG + 1, sg[1]);
+            load_signs((gi + SLEAD) * G::NBG, sg[0]);
+            load_signs((gi + SLEAD) * G::NBG + 1, sg[1]);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -782,9 +827,18 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
         unsigned anyc = 0;
         if (decltype(exact_c)::value) psum = 0.f;
         u32x4 raw[G::NMB];
-        unsigned sg[G::NBG][RA ? 1 : 2][NL];
+        unsigned sg[SLEAD][G::NBG][RA ? 1 : 2][NL];
+        u32x4 hist[G::NOB][G::NHIST], cur[G::NOB], skw[G::NOB];
+#pragma unroll
+        for (int ob = 0; ob < G::NOB; ob++) skw[ob] = (u32x4){0u, 0u, 0u, 0u};
         load_piece(0, raw);
         park_piece(0, raw);                          // (the one exposed round trip of the strip)
+        // The requests ahead of the loop stand in the order and number the loop keeps them in, oldest first: the loop head is reached
+        // from here and from its own end, and the compiler's count for a wait is the smaller of the two paths'.
+        if (RD && SLEAD == 2) {
+            load_signs(0, sg[0][0]);
+            load_signs(1, sg[0][1]);
+        }
         load_piece(1, raw);
         if (SIGN == AFCM_SIGNS_WRITE) {
             // The wait for a piece (park_piece) names the number of YOUNGER memory operations it may leave in flight (vmcnt is one
@@ -798,18 +852,15 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
             for (int i = 0; i < G::NBG * cdiv(NVW, 4); i++) __builtin_amdgcn_raw_buffer_store_b32(0u, rsx, kOut + 256u * i, 0, kStoreAux);   // (distinct, non-adjacent offsets: identical or adjacent stores are merged)
         }
         if (RD) {
-            load_signs(0, sg[0]);
-            load_signs(1, sg[1]);
+            load_signs((SLEAD - 1) * G::NBG, sg[SLEAD - 1][0]);
+            load_signs((SLEAD - 1) * G::NBG + 1, sg[SLEAD - 1][1]);
         }
-        u32x4 hist[G::NOB][G::NHIST], cur[G::NOB], skw[G::NOB];
 #pragma unroll
         for (int ob = 0; ob < G::NOB; ob++) {
-            skw[ob] = (u32x4){0u, 0u, 0u, 0u};
 #pragma unroll
             for (int h = 0; h < G::NHIST; h++) hist[ob][h] = (u32x4){0u, 0u, 0u, 0u};
         }
-        // the first down-x pass runs in group NDVK - 1 >= 1: when that is group 1 its skip rows are requested here (group 0 does
-        // it itself for later ones)
+        // the first down-x pass runs in group NDVK - 1 >= 1: group NDVK - 2 requests its skip rows
         static_assert(G::NDVK - 1 >= 1, "the first down-x pass must not be in group 0");
         if constexpr (G::NHIST == 1) {
             // down 2: the pair a group produces is the next group's history -- two groups per iteration with the two register sets
@@ -818,11 +869,24 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
             u32x4 alt[G::NOB];
 #pragma unroll
             for (int ob = 0; ob < G::NOB; ob++) alt[ob] = hist[ob][0];
+            if constexpr (SLEAD == 2) {
+                // whole pairs of groups, then the odd one out: with a way out of the loop between the two groups, the path that
+                // takes it still reaches the loop head in the compiler's graph -- with the first set's refill the youngest request
+                // -- and the wait at the head is counted for that path: vmcnt(0)
+                int gi = 0;
 #pragma unroll 1
-            for (int gi = 0; gi < ngc; gi += 2) {
-                group(gi, exact_c, lasty_c, raw, sg, reinterpret_cast<as_hist>(alt), cur, skw, amax, anyc);
-                if (gi + 1 >= ngc) break;
-                group(gi + 1, exact_c, lasty_c, raw, sg, reinterpret_cast<as_hist>(cur), alt, skw, amax, anyc);
+                for (; gi + 1 < ngc; gi += 2) {
+                    group(gi, exact_c, lasty_c, raw, sg[0], reinterpret_cast<as_hist>(alt), cur, skw, amax, anyc);
+                    group(gi + 1, exact_c, lasty_c, raw, sg[SLEAD - 1], reinterpret_cast<as_hist>(cur), alt, skw, amax, anyc);
+                }
+                if (gi < ngc) group(gi, exact_c, lasty_c, raw, sg[0], reinterpret_cast<as_hist>(alt), cur, skw, amax, anyc);
+            } else {
+#pragma unroll 1
+                for (int gi = 0; gi < ngc; gi += 2) {
+                    group(gi, exact_c, lasty_c, raw, sg[0], reinterpret_cast<as_hist>(alt), cur, skw, amax, anyc);
+                    if (gi + 1 >= ngc) break;
+                    group(gi + 1, exact_c, lasty_c, raw, sg[0], reinterpret_cast<as_hist>(cur), alt, skw, amax, anyc);
+                }
             }
             // (the register sets keep trading places by the parity of the group)
 #pragma unroll 1
@@ -833,7 +897,7 @@ __global__ __launch_bounds__(256, (wave_occupancy<UP, DOWN, TOW, TOH, SIGN, EPI>
         } else {
 #pragma unroll 1
             for (int gi = 0; gi < ng; gi++) {
-                if (gi < ngc) group(gi, exact_c, lasty_c, raw, sg, hist, cur, skw, amax, anyc);
+                if (gi < ngc) group(gi, exact_c, lasty_c, raw, sg[0], hist, cur, skw, amax, anyc);
                 else tail_group(gi, hist, cur, skw);
 #pragma unroll
                 for (int ob = 0; ob < G::NOB; ob++) {
