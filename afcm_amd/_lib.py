@@ -2,6 +2,7 @@
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -15,6 +16,10 @@ SCHEDULE_SLOTS = 8
 EMA_LERP, EMA_COPY = 0, 1
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+OUT_DTYPES = tuple(_DTYPES)
+# what a source volume may hold (the loader kernels and rescale_intensity), by torch and by numpy dtype
+SOURCE_DTYPES = {torch.uint8: SRC_U8, torch.int16: SRC_I16, torch.float32: SRC_F32, torch.float64: SRC_F64}
+NUMPY_SOURCE_DTYPES = {np.dtype(np.uint8): SRC_U8, np.dtype(np.int16): SRC_I16, np.dtype(np.float32): SRC_F32, np.dtype(np.float64): SRC_F64}
 
 
 class FilteredLReluArgs(C.Structure):
@@ -181,6 +186,25 @@ def dtype_code(t):
         return _DTYPES[t.dtype]
     except KeyError:
         raise RuntimeError(f'afcm_amd kernels support float32/float16/bfloat16, got {t.dtype}') from None
+
+
+def source_code(dtype, what):
+    """SRC_* of a source volume's torch or numpy dtype; ``what`` names the caller in the refusal."""
+    code = (SOURCE_DTYPES if isinstance(dtype, torch.dtype) else NUMPY_SOURCE_DTYPES).get(dtype)
+    if code is None:
+        raise RuntimeError(f'{what}: source volumes are uint8 / int16 / float32 / float64, got {dtype}')
+    return code
+
+
+def require_out_dtype(dtype, what):
+    if dtype not in OUT_DTYPES:
+        raise RuntimeError(f'{what}: output dtype float32 / float16 / bfloat16, got {dtype}')
+
+
+def require_slice_num(slice_num, what):
+    """The loader geometries that exist: the slice itself (1) or four thick slices around it (4)."""
+    if slice_num not in (1, 4):
+        raise RuntimeError(f'{what}: slice number {slice_num} not supported (1 or 4)')
 
 
 def require_gpu(*tensors):

@@ -8,20 +8,7 @@
 #include "common.h"
 #include "volume_common.h"
 
-// bytes of one thread's run along x (one store); 0: one element per thread, the form of slice_assemble_kernel (tools/bench_train_feed.py builds both)
-#ifndef AFCM_BATCH_RUN_BYTES
-#define AFCM_BATCH_RUN_BYTES 16
-#endif
-
 namespace afcm {
-
-template <typename T>
-constexpr int batch_run() { return AFCM_BATCH_RUN_BYTES > 0 ? AFCM_BATCH_RUN_BYTES / (int)sizeof(T) : 1; }
-
-template <typename T, int RUN>
-struct alignas(sizeof(T) * RUN) run_of {
-    T v[RUN];
-};
 
 // [offset, offset + depth hs ws) inside [0, pool_elems) with positive extents, without forming a product that could overflow
 __device__ __forceinline__ bool descriptor_ok(long long off, long long depth, long long hs, long long ws, long long pool_elems) {
@@ -64,72 +51,21 @@ __global__ __launch_bounds__(VOL_THREADS) void batch_assemble_kernel(T* __restri
         valid = descriptor_ok(off_a, depth, hs, ws, pool_elems) && descriptor_ok(off_b, db[1], db[2], db[3], pool_elems) && db[1] == depth &&
                 db[2] == hs && db[3] == ws && idx >= 0 && idx < depth;
     }
-    const int idx_a = valid && k == 4 ? (idx / t) * t : idx;
-    if (plane == 0 && y == 0 && x0 == 0) slice_idx[i] = valid ? (float)(idx - idx_a) / (float)t : __builtin_nanf("");
+    const thick_slice at = thick_slice_of(idx, valid ? t : 1, plane < k ? k : 1, plane);      // B: the k = 1 item of volume vb
+    if (plane == 0 && y == 0 && x0 == 0) slice_idx[i] = valid ? at.label() : __builtin_nanf("");
 
     float v[RUN];
     if (!valid) {
 #pragma unroll
         for (int j = 0; j < RUN; ++j) v[j] = __builtin_nanf("");
     } else {
-        const long long pos = plane < k && k == 4 ? (long long)idx_a + (long long)(plane - 1) * t : idx;
-        if (pos < 0 || pos > depth - 1) {
-            const float z = normalised<double>(nullptr, 0, false, lo, range);  // a plane of float64 zeros before normalisation
-#pragma unroll
-            for (int j = 0; j < RUN; ++j) v[j] = z;
-        } else {
-            const long long ys = y + crop_offset(hs, h), xs0 = x0 + crop_offset(ws, w);   // crop offset (> 0) or minus the leading pad
-            const bool row_inside = ys >= 0 && ys < hs;
-            const long long at = (plane < k ? off_a : off_b) + (pos * hs + ys) * ws + xs0;
-#pragma unroll
-            for (int j = 0; j < RUN; ++j) {
-                const bool inside = row_inside && xs0 + j >= 0 && xs0 + j < ws && x0 + j < w;
-                v[j] = normalised<S>(pool, at + j, inside, lo, range);
-            }
-        }
+        assembled_run<S, RUN>(v, pool + (plane < k ? off_a : off_b), depth, hs, ws, hs * ws, at.pos, y, x0, h, w, lo, range);
     }
-
-    T* out = (plane < k ? a + (((long long)i * k + plane) * h + y) * w : b + ((long long)i * h + y) * w) + x0;
-    if (RUN > 1 && x0 + RUN <= w && (uintptr_t)out % (sizeof(T) * RUN) == 0) {
-        run_of<T, RUN> pack;
-#pragma unroll
-        for (int j = 0; j < RUN; ++j) pack.v[j] = (T)v[j];
-        *reinterpret_cast<run_of<T, RUN>*>(out) = pack;
-    } else {                                                                   // the tail of a row, or a row that does not start on a run boundary
-#pragma unroll
-        for (int j = 0; j < RUN; ++j)
-            if (x0 + j < w) out[j] = (T)v[j];
-    }
+    store_run<T, RUN>((plane < k ? a + (((long long)i * k + plane) * h + y) * w : b + ((long long)i * h + y) * w) + x0, v, x0, w);
 }
 
 __global__ void cursor_advance_kernel(long long* __restrict__ cursor, long long by) {
     if (blockIdx.x == 0 && threadIdx.x == 0) cursor[0] += by;
-}
-
-template <typename S, typename T>
-static int launch_batch(void* a, void* b, float* slice_idx, const void* pool, long long pool_elems, const int64_t* vols, int n_vols, const int32_t* items,
-                        int n_items, const int64_t* cursor, int first, int count, int k, int h, int w, double lo, double range, hipStream_t stream) {
-    constexpr int RUN = batch_run<T>();
-    const int runs = cdiv(w, RUN);
-    const double threads = (double)count * (k + 1) * h * runs;                 // checked before the product is formed in 64 bits
-    AFCM_REQUIRE(threads / VOL_THREADS < 2147483647.0, "batch_assemble: %.0f workgroups exceed the grid", threads / VOL_THREADS);
-    const long long total = (long long)count * (k + 1) * h * runs;
-    const long long groups = (total + VOL_THREADS - 1) / VOL_THREADS;
-    hipLaunchKernelGGL((batch_assemble_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, stream, (T*)a, (T*)b, slice_idx, (const S*)pool,
-                       pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items, (const long long*)cursor, first, k, h, w, runs, total, lo,
-                       range);
-    return hip_status(hipGetLastError());
-}
-
-template <typename S>
-static int launch_batch_out(int out_dtype, void* a, void* b, float* slice_idx, const void* pool, long long pool_elems, const int64_t* vols, int n_vols,
-                            const int32_t* items, int n_items, const int64_t* cursor, int first, int count, int k, int h, int w, double lo, double range,
-                            hipStream_t stream) {
-    if (out_dtype == AFCM_F32)
-        return launch_batch<S, float>(a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w, lo, range, stream);
-    if (out_dtype == AFCM_F16)
-        return launch_batch<S, f16_t>(a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w, lo, range, stream);
-    return launch_batch<S, bf16_t>(a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w, lo, range, stream);
 }
 
 }  // namespace afcm
@@ -149,21 +85,20 @@ extern "C" int afcm_batch_assemble(void* a, void* b, float* slice_idx, const voi
     AFCM_REQUIRE(k == 1 || k == 4, "batch_assemble: slice number %d is not 1 or 4", k);
     AFCM_REQUIRE(max_value > min_value, "batch_assemble: max_value %g is not above min_value %g", max_value, min_value);
     const double range = max_value - min_value;
-    hipStream_t s = (hipStream_t)stream;
-    switch (src_dtype) {
-        case AFCM_SRC_U8:
-            return launch_batch_out<uint8_t>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
-                                             min_value, range, s);
-        case AFCM_SRC_I16:
-            return launch_batch_out<int16_t>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
-                                             min_value, range, s);
-        case AFCM_SRC_F32:
-            return launch_batch_out<float>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
-                                           min_value, range, s);
-        default:
-            return launch_batch_out<double>(out_dtype, a, b, slice_idx, pool, pool_elems, vols, n_vols, items, n_items, cursor, first, count, k, h, w,
-                                            min_value, range, s);
-    }
+    return dispatch_src_out(src_dtype, out_dtype, [&](auto s_tag, auto t_tag) -> int {
+        using S = typename decltype(s_tag)::type;
+        using T = typename decltype(t_tag)::type;
+        constexpr int RUN = run_length<T>;
+        const int runs = cdiv(w, RUN);
+        const double threads = (double)count * (k + 1) * h * runs;             // checked before the product is formed in 64 bits
+        AFCM_REQUIRE(threads / VOL_THREADS < 2147483647.0, "batch_assemble: %.0f workgroups exceed the grid", threads / VOL_THREADS);
+        const long long total = (long long)count * (k + 1) * h * runs;
+        const long long groups = (total + VOL_THREADS - 1) / VOL_THREADS;
+        hipLaunchKernelGGL((batch_assemble_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, (hipStream_t)stream, (T*)a, (T*)b, slice_idx,
+                           (const S*)pool, (long long)pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items, (const long long*)cursor,
+                           first, k, h, w, runs, total, min_value, range);
+        return hip_status(hipGetLastError());
+    });
 }
 
 extern "C" int afcm_cursor_advance(int64_t* cursor, int64_t by, void* stream) {

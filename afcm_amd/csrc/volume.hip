@@ -1,6 +1,7 @@
 // Whole-volume inference: the two ends of the reference's volume loop (evaluate.py -> StandardPredictor.__call__) on the device.
 //   slice_assemble_kernel   the test-phase loader item (data/cmsr_dataset.py:98-155: centre crop / constant pad, the four thick slices around the
-//                           target, Normalize to [-1, 1]) for a run of target slices of one source volume: one thread per output element
+//                           target, Normalize to [-1, 1]) for a run of target slices of one source volume: the shared body of volume_common.h,
+//                           one thread per run of consecutive x of one output row
 //   halo_accumulate_kernel  remove_halo + "map[index] += patch; mask[index] += 1" (models/predictor.py:17-51,173-200) for one batch, in gather
 //                           form: one thread per voxel of the batch's bounding box walks the batch's patches in ascending order
 // Neither kernel stages anything in LDS or uses an atomic; every volume offset is 64-bit.  See include/afcm_hip.h for the semantics kept.
@@ -9,31 +10,25 @@
 
 namespace afcm {
 
-template <typename S, typename T>
+// Arguments checked on the host.  A thread owns the run of RUN consecutive x at x0 of row y of input plane `plane` of target slice idx.
+template <typename S, typename T, int RUN>
 __global__ __launch_bounds__(VOL_THREADS) void slice_assemble_kernel(T* __restrict__ a, float* __restrict__ slice_idx, const S* __restrict__ src,
                                                                      int depth, int hs, int ws, long long stride_z, int first, int k,
-                                                                     int thickness, int h, int w, int oy, int ox, long long total, double lo,
+                                                                     int thickness, int h, int w, int runs, long long total, double lo,
                                                                      double range) {
     const long long e = (long long)blockIdx.x * VOL_THREADS + threadIdx.x;
     if (e >= total) return;
-    const int x = (int)(e % w);
-    long long r = e / w;
+    const int x0 = (int)(e % runs) * RUN;
+    long long r = e / runs;
     const int y = (int)(r % h);
     r /= h;
     const int plane = (int)(r % k);
-    const int idx = first + (int)(r / k);
-    const int idx_a = k == 4 ? (idx / thickness) * thickness : idx;
-    const long long pos = k == 4 ? (long long)idx_a + (long long)(plane - 1) * thickness : idx;
-    float v;
-    if (pos < 0 || pos > depth - 1) {
-        v = normalised<double>(nullptr, 0, false, lo, range);                  // a plane of float64 zeros before normalisation
-    } else {
-        const int ys = y + oy, xs = x + ox;                                    // oy / ox: crop offset (> 0) or minus the leading pad
-        const bool inside = ys >= 0 && ys < hs && xs >= 0 && xs < ws;
-        v = normalised<S>(src, pos * stride_z + (long long)ys * ws + xs, inside, lo, range);
-    }
-    a[e] = (T)v;
-    if (plane == 0 && y == 0 && x == 0) slice_idx[idx - first] = (float)(idx - idx_a) / (float)thickness;
+    const int i = (int)(r / k);
+    const thick_slice at = thick_slice_of(first + i, thickness, k, plane);
+    if (plane == 0 && y == 0 && x0 == 0) slice_idx[i] = at.label();
+    float v[RUN];
+    assembled_run<S, RUN>(v, src, depth, hs, ws, stride_z, at.pos, y, x0, h, w, lo, range);
+    store_run<T, RUN>(a + (r * h + y) * w + x0, v, x0, w);
 }
 
 struct halo_axis {
@@ -80,22 +75,6 @@ __global__ __launch_bounds__(VOL_THREADS) void halo_accumulate_kernel(float* __r
     if (touched) { map[at] = acc; mask[at] = (uint8_t)visits; }
 }
 
-template <typename S>
-static int launch_assemble(void* a, int out_dtype, float* slice_idx, const void* src, int depth, int hs, int ws, long long stride_z, int first, int k,
-                           int thickness, int h, int w, int oy, int ox, long long total, double lo, double range, hipStream_t stream) {
-    const dim3 grid((unsigned)((total + VOL_THREADS - 1) / VOL_THREADS)), block(VOL_THREADS);
-    if (out_dtype == AFCM_F32)
-        hipLaunchKernelGGL((slice_assemble_kernel<S, float>), grid, block, 0, stream, (float*)a, slice_idx, (const S*)src, depth, hs, ws, stride_z, first,
-                           k, thickness, h, w, oy, ox, total, lo, range);
-    else if (out_dtype == AFCM_F16)
-        hipLaunchKernelGGL((slice_assemble_kernel<S, f16_t>), grid, block, 0, stream, (f16_t*)a, slice_idx, (const S*)src, depth, hs, ws, stride_z, first,
-                           k, thickness, h, w, oy, ox, total, lo, range);
-    else
-        hipLaunchKernelGGL((slice_assemble_kernel<S, bf16_t>), grid, block, 0, stream, (bf16_t*)a, slice_idx, (const S*)src, depth, hs, ws, stride_z,
-                           first, k, thickness, h, w, oy, ox, total, lo, range);
-    return hip_status(hipGetLastError());
-}
-
 }  // namespace afcm
 
 extern "C" int afcm_slice_assemble(void* a, float* slice_idx, const void* src, int32_t src_dtype, int32_t out_dtype, int32_t depth, int32_t hs,
@@ -113,25 +92,20 @@ extern "C" int afcm_slice_assemble(void* a, float* slice_idx, const void* src, i
     AFCM_REQUIRE(k == 1 || k == 4, "slice_assemble: slice number %d is not 1 or 4", k);
     AFCM_REQUIRE(thickness != 0 && (k == 1 || thickness >= 1), "slice_assemble: thickness %d with slice number %d", thickness, k);
     AFCM_REQUIRE(max_value > min_value, "slice_assemble: max_value %g is not above min_value %g", max_value, min_value);
-    const long long total = (long long)count * k * h * w;
-    AFCM_REQUIRE((total + VOL_THREADS - 1) / VOL_THREADS < (1ll << 31), "slice_assemble: %lld output elements exceed the grid", total);
-    const int oy = (int)crop_offset(hs, h), ox = (int)crop_offset(ws, w);
     const double range = max_value - min_value;
-    hipStream_t s = (hipStream_t)stream;
-    switch (src_dtype) {
-        case AFCM_SRC_U8:
-            return launch_assemble<uint8_t>(a, out_dtype, slice_idx, src, depth, hs, ws, src_stride_z, first, k, thickness, h, w, oy, ox, total, min_value,
-                                            range, s);
-        case AFCM_SRC_I16:
-            return launch_assemble<int16_t>(a, out_dtype, slice_idx, src, depth, hs, ws, src_stride_z, first, k, thickness, h, w, oy, ox, total, min_value,
-                                            range, s);
-        case AFCM_SRC_F32:
-            return launch_assemble<float>(a, out_dtype, slice_idx, src, depth, hs, ws, src_stride_z, first, k, thickness, h, w, oy, ox, total, min_value,
-                                          range, s);
-        default:
-            return launch_assemble<double>(a, out_dtype, slice_idx, src, depth, hs, ws, src_stride_z, first, k, thickness, h, w, oy, ox, total, min_value,
-                                           range, s);
-    }
+    return dispatch_src_out(src_dtype, out_dtype, [&](auto s_tag, auto t_tag) -> int {
+        using S = typename decltype(s_tag)::type;
+        using T = typename decltype(t_tag)::type;
+        constexpr int RUN = run_length<T>;
+        const int runs = cdiv(w, RUN);
+        const double threads = (double)count * k * h * runs;                   // checked before the product is formed in 64 bits
+        AFCM_REQUIRE(threads / VOL_THREADS < 2147483647.0, "slice_assemble: %.0f output elements exceed the grid", (double)count * k * h * w);
+        const long long total = (long long)count * k * h * runs;
+        const long long groups = (total + VOL_THREADS - 1) / VOL_THREADS;
+        hipLaunchKernelGGL((slice_assemble_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, (hipStream_t)stream, (T*)a, slice_idx,
+                           (const S*)src, depth, hs, ws, (long long)src_stride_z, first, k, thickness, h, w, runs, total, min_value, range);
+        return hip_status(hipGetLastError());
+    });
 }
 
 extern "C" int afcm_halo_accumulate(float* map, uint8_t* mask, const void* pred, int32_t dtype, int64_t stride_b, int64_t stride_c, int64_t stride_d,

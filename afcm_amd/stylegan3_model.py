@@ -196,14 +196,24 @@ def capture_step(step, inputs, warmup=3):
     pool, so the captured graph replays the step on the SAME input tensors (refresh them in place between replays).  Returns the
     torch.cuda.CUDAGraph; `graph.replay()` runs one step.  What a replay does not do: Python-side bookkeeping (optimizer state['step'] --
     FusedScrubAdam.device_step() has the count --, loss tensors are those of the captured step's buffers, refreshed by every replay)."""
-    if step.buckets is not None or not step.optimizer_G.capturable or not getattr(getattr(step, 'optimizer_D', None), 'capturable', True):
-        raise RuntimeError('capture_step needs a single-process step built with capturable=True')
+    require_capturable(step, 'capture_step')
     real_A, real_B, z, c = inputs
 
     def one():
         step.set_input(real_A, real_B, z, c)
         step.optimize_parameters()
+    return capture_graph(one, warmup)
 
+
+def require_capturable(step, what):
+    if step.buckets is not None or not step.optimizer_G.capturable or not getattr(getattr(step, 'optimizer_D', None), 'capturable', True):
+        raise RuntimeError(f'{what} needs a single-process step built with capturable=True')
+
+
+def capture_graph(one, warmup=3, before_each=None, after_warmup=None):
+    """The capture recipe: ``max(1, warmup)`` eager runs of the step body ``one`` on a side stream, then ``one`` captured on the SAME stream into
+    the torch.cuda.CUDAGraph returned.  ``before_each()`` runs in front of every warm-up run and ``after_warmup()`` once after the last, both
+    on the side stream, neither inside the graph."""
     # warm-up AND capture on one side stream (allocator pools, workspace caches, pointer tables: everything lazy happens in the warm-up).  The same
     # stream for both, and the step's FIRST use of autograd should be this warm-up: a parameter's AccumulateGrad node runs on the stream that was
     # current when the node was made (the first time the parameter entered a graph) -- a step that has already run on the default stream would
@@ -212,7 +222,11 @@ def capture_step(step, inputs, warmup=3):
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         for _ in range(max(1, warmup)):
+            if before_each is not None:
+                before_each()
             one()
+        if after_warmup is not None:
+            after_warmup()
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()

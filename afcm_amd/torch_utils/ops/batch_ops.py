@@ -8,9 +8,6 @@ as a NaN item and reads nothing.  Both calls are asynchronous on the current str
 import torch
 
 from ... import _lib
-from .volume_ops import _SOURCE_DTYPES
-
-_OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 
 
 def _table(t, what, dtype, cols):
@@ -28,16 +25,13 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     tensors (a captured graph needs stable addresses); ``cursor``: DEVICE int64 scalar tensor, see ``advance_cursor``."""
     h, w = (int(v) for v in patch_hw)
     first, count = int(first), int(count)
-    if slice_num not in (1, 4):
-        raise RuntimeError(f'assemble_batch: slice number {slice_num} not supported (1 or 4)')
+    _lib.require_slice_num(slice_num, 'assemble_batch')
     if not isinstance(pool, torch.Tensor) or pool.dim() != 1 or not pool.is_contiguous() or pool.numel() < 1:
         raise RuntimeError(f'assemble_batch: the pool must be a non-empty contiguous 1-D tensor, got shape {tuple(getattr(pool, "shape", ()))}')
-    if pool.dtype not in _SOURCE_DTYPES:
-        raise RuntimeError(f'assemble_batch: source volumes are uint8 / int16 / float32 / float64, got {pool.dtype}')
+    code = _lib.source_code(pool.dtype, 'assemble_batch')
     _table(vols, 'the volume table', torch.int64, 4)
     _table(items, 'the item table', torch.int32, 4)
-    if dtype not in _OUT_DTYPES:
-        raise RuntimeError(f'assemble_batch: output dtype float32 / float16 / bfloat16, got {dtype}')
+    _lib.require_out_dtype(dtype, 'assemble_batch')
     if count < 1 or first < 0 or h < 1 or w < 1:
         raise RuntimeError(f'assemble_batch: {count} items from row {first} at [{h}, {w}]: count and the patch must be positive, first not negative')
     if cursor is not None and (not isinstance(cursor, torch.Tensor) or cursor.dtype != torch.int64 or cursor.numel() != 1):
@@ -60,7 +54,7 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     _lib.require_gpu(*tensors)
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f'assemble_batch: pool, tables, outputs and cursor must be on one device, got {sorted({str(t.device) for t in tensors})}')
-    rc = _lib.load().afcm_batch_assemble(a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), _SOURCE_DTYPES[pool.dtype],
+    rc = _lib.load().afcm_batch_assemble(a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), code,
                                          vols.data_ptr(), int(vols.shape[0]), items.data_ptr(), int(items.shape[0]), _lib.ptr(cursor), first, count,
                                          slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
     _lib.launched(rc, 'batch_assemble')

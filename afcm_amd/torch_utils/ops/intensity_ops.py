@@ -10,7 +10,6 @@ import torch
 
 from ... import _lib
 
-_SOURCE_DTYPES = {torch.uint8: _lib.SRC_U8, torch.int16: _lib.SRC_I16, torch.float32: _lib.SRC_F32, torch.float64: _lib.SRC_F64}
 _PLAN_VALUES = 11
 
 
@@ -29,10 +28,9 @@ def rescale_plan(voxels, dtype):
     """Where the select's seams are for a volume of ``voxels`` elements of torch ``dtype``, from the library itself (pure host, no GPU needed):
     {'groups': histogram workgroups, 'chunk': voxels of one workgroup per round of the grid, 'passes': digits, 'bits': their widths, most
     significant first}."""
-    if dtype not in _SOURCE_DTYPES:
-        raise RuntimeError(f'rescale_plan: source volumes are uint8 / int16 / float32 / float64, got {dtype}')
+    code = _lib.source_code(dtype, 'rescale_plan')
     plan = (C.c_int32 * _PLAN_VALUES)()
-    _lib.launched(_lib.load().afcm_rescale_plan(int(voxels), _SOURCE_DTYPES[dtype], plan), 'rescale_plan')
+    _lib.launched(_lib.load().afcm_rescale_plan(int(voxels), code, plan), 'rescale_plan')
     return {'groups': plan[0], 'chunk': plan[1], 'passes': plan[2], 'bits': tuple(plan[3:3 + plan[2]])}
 
 
@@ -45,8 +43,7 @@ def rescale_intensity(volume, percentiles=(0.5, 99.5), out=None):
     q_lo, q_hi = percentile_fractions(percentiles)
     if not isinstance(volume, torch.Tensor) or volume.dim() != 3:
         raise RuntimeError(f'rescale_intensity: expected a [D, H, W] tensor, got {type(volume).__name__} of shape {tuple(getattr(volume, "shape", ()))}')
-    if volume.dtype not in _SOURCE_DTYPES:
-        raise RuntimeError(f'rescale_intensity: source volumes are uint8 / int16 / float32 / float64, got {volume.dtype}')
+    code = _lib.source_code(volume.dtype, 'rescale_intensity')
     d, h, w = (int(v) for v in volume.shape)
     if min(d, h, w) < 1 or d * h * w >= 2 ** 31:
         raise RuntimeError(f'rescale_intensity: a volume has between 1 and 2^31 - 1 voxels, got shape {(d, h, w)}')
@@ -60,7 +57,6 @@ def rescale_intensity(volume, percentiles=(0.5, 99.5), out=None):
             raise RuntimeError(f'rescale_intensity: out is on {out.device}, the volume on {volume.device}')
     _lib.require_gpu(volume)
     lib = _lib.load()
-    code = _SOURCE_DTYPES[volume.dtype]
     if out is None:
         out = torch.empty((d, h, w), dtype=torch.uint8, device=volume.device)
     stats = torch.empty(3, dtype=torch.float64, device=volume.device)

@@ -9,8 +9,6 @@ import torch
 
 from ... import _lib
 
-_SOURCE_DTYPES = {torch.uint8: _lib.SRC_U8, torch.int16: _lib.SRC_I16, torch.float32: _lib.SRC_F32, torch.float64: _lib.SRC_F64}
-
 
 def _triple(v, what):
     v = tuple(int(x) for x in v)
@@ -28,25 +26,22 @@ def assemble_slices(volume, first, count, patch_shape, thickness=None, slice_num
     pd, h, w = _triple(patch_shape, 'assemble_slices: patch_shape')
     if pd != 1 or int(stride_shape[0]) != 1:
         raise RuntimeError(f'assemble_slices: patch depth {pd} with z stride {int(stride_shape[0])}: only one slice per patch and z stride 1 are supported')
-    if slice_num not in (1, 4):
-        raise RuntimeError(f'assemble_slices: slice number {slice_num} not supported (1 or 4)')
+    _lib.require_slice_num(slice_num, 'assemble_slices')
     if slice_num == 4 and thickness is None:
         raise RuntimeError('assemble_slices: slice number 4 needs a thickness')
     _lib.require_gpu(volume)
     if volume.dim() != 3:
         raise RuntimeError(f'assemble_slices: expected a [D, Hs, Ws] volume, got shape {tuple(volume.shape)}')
-    if volume.dtype not in _SOURCE_DTYPES:
-        raise RuntimeError(f'assemble_slices: source volumes are uint8 / int16 / float32 / float64, got {volume.dtype}')
+    code = _lib.source_code(volume.dtype, 'assemble_slices')
     depth, hs, ws = (int(v) for v in volume.shape)
     if volume.stride(2) != 1 or volume.stride(1) != ws:
         raise RuntimeError(f'assemble_slices: the rows of the source must be contiguous, got strides {tuple(volume.stride())}')
-    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise RuntimeError(f'assemble_slices: output dtype float32 / float16 / bfloat16, got {dtype}')
+    _lib.require_out_dtype(dtype, 'assemble_slices')
     first, count = int(first), int(count)
     a = torch.empty([max(count, 0), slice_num, h, w], dtype=dtype, device=volume.device)
     slice_idx = torch.empty([max(count, 0), 1], dtype=torch.float32, device=volume.device)
-    rc = _lib.load().afcm_slice_assemble(a.data_ptr(), slice_idx.data_ptr(), volume.data_ptr(), _SOURCE_DTYPES[volume.dtype], _lib.dtype_code(a), depth, hs,
-                                         ws, volume.stride(0), first, count, slice_num, -1 if thickness is None else int(thickness), h, w,
+    rc = _lib.load().afcm_slice_assemble(a.data_ptr(), slice_idx.data_ptr(), volume.data_ptr(), code, _lib.dtype_code(a), depth, hs, ws,
+                                         volume.stride(0), first, count, slice_num, -1 if thickness is None else int(thickness), h, w,
                                          float(min_value), float(max_value), _lib.stream_ptr(volume))
     _lib.launched(rc, 'slice_assemble')
     return a, slice_idx

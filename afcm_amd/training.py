@@ -10,13 +10,12 @@ replayed graph that reads its batch through a device-side cursor: no host data w
 import numpy as np
 import torch
 
+from . import _lib
 from .data import SliceDataset, open_volumes
 from .intensity import rescale_intensity_host
 from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch
+from .stylegan3_model import capture_graph, require_capturable
 from .torch_utils.ops.intensity_ops import percentile_fractions, rescale_intensity
-
-_NUMPY_SOURCES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.int16): torch.int16, np.dtype(np.float32): torch.float32,
-                  np.dtype(np.float64): torch.float64}
 
 
 class DeviceSliceSet:
@@ -39,8 +38,7 @@ class DeviceSliceSet:
         patch_shape = tuple(int(v) for v in patch_shape)
         if len(patch_shape) != 3 or patch_shape[0] != 1 or min(patch_shape) < 1:
             raise RuntimeError(f'DeviceSliceSet: patch_shape must be (1, H, W), got {patch_shape}')
-        if slice_num not in (1, 4):
-            raise RuntimeError(f'DeviceSliceSet: slice number {slice_num} not supported (1 or 4)')
+        _lib.require_slice_num(slice_num, 'DeviceSliceSet')
         self.phase, self.patch_shape, self.rand_output, self.slice_num = phase, patch_shape, bool(rand_output), int(slice_num)
         self.raw_internal_path_in, self.raw_internal_path_out = list(raw_internal_path_in), list(raw_internal_path_out)
         self.thickness = [int(t) for t in thickness]
@@ -61,8 +59,7 @@ class DeviceSliceSet:
         if self.rescale is None and len(dtypes) != 1:
             raise RuntimeError(f'DeviceSliceSet: mixed source dtypes {dtypes}: the pool holds one dtype, convert the volumes first')
         for name in dtypes:
-            if np.dtype(name) not in _NUMPY_SOURCES:
-                raise RuntimeError(f'DeviceSliceSet: source volumes are uint8 / int16 / float32 / float64, got {name}')
+            _lib.source_code(np.dtype(name), 'DeviceSliceSet')
         self.source_dtype = np.dtype(np.uint8) if self.rescale is not None else np.dtype(dtypes[0])
         rows, offset, self.depths = [], 0, []
         for s, subject in enumerate(self.volumes):
@@ -216,6 +213,19 @@ def _label(step, slice_idx):
     return slice_idx if step.netG.c_dim > 0 else torch.zeros_like(slice_idx)
 
 
+def _fed_step(step, schedule, batch_size, batch, gen_z, cur_nimg=None):
+    """One training step on the batch ``batch()`` returns, as ``train_epoch``, ``TrainingGraph`` and ``train_epochs`` all run it: with a
+    ``schedule`` (the step's own ``DeviceSchedule``) ``schedule.advance(batch_size)`` first -- total_iters, sigma and beta are the block's -- and,
+    when the step has an EMA copy and the schedule an ``ema_kimgs``, ``step.update_ema()`` last."""
+    if schedule is not None:
+        schedule.advance(batch_size)
+    a, b, slice_idx = batch()
+    step.set_input(a, b, gen_z=gen_z, gen_c=_label(step, slice_idx))
+    step.optimize_parameters(cur_nimg=cur_nimg)
+    if schedule is not None and schedule.ema_kimgs is not None and step.netG_ema is not None:
+        step.update_ema()
+
+
 def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None):
     """The inner loop of the reference's train.py:45-77 over the epoch table ``items`` (``DeviceSliceSet.epoch_items``): per batch
     ``total_iters += batch_size``, ``step.set_input(A, B, gen_c=slice_idx)``, ``step.optimize_parameters(cur_nimg=total_iters)`` and, when the step
@@ -237,16 +247,10 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     schedule = getattr(step, 'schedule', None) if where == 'device' else None
     for first in range(0, n, batch_size):
         count = min(batch_size, n - first)
-        a, b, slice_idx = dataset.batch(first, count) if where == 'device' else dataset.host_batch(items, first, count, device=device)
+        batch = (lambda: dataset.batch(first, count)) if where == 'device' else (lambda: dataset.host_batch(items, first, count, device=device))
         total_iters += batch_size
-        if schedule is not None:                            # the two calls TrainingGraph captures, eagerly: total_iters, sigma and beta are the block's
-            schedule.advance(batch_size)
-        step.set_input(a, b, gen_z=None if gen_z is None else gen_z[:count], gen_c=_label(step, slice_idx))
-        step.optimize_parameters(cur_nimg=total_iters)
-        if schedule is not None:
-            if schedule.ema_kimgs is not None and step.netG_ema is not None:
-                step.update_ema()
-        elif ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
+        _fed_step(step, schedule, batch_size, batch, None if gen_z is None else gen_z[:count], cur_nimg=total_iters)
+        if schedule is None and ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
             step.update_ema(batch_size, total_iters, ema_kimgs=ema_kimgs, ramp=ramp)
     return total_iters
 
@@ -268,8 +272,7 @@ class TrainingGraph:
     ``capture_step`` does.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None."""
 
     def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None, undo_warmup=False):
-        if step.buckets is not None or not step.optimizer_G.capturable or not getattr(getattr(step, 'optimizer_D', None), 'capturable', True):
-            raise RuntimeError('TrainingGraph needs a single-process step built with capturable=True')
+        require_capturable(step, 'TrainingGraph')
         dataset._need_device('TrainingGraph')
         batch_size = int(batch_size)
         if batch_size < 1 or dataset.rows < batch_size:
@@ -285,34 +288,25 @@ class TrainingGraph:
             raise RuntimeError(f'TrainingGraph: gen_z must be [{batch_size}, {step.netG.z_dim}], got {tuple(self.gen_z.shape)}')
 
         schedule = getattr(step, 'schedule', None)
-        ema_inside = schedule is not None and schedule.ema_kimgs is not None and step.netG_ema is not None
-
-        def one():
-            if schedule is not None:
-                schedule.advance(batch_size)
-            dataset.batch(0, batch_size, out=(self.real_A, self.real_B, self.slice_idx), use_cursor=True)
-            advance_cursor(dataset.cursor, batch_size)
-            step.set_input(self.real_A, self.real_B, gen_z=self.gen_z, gen_c=_label(step, self.slice_idx))
-            step.optimize_parameters()
-            if ema_inside:
-                step.update_ema()
-
         saved = None if schedule is None else schedule.block.clone()
         optimizers = [opt for opt in (step.optimizer_G, getattr(step, 'optimizer_D', None)) if opt is not None]
         if undo_warmup:
             tensors = [t for name in step.model_names for net in [getattr(step, 'net' + name)] for t in list(net.parameters()) + list(net.buffers())]
             before = [t.detach().clone() for t in tensors], [opt.snapshot() for opt in optimizers]
-        # warm-up and capture on one side stream, the step's first use of autograd: see capture_step
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                if dataset.position + batch_size > dataset.rows:
-                    dataset.rewind()
-                if not self.fixed_z:
-                    self.gen_z.normal_()
-                one()
-                dataset.position += batch_size
+
+        def cursor_batch():
+            out = dataset.batch(0, batch_size, out=(self.real_A, self.real_B, self.slice_idx), use_cursor=True)
+            advance_cursor(dataset.cursor, batch_size)
+            return out
+
+        def next_rows():                                      # what replay() does around the graph
+            if dataset.position + batch_size > dataset.rows:
+                dataset.rewind()
+            if not self.fixed_z:
+                self.gen_z.normal_()
+            dataset.position += batch_size
+
+        def leave_no_trace():
             dataset.rewind()
             if saved is not None:
                 schedule.block.copy_(saved)               # the warm-up's steps are real ones, but total_iters stays where it was
@@ -322,11 +316,8 @@ class TrainingGraph:
                         t.copy_(v)
                 for opt, state in zip(optimizers, before[1]):
                     opt.restore(state)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode='thread_local'):
-            one()
+
+        self.graph = capture_graph(lambda: _fed_step(step, schedule, batch_size, cursor_batch, self.gen_z), warmup, next_rows, leave_no_trace)
 
     def load_epoch(self, items):
         self.dataset.load_epoch(items)
@@ -360,7 +351,6 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
     if batch_size < 1:
         raise ValueError(f'batch_size {batch_size}')
     rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
-    ema = schedule.ema_kimgs is not None and step.netG_ema is not None
     runner, steps = None, 0
     for k, epoch in enumerate(epochs, start=1):
         lr = lr_schedule.lr_at(k)
@@ -375,12 +365,7 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
             if graph:
                 runner.replay()
             else:
-                schedule.advance(batch_size)
-                a, b, slice_idx = dataset.batch(first, batch_size)
-                step.set_input(a, b, gen_z=gen_z, gen_c=_label(step, slice_idx))
-                step.optimize_parameters()
-                if ema:
-                    step.update_ema()
+                _fed_step(step, schedule, batch_size, lambda: dataset.batch(first, batch_size), gen_z)
             steps += 1
         if on_epoch is not None:
             on_epoch(epoch, step)

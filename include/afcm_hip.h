@@ -565,7 +565,7 @@ enum { AFCM_SRC_U8 = 0, AFCM_SRC_I16 = 1, AFCM_SRC_F32 = 2, AFCM_SRC_F64 = 3 };
  *            min and max - min are rounded to float32 first).  Then one rounding to float32, and one more to a 16-bit out_dtype.
  *   label    slice_idx[i] = float32(idx - idx_a) / float32(thickness), one IEEE division (k = 1: idx_a = idx; the loader's "no thickness" is
  *            thickness = -1, which gives -0.0f).
- * One thread per output element, consecutive lanes along x.  AFCM_E_INVALID: null pointers, unknown dtypes, depth / hs / ws / h / w < 1, a slice
+ * One thread per 16 bytes of one output row, as in afcm_batch_assemble below.  AFCM_E_INVALID: null pointers, unknown dtypes, depth / hs / ws / h / w < 1, a slice
  * range outside [0, depth], k not 1 or 4, thickness 0 (or < 1 with k = 4), src_stride_z < 0, max_value <= min_value, more than 2^31 - 1 workgroups. */
 int afcm_slice_assemble(void* a, float* slice_idx, const void* src, int32_t src_dtype, int32_t out_dtype, int32_t depth, int32_t hs, int32_t ws,
                         int64_t src_stride_z, int32_t first, int32_t count, int32_t k, int32_t thickness, int32_t h, int32_t w, double min_value,
@@ -621,8 +621,8 @@ int afcm_volume_ssim(double* layers, const void* ref, const void* test, int32_t 
  *                       A position outside [0, depth - 1] is a plane of float64 zeros BEFORE normalisation.
  *   b [count][1][h][w]  slice idx of volume vol_b.
  *   slice_idx [count]   float32(idx - idx_a) / float32(t) (k = 1: idx_a = idx; "no thickness" is t = -1, which gives -0.0f).
- * Crop / pad (per volume, from its own hs, ws), the normalisation in numpy's type for the source, the roundings and out_dtype are those of
- * afcm_slice_assemble above; a and b are contiguous and both of out_dtype.
+ * Crop / pad (per volume, from its own hs, ws), the normalisation in numpy's type for the source, the roundings and out_dtype are
+ * afcm_slice_assemble's: both kernels call one body (csrc/volume_common.h); a and b are contiguous and both of out_dtype.
  * The tables cannot be checked at launch, so the KERNEL checks every row before it reads the pool.  An item is invalid when its row is outside
  * [0, n_items) (a cursor outside it included); vol_a or vol_b is outside [0, n_vols); a descriptor has a non-positive extent or an
  * [offset, offset + depth hs ws) outside [0, pool_elems); the two descriptors' (depth, hs, ws) differ; idx is outside [0, depth); thickness is 0, or

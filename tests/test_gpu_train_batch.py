@@ -91,6 +91,27 @@ def test_16bit_outputs_are_one_more_rounding(out_dtype, hw, loader_items):
             _same_bits(c, want[2][sl])
 
 
+@pytest.mark.parametrize('k', [4, 1])
+@pytest.mark.parametrize('dtype', [np.uint8, np.float32])
+def test_batch_items_equal_slice_assembly(dtype, k):
+    """The two loader entry points against each other: every row of a batch is ``assemble_slices`` on the row's own volumes, target by target --
+    ``A[i]`` and ``slice_idx[i]`` the call on ``vol_a`` with the row's thickness, ``B[i]`` the ``slice_num=1`` call on ``vol_b``."""
+    from afcm_amd.torch_utils.ops.volume_ops import assemble_slices
+    hw = (12, 10)
+    lo, hi = T.value_range(dtype)
+    ds = _device_set(dtype, hw, k)
+    items = T.shuffled_items(k)
+    ds.load_epoch(items)
+    a, b, c = ds.batch(0, len(items))
+    volumes = [ds.pool[off:off + d * hs * ws].view(d, hs, ws) for off, d, hs, ws in ds.vols_host.tolist()]
+    for i, (va, vb, idx, t) in enumerate(items.tolist()):
+        want_a, want_c = assemble_slices(volumes[va], idx, 1, (1,) + hw, thickness=t, slice_num=k, min_value=lo, max_value=hi)
+        want_b, _ = assemble_slices(volumes[vb], idx, 1, (1,) + hw, slice_num=1, min_value=lo, max_value=hi)
+        _same_bits(a[i:i + 1], want_a.cpu())
+        _same_bits(c[i:i + 1], want_c.cpu())
+        _same_bits(b[i:i + 1], want_b.cpu())
+
+
 def test_out_writes_in_place_and_repeats_bit_for_bit(loader_items):
     want = loader_items(np.uint8, (12, 10), 4)
     ds = _device_set(np.uint8, (12, 10), 4)

@@ -126,11 +126,12 @@ def test_assembly_equals_stacked_dataset_items(name):
     assert a.shape == (shape[0], slice_num) + hw and idx.shape == (shape[0], 1)
     _same_bits(a, want_a)
     _same_bits(idx, want_idx)
-    if slice_num == 4:                                    # zero planes at both ends (targets 0-4 and 15-22), at the value a zero normalises to
+    if slice_num == 4:                                    # zero planes at both ends (depth 23, thickness 5: targets 0-4 and 15-22), at the value
+        before, after = R.zero_plane_targets(shape[0], thickness)                  # a zero normalises to
         pad_value = np.float32(np.clip(2 * ((0.0 - lo) / (hi - lo)) - 1, -1, 1))
-        assert (a[:5, 0] == float(pad_value)).all() and (a[15:, 3] == float(pad_value)).all()
+        assert (a[before, 0] == float(pad_value)).all() and (a[after, 3] == float(pad_value)).all()
         assert (pad_value == -1) == (lo == 0.0)
-    for first, count in ((7, 4), (shape[0] - 3, 3)):      # a run in the middle; a batch that ends at the last slice
+    for first, count in ((shape[0] // 3, 4), (shape[0] - 3, 3)):      # a run in the middle; a batch that ends at the last slice
         part_a, part_idx = assemble_slices(vol, first, count, (1,) + hw, **kw)
         _same_bits(part_a, want_a[first:first + count])
         _same_bits(part_idx, want_idx[first:first + count])

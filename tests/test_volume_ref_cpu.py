@@ -65,13 +65,15 @@ def test_assembly_reference_equals_the_slice_dataset(name):
     assert got_a.dtype == want_a.dtype == np.float32 and got_a.shape == want_a.shape == (shape[0], slice_num) + hw
     assert np.array_equal(got_a.view(np.uint32), want_a.view(np.uint32))                 # bit for bit (the sign of a zero included)
     assert np.array_equal(got_idx.view(np.uint32), want_idx.view(np.uint32))
-    if slice_num == 4:                                     # zero planes at both ends: targets 0-4 lack the slice before, 15-22 the second after
+    if slice_num == 4:                                     # zero planes at both ends (depth 23, thickness 5: targets 0-4 lack the slice before,
+        before, after = R.zero_plane_targets(shape[0], thickness)          # 15-22 the second after)
+        assert shape[0] != 23 or (before, after) == (list(range(5)), list(range(15, 23)))
         pad_value = np.float32(np.clip(2 * ((0.0 - lo) / (hi - lo)) - 1, -1, 1))
-        assert (got_a[:5, 0] == pad_value).all() and (got_a[15:, 3] == pad_value).all() and not (got_a[5:, 0] == pad_value).all()
+        assert (got_a[before, 0] == pad_value).all() and (got_a[after, 3] == pad_value).all() and not (got_a[len(before):, 0] == pad_value).all()
         if lo != 0.0:
             assert pad_value != -1
     # a run in the middle and one that ends at the last slice are the same rows
-    for first, count in ((7, 4), (shape[0] - 3, 3)):
+    for first, count in ((shape[0] // 3, 4), (shape[0] - 3, 3)):
         part_a, part_idx = R.assemble(src, first, count, slice_num, thickness, hw[0], hw[1], lo, hi)
         assert np.array_equal(part_a, got_a[first:first + count]) and np.array_equal(part_idx, got_idx[first:first + count])
 
@@ -175,7 +177,9 @@ def test_predict_volume_host_arm_is_the_hand_rolled_loop():
 
 def test_volume_kernels_use_no_scratch_and_no_lds():
     """Code-object metadata of the built volume.o: both kernels, every dtype instance, without scratch, spills or LDS (DESIGN section 8g quotes the
-    registers).  The object is a build product; a tree that has the library but not the object compiles this one file."""
+    registers).  ``slice_assemble_kernel`` produces 16 output bytes per thread, as ``batch_assemble_kernel`` does, and is held to the same bound:
+    64 VGPRs, the largest allocation that still gives 8 waves per SIMD (min(8, 512 / allocation)): the occupancy bound, not a measured need.
+    ``halo_accumulate_kernel`` keeps its 32.  The object is a build product; a tree that has the library but not the object compiles this one file."""
     import os
     import subprocess
     import sys
@@ -189,4 +193,4 @@ def test_volume_kernels_use_no_scratch_and_no_lds():
     assert len(kernels) == 4 * 3 + 3, [k['name'] for k in kernels]
     for k in kernels:
         assert k.get('scratch', 0) == 0 and k.get('vgpr_spill', 0) == 0 and k.get('sgpr_spill', 0) == 0 and k.get('lds', 0) == 0, k
-        assert k.get('vgpr', 0) <= 32, k
+        assert k.get('vgpr', 0) <= (64 if 'slice_assemble_kernel' in k['name'] else 32), k

@@ -33,7 +33,19 @@ ASSEMBLY_CASES = {   # name: (source shape, dtype, (H, W), thickness, slice_num,
     'pad_f32': ((23, 28, 30), np.float32, (32, 32), 5, 4, (-100., 900.)),
     'crop_f32': ((23, 40, 36), np.float32, (32, 32), 5, 4, (-100., 900.)),
     'pad_f64': ((23, 28, 30), np.float64, (32, 32), 5, 4, (-100., 900.)),
+    # rows that are no whole number of 16-byte runs.  W = 10: float32 rows of 40 bytes start on and off a 16-byte boundary in turn, 16-bit rows are
+    # one run and a tail of 2; W = 6: shorter than a 16-bit run.  x cropped (u8, f32, f64) and padded (i16), y padded (f32) and cropped (the rest)
+    'tail_u8': ((11, 13, 18), np.uint8, (12, 10), 3, 4, (0., 255.)),
+    'tail_f32': ((11, 9, 23), np.float32, (12, 10), 5, 4, (-100., 900.)),
+    'tail_i16_k1': ((7, 16, 7), np.int16, (12, 10), None, 1, (-100., 900.)),
+    'narrow_f64': ((7, 20, 16), np.float64, (8, 6), 2, 4, (-100., 900.)),
 }
+
+
+def zero_plane_targets(depth, thickness):
+    """The targets whose plane 0 (the thick slice before the target's own) and whose plane 3 (the second after it) lie outside the volume."""
+    own = [(i // thickness) * thickness for i in range(depth)]
+    return [i for i in range(depth) if own[i] - thickness < 0], [i for i in range(depth) if own[i] + 2 * thickness > depth - 1]
 
 
 def starts(n, k, s):

@@ -1,39 +1,22 @@
 """Feeding the training step: what a batch of 16 x (4 + 1) planes at 256^2 costs the host way and the device way, and what the fed graph costs
-against the fixed-input one.  Three steps, each its own process (run each under its own time limit; chain them with && from a script):
+against the fixed-input one.  Two steps, each its own process (run each under its own time limit; chain them with && from a script):
 
-    python tools/bench_train_feed.py forms                 # no GPU: compiles csrc/batch.hip in both kernel forms into afcm_amd/csrc/variants/
-    python tools/bench_train_feed.py feed  [--repeats 5]   # (a) host arm against device arm, ms per batch; (b) the launch alone, both forms, device events
+    python tools/bench_train_feed.py feed  [--repeats 5]   # (a) host arm against device arm, ms per batch; (b) the launch alone, device events
     python tools/bench_train_feed.py step  [--repeats 3]   # TrainingGraph.replay() against capture_step's replay on fixed inputs, full-width bf16
 
 (a) alternates ``DeviceSliceSet.host_batch`` (SliceDataset items in numpy, stacked, uploaded) and ``DeviceSliceSet.batch`` (one launch) over the same
 rows of a synthetic uint8 set after a warm-up of each, the alternation repeated; wall time by a host clock ended by a synchronise.  (b) times
-``afcm_batch_assemble`` in the run form (16 bytes per thread and store) and the element form (one element per thread, as slice_assemble_kernel) from
-two builds of the one source file, per output byte, with ``afcm_slice_assemble`` on 16 x 4 x 256^2 fp32 beside them as the yardstick; the two forms'
-outputs are compared bit for bit.  No timing here is gated by a test; the numbers go to DESIGN section 8i with their spread."""
+``afcm_batch_assemble`` on 16 x (4 + 1) x 256^2, fp32 and bf16, and ``afcm_slice_assemble`` on 16 x 4 x 256^2 fp32, per output byte, in the loaded
+library (``AFCM_HIP_LIB`` names another build to set beside it).  No timing here is gated by a test; the numbers go to DESIGN section 8i with their
+spread."""
 import argparse
-import ctypes
 import json
 import os
-import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-CSRC = os.path.join(ROOT, 'afcm_amd', 'csrc')
-VARIANTS = os.path.join(CSRC, 'variants')
-FORMS = {'run16': 16, 'element': 0}
-
-
-def forms(args):
-    os.makedirs(VARIANTS, exist_ok=True)
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    for name, run_bytes in FORMS.items():
-        out = os.path.join(VARIANTS, f'libbatch_{name}.so')
-        subprocess.check_call([hipcc, '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-ffp-contract=off', '-shared', f'-DAFCM_BATCH_RUN_BYTES={run_bytes}',
-                               os.path.join(CSRC, 'batch.hip'), os.path.join(CSRC, 'common.hip'), '-o', out])
-        print('built', os.path.relpath(out, ROOT))
-    return 0
 
 
 def synthetic_set(subjects, depth, res, device, **kw):
@@ -100,33 +83,23 @@ def feed(args):
         print(f'{name:8s} ms/batch per repeat {"  ".join(f"{x:8.4f}" for x in v)}   mean {stats[name]["mean_ms"]:8.4f}   spread {stats[name]["spread_ms"]:.4f}')
     print(f'the two arms\' last batches are {"bit-identical" if equal else "DIFFERENT"}')
 
-    # the launch alone, both forms: the same call on the same tables through two builds of csrc/batch.hip
-    launches, outputs = {}, {}
+    # the launch alone: the C entry point on the loaded epoch's tables, outputs reused
+    launches, lib = {}, _lib.load()
     for out_name, out_dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
         a = torch.empty((args.batch, 4, args.res, args.res), dtype=out_dtype, device=dev)
         b = torch.empty((args.batch, 1, args.res, args.res), dtype=out_dtype, device=dev)
         c = torch.empty((args.batch, 1), dtype=torch.float32, device=dev)
         out_bytes = a.numel() * a.element_size() + b.numel() * b.element_size()
-        for form in FORMS:
-            path = os.path.join(VARIANTS, f'libbatch_{form}.so')
-            if not os.path.exists(path):
-                raise SystemExit(f'{path} is missing: run `python tools/bench_train_feed.py forms` first')
-            lib = ctypes.CDLL(path)
-            res, argtypes = _lib.SIGNATURES['afcm_batch_assemble']
-            lib.afcm_batch_assemble.restype, lib.afcm_batch_assemble.argtypes = res, argtypes
-            stream = _lib.stream_ptr(a)
+        stream = _lib.stream_ptr(a)
 
-            def launch():
-                rc = lib.afcm_batch_assemble(a.data_ptr(), b.data_ptr(), c.data_ptr(), ds.pool.data_ptr(), ds.pool.numel(), _lib.SRC_U8, ds.vols.data_ptr(),
-                                             int(ds.vols.shape[0]), ds.items.data_ptr(), int(ds.items.shape[0]), None, 0, args.batch, 4, args.res, args.res,
-                                             _lib.dtype_code(a), 0., 255., stream)
-                assert rc == 0, rc
-            us = [events_us(launch) for _ in range(args.repeats)]
-            launches[f'{form}_{out_name}'] = dict(per_repeat_us=us, mean_us=sum(us) / len(us), spread_us=spread(us), ns_per_kib=sum(us) / len(us) * 1e3 / (out_bytes / 1024))
-            outputs[(form, out_name)] = (a.clone(), b.clone(), c.clone())
-        same = all(torch.equal(x.view(torch.int16), y.view(torch.int16)) for x, y in zip(outputs[('run16', out_name)], outputs[('element', out_name)]))
-        equal = equal and same
-        print(f'{out_name}: the two forms\' outputs are {"bit-identical" if same else "DIFFERENT"}')
+        def launch():
+            rc = lib.afcm_batch_assemble(a.data_ptr(), b.data_ptr(), c.data_ptr(), ds.pool.data_ptr(), ds.pool.numel(), _lib.SRC_U8, ds.vols.data_ptr(),
+                                         int(ds.vols.shape[0]), ds.items.data_ptr(), int(ds.items.shape[0]), None, 0, args.batch, 4, args.res, args.res,
+                                         _lib.dtype_code(a), 0., 255., stream)
+            assert rc == 0, rc
+        us = [events_us(launch) for _ in range(args.repeats)]
+        launches[f'batch_assemble_{out_name}'] = dict(per_repeat_us=us, mean_us=sum(us) / len(us), spread_us=spread(us),
+                                                      ns_per_kib=sum(us) / len(us) * 1e3 / (out_bytes / 1024))
     volume = ds.pool[:args.depth * args.res * args.res].view(args.depth, args.res, args.res)
     us = [events_us(lambda: assemble_slices(volume, 0, args.batch, (1, args.res, args.res), thickness=5)) for _ in range(args.repeats)]
     launches['slice_assemble_fp32'] = dict(per_repeat_us=us, mean_us=sum(us) / len(us), spread_us=spread(us),
@@ -196,7 +169,7 @@ def step(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('what', choices=['forms', 'feed', 'step'])
+    ap.add_argument('what', choices=['feed', 'step'])
     ap.add_argument('--subjects', type=int, default=4)
     ap.add_argument('--depth', type=int, default=64)
     ap.add_argument('--res', type=int, default=256)
@@ -205,7 +178,7 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=3)
     args = ap.parse_args()
-    return {'forms': forms, 'feed': feed, 'step': step}[args.what](args)
+    return {'feed': feed, 'step': step}[args.what](args)
 
 
 if __name__ == '__main__':
