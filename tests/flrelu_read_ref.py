@@ -205,6 +205,29 @@ def first_pad(n, up, down, p0, fut, fdt, even, at_least=1):
         p1 += 1
 
 
+def geometry(kern, yh, yw, mx=5, my=6):
+    """Input size and padding of a forward of `kern` with a yh x yw output whose backward reads its codes at (mx, my) mod 16 (my >= up:
+    the aligned sign-reading call moves its strips' origin up, oy0 < 0): px0 / py0 as sweep_case, the input extent the
+    smallest even one for which px1 >= px0 - up gives exactly the output asked for."""
+    up, down, fu, fd = KERNELS[kern]
+    F = filters()
+    fut, fdt = len(F[fu]), len(F[fd])
+    k = up // 2
+
+    def axis(t, m):
+        p0 = m + fut - 1 - 16 * k
+        need = (t - 1) * down + 1 + (fdt - 1) + (fut - 1)          # n up + p0 + p1 for the smallest upsampled extent that gives t outputs
+        n = max(2, -(-(need - 2 * p0) // up))
+        n += n & 1
+        p1 = need - n * up - p0
+        assert out_size(n, up, down, p0, p1, fut, fdt) == t
+        return n, p0, p1
+
+    w, px0, px1 = axis(yw, mx)
+    h, py0, py1 = axis(yh, my)
+    return h, w, [px0, px1, py0, py1]
+
+
 # ------------------------------------------------------------------------------------------------- (a) padding sweep, public op
 def sweep_case(kern, mx, my, h=20, w=20, dtype='float16', seed=0):
     """One forward of the public op whose backward reads its codes at (sx, sy) = (mx, my) mod 16: px0 = mx + (fu taps - 1) - 16 k

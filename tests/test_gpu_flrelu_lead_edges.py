@@ -16,33 +16,11 @@ import pytest
 import torch
 
 import flrelu_read_ref as R
+from flrelu_read_ref import geometry as _geometry
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = [('float16', R.TOL_MATRIX['float16']), ('bfloat16', R.TOL_MATRIX['bfloat16'])]
-
-
-def _geometry(kern, yh, yw, mx=5, my=6):
-    """Input size and padding of a forward of `kern` with a yh x yw output whose backward reads its codes at (mx, my) mod 16 (my >= up:
-    the aligned sign-reading call moves its strips' origin up, oy0 < 0): px0 / py0 as flrelu_read_ref.sweep_case, the input extent the
-    smallest even one for which px1 >= px0 - up gives exactly the output asked for."""
-    up, down, fu, fd = R.KERNELS[kern]
-    F = R.filters()
-    fut, fdt = len(F[fu]), len(F[fd])
-    k = up // 2
-
-    def axis(t, m):
-        p0 = m + fut - 1 - 16 * k
-        need = (t - 1) * down + 1 + (fdt - 1) + (fut - 1)          # n up + p0 + p1 for the smallest upsampled extent that gives t outputs
-        n = max(2, -(-(need - 2 * p0) // up))
-        n += n & 1
-        p1 = need - n * up - p0
-        assert R.out_size(n, up, down, p0, p1, fut, fdt) == t
-        return n, p0, p1
-
-    w, px0, px1 = axis(yw, mx)
-    h, py0, py1 = axis(yh, my)
-    return h, w, [px0, px1, py0, py1]
 
 
 def _in_nan(t, pitched):
