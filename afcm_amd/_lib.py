@@ -14,6 +14,7 @@ SIGNS_NONE, SIGNS_WRITE, SIGNS_READ = 0, 1, 2
 SRC_U8, SRC_I16, SRC_F32, SRC_F64 = 0, 1, 2, 3
 SCHEDULE_SLOTS = 8
 EMA_LERP, EMA_COPY = 0, 1
+GROUP_2B, GROUP_4B = 2, 4
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 OUT_DTYPES = tuple(_DTYPES)
@@ -159,6 +160,8 @@ SIGNATURES = {
     'afcm_rescale_plan': (C.c_int, [_i64, _i32, C.POINTER(_i32)]),
     'afcm_rescale_workspace_bytes': (C.c_int64, [_i64, _i32]),
     'afcm_rescale_intensity': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _f64, _f64, _vp]),
+    'afcm_group_chunk_bytes': (C.c_int32, []),
+    'afcm_group_expand': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
 }
 
 

@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from . import layer_schedule as sched
-from .torch_utils.ops import affine_bank, bias_act, conv2d_gradfix, fc_bank, filtered_lrelu, fused_layer, modulation_bank
+from .torch_utils.ops import affine_bank, bias_act, conv2d_gradfix, fc_bank, filtered_lrelu, fused_layer, group_ops, modulation_bank
 from .torch_utils.ops import conv2d as _conv_ops
 from .torch_utils.ops.conv2d import modulation_coefficients_fused, scaled_conv2d
 from .torch_utils.ops.conv2d import modulated_conv2d  # noqa: F401  (re-exported: NET:25 lives in this module)
@@ -410,6 +410,15 @@ class Conv2dLayer(torch.nn.Module):
         return bias_act.bias_act(x, b, act=self.activation, gain=act_gain, clamp=act_clamp)
 
 
+class EncoderState:
+    """What ``SynthesisNetwork.encode`` hands to ``decode``: the bottleneck ``x``, the skip maps ``E_features`` {plane size: tensor} and the global
+    vector ``img_global`` -- functions of the conditioning image alone."""
+    __slots__ = ('x', 'E_features', 'img_global')
+
+    def __init__(self, x, E_features, img_global):
+        self.x, self.E_features, self.img_global = x, E_features, img_global
+
+
 class SynthesisNetwork(torch.nn.Module):
     """Alias-free encoder (14 layers) -> global vector -> co-modulated alias-free decoder (15 layers) (NET:556-712)."""
 
@@ -488,8 +497,12 @@ class SynthesisNetwork(torch.nn.Module):
 
     def forward(self, ws, img_in, **layer_kwargs):
         _assert_shape(ws, [None, self.num_ws, self.w_dim])
-        ws_stack = ws
-        ws = ws.to(torch.float32).unbind(dim=1)
+        ws = ws.to(torch.float32)                                # (before the encoder, where a cast of the latents has always been issued)
+        return self.decode(ws, self.encode(img_in), **layer_kwargs)
+
+    def encode(self, img_in):
+        """The half of ``forward`` that depends on the conditioning image alone: the encoder layers, ``e_16x16``, the 4x4 pool and ``fc_in``
+        (the reference passes no kwargs to them, NET:678).  Returns the ``EncoderState`` that ``decode`` takes."""
         img_in = F.pad(img_in.to(self.compute_dtype), [self.margin_size] * 4, 'constant', 0)
 
         # every conv weight of the step exists before its first convolution: the 16-bit MFMA images (forward + data gradient) of all
@@ -515,13 +528,55 @@ class SynthesisNetwork(torch.nn.Module):
         img_pool = self._pool4(img_pool)                         # (fp32 out)
         img_pool = self.fc_in(img_pool.flatten(1))
         img_global = self.dropout(img_pool)
+        return EncoderState(img_in, E_features, img_global)
 
-        x = img_in
-        res_idx = 1
+    def _skip_plan(self):
+        """Per decoder layer: does it read its skip map (NET:693-700)?"""
+        plan, res_idx = [], 1
+        for idx in range(len(self.layer_names)):
+            nxt = min(idx + 1, len(self.layer_names) - 1)
+            if (self.sizes[idx] != self.sizes[nxt]) and self.sizes[idx] != self.sizes[0]:
+                plan.append(self.skip_connects[res_idx])
+                res_idx += 1
+            else:
+                plan.append(False)
+        return plan
+
+    def _expand_state(self, state, groups, batch, layers, skip_plan, update_emas):
+        """The state of G conditioning images as the state of ``batch`` samples, sample b from image ``groups[b]``: the bottleneck, the skip
+        maps a decoder layer reads and the global vector, one launch (torch_utils/ops/group_ops.py).  Inference only."""
+        if torch.is_grad_enabled():
+            raise RuntimeError('decode(groups=...) is inference only: call it under torch.no_grad()')
+        if self.training:
+            raise RuntimeError('decode(groups=...) is inference only: dropout would make the shared and the repeated encoder differ; call .eval()')
+        if update_emas:
+            raise RuntimeError('decode(groups=...) is inference only: update_emas=True is refused')
+        if not isinstance(groups, torch.Tensor) or groups.dtype != torch.int32 or groups.ndim != 1 or groups.shape[0] != batch:
+            got = f'{groups.dtype} {tuple(groups.shape)}' if isinstance(groups, torch.Tensor) else type(groups).__name__
+            raise RuntimeError(f'decode(groups=...): groups must be an int32 tensor [{batch}] (one entry per row of ws), got {got}')
+        keys = []
+        for layer, skip in zip(layers, skip_plan):
+            key = layer.out_size[0]
+            if skip and key in state.E_features and key not in keys:
+                keys.append(key)
+        out = group_ops.group_expand([state.x, state.img_global] + [state.E_features[k] for k in keys], groups)
+        return EncoderState(out[0], dict(zip(keys, out[2:])), out[1])
+
+    def decode(self, ws, state, groups=None, **layer_kwargs):
+        """The rest of ``forward``: the co-modulated decoder on an ``EncoderState``.  With ``groups`` (int32 device tensor [B], values in [0, G)) the
+        state was encoded from G conditioning images while ``ws`` has B rows: sample b is decoded from image ``groups[b]``."""
+        _assert_shape(ws, [None, self.num_ws, self.w_dim])
+        ws_stack = ws
+        ws = ws.to(torch.float32).unbind(dim=1)
+        layers = [getattr(self, name) for name in self.layer_names]
+        skip_plan = self._skip_plan()
+        if groups is not None:
+            state = self._expand_state(state, groups, ws_stack.shape[0], layers, skip_plan, layer_kwargs.get('update_emas', False))
+        x, E_features, img_global = state.x, state.E_features, state.img_global
+        bank16 = self.compute_dtype in (torch.bfloat16, torch.float16) and x.is_cuda
         # Every layer's styles depend on the latents only: compute them up front, so that a layer running as the fused node
         # can fold the NEXT layer's style factor into its own output epilogue (no separate pass over the activations).
         fuse = not layer_kwargs.get('update_emas', False)
-        layers = [getattr(self, name) for name in self.layer_names]
         mods = None
         if fuse and all(layer.cond_mod for layer in layers):
             # every layer's styles = affine_l(cat(ws[:, 1 + l], img_global)) from ONE launch (and three backward) instead of 15 cat +
@@ -548,12 +603,7 @@ class SynthesisNetwork(torch.nn.Module):
         prescaled = False
         links = [fused_layer.LayerLink() for _ in layers]        # links[i]: between layer i and layer i + 1 (its only consumer)
         for idx, (layer, w) in enumerate(zip(layers, ws[1:])):
-            nxt = min(idx + 1, len(self.layer_names) - 1)
-            if (self.sizes[idx] != self.sizes[nxt]) and self.sizes[idx] != self.sizes[0]:
-                include_skip = self.skip_connects[res_idx]
-                res_idx += 1
-            else:
-                include_skip = False
+            include_skip = skip_plan[idx]
             next_scale = mods[idx + 1][1] if (fuse and idx + 1 < len(layers) and layer.fusable(x)) else None
             x = layer(x, w, img_global, E_features, include_skip, _mod=mods[idx], _prescaled=prescaled, _next_scale=next_scale,
                       _packed=dec_packs[idx], _link_in=(links[idx - 1] if prescaled else None),
@@ -585,6 +635,11 @@ class Stylegan3Generator(torch.nn.Module):
         self.num_ws = self.synthesis.num_ws
         self.mapping = MappingNetwork(z_dim=z_dim, c_dim=c_dim, w_dim=w_dim, num_ws=self.num_ws, **mapping_kwargs)
 
-    def forward(self, z, c, cond_img, ref_img=None, truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs):
+    def forward(self, z, c, cond_img, ref_img=None, truncation_psi=1, truncation_cutoff=None, update_emas=False, cond_groups=None,
+                **synthesis_kwargs):
+        """``cond_groups`` (inference only; int32 device tensor [B], values in [0, G)): ``cond_img`` is [G, ...] while ``z`` and ``c`` are
+        [B, ...]; the encoder runs once per conditioning image and sample b is decoded from image ``cond_groups[b]``."""
         ws = self.mapping(z, c, img_in=ref_img, truncation_psi=truncation_psi, truncation_cutoff=truncation_cutoff, update_emas=update_emas)
-        return self.synthesis(ws, cond_img, update_emas=update_emas, **synthesis_kwargs)
+        if cond_groups is None:
+            return self.synthesis(ws, cond_img, update_emas=update_emas, **synthesis_kwargs)
+        return self.synthesis.decode(ws, self.synthesis.encode(cond_img), groups=cond_groups, update_emas=update_emas, **synthesis_kwargs)

@@ -67,6 +67,7 @@ class StyleGAN3GeneratorStep:
         self.style_mixing_prob = style_mixing_prob
         self.real_A = self.real_B = self.fake_B = None
         self.gen_z = self.gen_c = None
+        self.test_groups = self.test_leaders = None
         self.buckets = GradientBuckets(netG.parameters(), bucket_bytes=bucket_bytes, force=force_collectives, comm_dtype=comm_dtype) if distributed else None
         if self.buckets is not None:
             self.buckets.broadcast_parameters(netG)
@@ -86,13 +87,26 @@ class StyleGAN3GeneratorStep:
         dev = next(self.netG.parameters()).device
         self.real_A = real_A.to(dev)
         self.real_B = real_B.to(dev)
+        self.test_groups = self.test_leaders = None
         self.gen_z = torch.randn([real_A.shape[0], self.netG.z_dim], device=dev) if gen_z is None else gen_z.to(dev)
         self.gen_c = gen_c.to(dev) if gen_c is not None else torch.zeros([real_A.shape[0], self.netG.c_dim], device=dev)
 
-    def set_test_input(self, real_A, slice_idx):
+    def set_test_input(self, real_A, slice_idx, groups=None, leaders=None):
         """models/pix2pix_model.py:115-117 + models/comodgan_model.py:101-108: the test loader's item -- a fresh ``gen_z``, the label from
-        ``slice_idx`` [B, 1] (zeros for an unconditional generator); ``real_B`` is left as it is, as in the reference."""
+        ``slice_idx`` [B, 1] (zeros for an unconditional generator); ``real_B`` is left as it is, as in the reference.
+        ``groups`` (int32 [B], values in [0, G)) with ``leaders`` (int64 [G], the batch position of one member of each group) say which rows of
+        ``real_A`` are the same conditioning stack: ``forward_ema`` then encodes the G leaders only and decodes every sample from its group's
+        state.  ``real_A`` stays the full batch, and ``gen_z`` is drawn as without them."""
+        if (groups is None) != (leaders is None):
+            raise RuntimeError('set_test_input: groups and leaders come together')
         dev = next(self.netG.parameters()).device
+        if groups is not None:
+            if groups.dtype != torch.int32 or groups.ndim != 1 or groups.shape[0] != real_A.shape[0]:
+                raise RuntimeError(f'set_test_input: groups must be int32 [{real_A.shape[0]}], got {groups.dtype} {tuple(groups.shape)}')
+            if leaders.dtype != torch.int64 or leaders.ndim != 1 or not 1 <= leaders.shape[0] <= real_A.shape[0]:
+                raise RuntimeError(f'set_test_input: leaders must be int64 [G] with 1 <= G <= {real_A.shape[0]}, got {leaders.dtype} {tuple(leaders.shape)}')
+            groups, leaders = groups.to(dev), leaders.to(dev)
+        self.test_groups, self.test_leaders = groups, leaders
         self.real_A = real_A.to(dev)
         self.gen_z = torch.randn([real_A.shape[0], self.netG.z_dim], device=dev)
         self.gen_c = slice_idx.to(dev) if self.netG.c_dim > 0 else torch.zeros([real_A.shape[0], 1], device=dev)
@@ -114,6 +128,10 @@ class StyleGAN3GeneratorStep:
         """models/comodgan_model.py:114-116: the EMA generator, whole forward (mapping + synthesis), noise_mode='const'."""
         if self.netG_ema is None:
             raise RuntimeError('this step was built without the EMA generator (ema=True)')
+        if self.test_groups is not None:                     # the encoder once per group of equal conditioning stacks (set_test_input)
+            self.fake_B = self.netG_ema(z=self.gen_z, c=self.gen_c, cond_img=self.real_A.index_select(0, self.test_leaders), ref_img=self.real_B,
+                                        noise_mode='const', cond_groups=self.test_groups)
+            return
         self.fake_B = self.netG_ema(z=self.gen_z, c=self.gen_c, cond_img=self.real_A, ref_img=self.real_B, noise_mode='const')
 
     def test(self):

@@ -113,6 +113,37 @@ class DevicePredictor:
         return self.prediction_map / self.normalization_mask
 
 
+class GroupTables:
+    """Which samples of every batch of a plan share their conditioning stack ``A``.  With four-slice inputs the stack of target ``idx`` is a function
+    of ``idx // thickness`` alone (afcm_slice_assemble: ``idx_a = (idx / t) * t``), so that quotient names the group; ``thickness=None`` (one-slice
+    inputs): every sample is its own group.  Built on the host from the plan's z origins and uploaded ONCE per volume; ``batch(first)`` returns
+    device views: ``groups`` int32 [B], each sample's group numbered from 0 within its batch, and ``leaders`` int64 [G], the batch position of
+    the first member of each group.  ``encoder_batches``: G of every batch, for reports."""
+
+    def __init__(self, plan, batch_size, thickness, device):
+        z = plan.origins[:, 0].astype(np.int64)
+        keys = z // int(thickness) if thickness is not None else np.arange(len(plan), dtype=np.int64)
+        groups, leaders, self._spans, self.encoder_batches = [], [], {}, []
+        for first in range(0, len(plan), batch_size):
+            k = keys[first:first + batch_size]
+            _, lead, inverse = np.unique(k, return_index=True, return_inverse=True)
+            order = np.argsort(lead, kind='stable')                            # groups numbered by first appearance in the batch
+            rank = np.empty_like(order)
+            rank[order] = np.arange(len(order))
+            self._spans[first] = (len(k), sum(self.encoder_batches), len(lead))
+            groups.append(rank[inverse.reshape(-1)])
+            leaders.append(lead[order])
+            self.encoder_batches.append(len(lead))
+        flat = np.concatenate(groups + leaders).astype(np.int64)
+        table = torch.from_numpy(flat).to(device)                              # the one upload
+        self._groups = table[:len(plan)].to(torch.int32)
+        self._leaders = table[len(plan):]
+
+    def batch(self, first):
+        count, lead0, n_groups = self._spans[first]
+        return self._groups[first:first + count], self._leaders[lead0:lead0 + n_groups]
+
+
 def _input_head(real_A):
     """models/predictor.py:152-158: the input head is the target's own thick slice, channel 1 of a four-slice input (a view, no copy)."""
     return real_A[:, 1:2] if real_A.shape[1] > 1 else real_A
@@ -120,7 +151,7 @@ def _input_head(real_A):
 
 @torch.no_grad()
 def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4, patch_hw, batch_size, patch_halo=(0, 8, 8), heads=('prediction',),
-                   where='device', min_value=0., max_value=255., rescale=None):
+                   where='device', min_value=0., max_value=255., rescale=None, share_encoder=False):
     """One subject through the EMA generator: ``source`` (a mapping {internal path: array [D, Hs, Ws]} or an HDF5 file name) -> {head: [C, D, H, W]}
     with ``heads`` out of 'prediction' (``fake_B``) and 'input' (the thick slice each target falls into).  ``step`` needs
     ``set_test_input(real_A, slice_idx)``, ``test()``, ``real_A`` and ``fake_B`` [B, C, H, W] (``StyleGAN3GeneratorStep`` built with ``ema=True``).
@@ -129,9 +160,15 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     loop; ``where='host'`` returns CPU tensors, the same bits.  Both arms draw ``gen_z`` batch by batch in the same order.
     ``rescale=(q_lo, q_hi)``: the source is a raw scanner volume and goes through ``intensity.rescale_intensity`` with those percentiles first -- on
     the device after the upload (``where='device'``, still no host read) or through ``rescale_intensity_host`` -- so the loop sees a uint8 volume, the
-    same one in both arms.  None: the source is taken as it is."""
+    same one in both arms.  None: the source is taken as it is.
+    ``share_encoder=True`` (``where='device'`` only): with four-slice inputs the ``thickness`` consecutive targets of one thick slice carry the same
+    ``A`` bit for bit, so the step is told which rows of a batch are equal (``set_test_input(a, slice_idx, groups, leaders)``) and runs the
+    generator's encoder once per group instead of once per sample.  The batch partition does not change; a group that straddles a batch boundary
+    is encoded once in each batch.  With ``slice_num`` 1 or no thickness every sample is its own group."""
     if where not in ('device', 'host'):
         raise ValueError(f"where must be 'device' or 'host', got {where!r}")
+    if share_encoder and where != 'device':
+        raise ValueError("share_encoder=True needs where='device'")
     heads = tuple(heads)
     if not heads or any(h not in ('prediction', 'input') for h in heads):
         raise ValueError(f"heads are 'prediction' and 'input', got {heads!r}")
@@ -177,10 +214,14 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     volume_shape = (int(volume.shape[0]),) + patch_shape[1:]
     plan = PatchPlan(volume_shape, patch_indices(volume_shape, patch_shape, stride_shape))
     predictors = {}
+    shared = GroupTables(plan, batch_size, thickness if slice_num == 4 else None, device) if share_encoder else None
     for first in range(0, len(plan), batch_size):
         a, slice_idx = assemble_slices(volume, first, min(batch_size, len(plan) - first), patch_shape, thickness=thickness, slice_num=slice_num,
                                        min_value=min_value, max_value=max_value, stride_shape=stride_shape)
-        step.set_test_input(a, slice_idx)
+        if shared is None:
+            step.set_test_input(a, slice_idx)
+        else:
+            step.set_test_input(a, slice_idx, *shared.batch(first))
         step.test()
         for head in heads:
             t = step.fake_B if head == 'prediction' else _input_head(step.real_A)

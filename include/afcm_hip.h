@@ -717,6 +717,36 @@ int64_t afcm_rescale_workspace_bytes(int64_t n, int32_t src_dtype);
 int afcm_rescale_intensity(uint8_t* out, double* stats, void* workspace, const void* volume, int32_t src_dtype, int32_t depth, int32_t h, int32_t w,
                            int64_t src_stride_z, double q_lo, double q_hi, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * afcm_group_expand: whole per-sample blocks of several tensors repeated by a DEVICE index, in one launch -- the encoder state of G conditioning
+ * images handed to a decoder batch of `batch` samples (SynthesisNetwork.decode with `groups`).  For every row k of the table and every sample b
+ *   dst_k[b * block_bytes, + block_bytes) = src_k[groups[b] * block_bytes, + block_bytes)     byte for byte.
+ * A block is what lies between two samples of the tensor as allocated: C * H * pitch elements of a row-pitched tensor, padding included, so the
+ * output has the source's layout and finite padding wherever the source's producer left it finite.
+ * `table_dev` is a DEVICE array of n rows sorted by chunk0, as in afcm_ema_multi; a chunk is afcm_group_chunk_bytes() bytes of ONE block, so row k owns
+ * batch * ceil(block_bytes / chunk bytes) chunks starting at chunk0 (sample-major).  `table_host` is the host image of the same rows: the entry point
+ * checks it and sizes the grid from it, the kernel reads table_dev only.  `groups` (device, int32 [batch]) is read when the kernel RUNS; nothing is read
+ * back.  An index outside [0, groups_k) cannot be raised from the device: that sample reads nothing, and every element of its block in every output is
+ * NaN (afcm_batch_assemble's convention; kind says which NaN: AFCM_GROUP_2B stores 0x7FFF, a NaN in fp16 and in bf16, AFCM_GROUP_4B 0x7FC00000).
+ * 16 bytes per lane, four in flight, where the source block and the destination block start on 16-byte boundaries; element by element (kind bytes)
+ * otherwise and in the last block_bytes % 16 bytes.  Offsets are formed in 64 bits.  No atomics, no LDS, no allocation, no synchronise: capturable.
+ * AFCM_E_INVALID: a null table, groups, src or dst; n < 1; batch < 1; a row with groups < 1, a block size of 0 or not a multiple of kind, an unknown
+ * kind or a chunk0 that is not the running total of the rows before it; more than 2^31 - 1 workgroups.
+ * ---------------------------------------------------------------------------------------- */
+#define AFCM_GROUP_2B 2
+#define AFCM_GROUP_4B 4
+typedef struct afcm_group_entry {
+    void*       dst;          /* [batch] blocks */
+    const void* src;          /* [groups] blocks */
+    int64_t     block_bytes;
+    int64_t     chunk0;
+    int32_t     groups;       /* G of this tensor */
+    int32_t     kind;         /* AFCM_GROUP_2B / AFCM_GROUP_4B: the element size */
+} afcm_group_entry;
+int32_t afcm_group_chunk_bytes(void);
+int afcm_group_expand(const afcm_group_entry* table_dev, const afcm_group_entry* table_host, int32_t n, int32_t batch, const int32_t* groups,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
