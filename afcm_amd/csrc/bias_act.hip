@@ -70,9 +70,11 @@ __device__ __forceinline__ float act_eval(int G, float x, float yy, float xr, fl
     }
     // swish: derivatives from the saved input
     if (G == 0) return (x < -kExpRange) ? 0.f : x / (expf(-x) + 1.f);
-    const float e = expf(xr), d = e + 1.f;
-    if (G == 1) return (xr > 0.5f * kExpRange) ? x : x * e * (xr + d) / (d * d);
-    return (xr > 0.5f * kExpRange) ? 0.f : x * e * (xr * (2.f - d) + 2.f * d) / (d * d * d);
+    // Every factor stays at the scale of the result: s = e / d <= 1, and d * d <= 5.6e34 up to the cut at 40.  (The reference's
+    // order x * e * (xr + d) / (d * d) overflows for a loss-scaled x -- inf at xr = 40, x = 7000 -- and its d * d * d from xr = 29.6.)
+    const float e = expf(xr), d = e + 1.f, s = e / d;
+    if (G == 1) return (xr > 0.5f * kExpRange) ? x : x * s * ((xr + d) / d);
+    return (xr > 0.5f * kExpRange) ? 0.f : x * s * ((xr * (2.f - d) + 2.f * d) / (d * d));
 }
 
 template <int A>

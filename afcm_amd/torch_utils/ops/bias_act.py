@@ -76,7 +76,8 @@ class _SumPlanes(torch.autograd.Function):
 def _sum_except(t, dim):
     if t.ndim == 4 and dim == 1 and t.is_cuda and t.dtype in (torch.float32, torch.bfloat16, torch.float16) and t.numel() > 0:
         return _SumPlanes.apply(t)
-    return t.sum([i for i in range(t.ndim) if i != dim])
+    dims = [i for i in range(t.ndim) if i != dim]
+    return t.sum(dims) if dims else t.clone()       # 1-D x: nothing to reduce (an empty dim list would sum everything)
 
 
 class _BiasAct(torch.autograd.Function):
@@ -133,7 +134,10 @@ class _BiasActGrad(torch.autograd.Function):
 
 
 def bias_act(x, b=None, dim=1, act='linear', alpha=None, gain=None, clamp=None, impl='cuda'):
-    """Fused bias + activation.  Same signature and defaults as SG3OPS/bias_act.py:52."""
+    """Fused bias + activation.  Same signature and defaults as SG3OPS/bias_act.py:52.
+
+    Non-finite inputs (forward): the kernel's selections are IEEE selections, so NaN stays NaN except that relu gives 0 and a clamp
+    turns it into -clamp (relu: 0); +-inf go to the activation's limit times the gain, then into the clamp."""
     assert isinstance(x, torch.Tensor)
     assert impl in ['ref', 'cuda']
     # impl='ref' on a GPU tensor runs the same HIP kernel (one device implementation; the reference's 'ref' twin is the aten
@@ -148,4 +152,7 @@ def bias_act(x, b=None, dim=1, act='linear', alpha=None, gain=None, clamp=None, 
         assert isinstance(b, torch.Tensor) and b.ndim == 1
         assert 0 <= dim < x.ndim
         assert b.shape[0] == x.shape[dim]
-    return _BiasAct.apply(x, b, dim, act, alpha, gain, clamp)
+        b = b.contiguous()
+    # The copy of a non-contiguous x is made HERE, as a node of the graph: made inside _BiasAct.forward it is a tensor autograd does not
+    # know, and the second-order gradient that _BiasActGrad.backward returns for the saved x never reached the caller's x.
+    return _BiasAct.apply(x.contiguous(), b, dim, act, alpha, gain, clamp)
