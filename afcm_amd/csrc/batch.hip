@@ -2,8 +2,10 @@
 // rows of a DEVICE item table, over a pool that holds every volume of the training set.
 //   batch_assemble_kernel   A [count, k, h, w], B [count, 1, h, w] and the labels in one launch; a thread produces a run of RUN consecutive x of one
 //                           output row (item, plane and row decoding, the table reads and the guards happen once per run) and stores it at once
+//   batch_augment_kernel    the same launch with the item's flips, quarter turns and nearest-neighbour rotation (data/augment/transforms.py:25-112)
+//                           from a DEVICE table of float64 parameter rows: a gather through the same crop / pad / normalise read
 //   cursor_advance_kernel   cursor[0] += by, one thread: the table position of a captured graph moves on the device
-// The tables cannot be checked on the host, so the kernel checks every row before it reads the pool; an invalid item reads nothing and comes out as
+// The tables cannot be checked on the host, so the kernels check every row before they read the pool; an invalid item reads nothing and comes out as
 // NaN.  No LDS, no atomics; every pool offset is 64-bit.  See include/afcm_hip.h for the semantics kept.
 #include "common.h"
 #include "volume_common.h"
@@ -16,6 +18,35 @@ __device__ __forceinline__ bool descriptor_ok(long long off, long long depth, lo
     const long long plane = hs * ws;
     if (depth > pool_elems / plane) return false;
     return off >= 0 && off <= pool_elems - depth * plane;
+}
+
+// Sample i of a launch for batch_augment_kernel: batch_assemble_kernel's own row and descriptor checks, statement for statement (that kernel keeps
+// them in its body: routed through this function its instances compile to a different instruction order, and they are held to the one they have)
+struct batch_item {
+    bool valid;
+    long long row, off_a, off_b, depth, hs, ws;
+    int idx, t;
+};
+__device__ __forceinline__ batch_item item_of(int i, long long pool_elems, const long long* __restrict__ vols, int n_vols, const int* __restrict__ items,
+                                              int n_items, const long long* __restrict__ cursor, int first, int k) {
+    const long long c0 = cursor != nullptr ? cursor[0] : 0;
+    bool valid = c0 >= 0 && c0 < n_items;
+    const long long row = valid ? c0 + first + i : 0;
+    valid = valid && row < n_items;
+    int va = 0, vb = 0, idx = 0, t = 1;
+    if (valid) {
+        va = items[row * 4 + 0], vb = items[row * 4 + 1], idx = items[row * 4 + 2], t = items[row * 4 + 3];
+        valid = va >= 0 && va < n_vols && vb >= 0 && vb < n_vols && t != 0 && (k == 1 || t >= 1);
+    }
+    long long off_a = 0, off_b = 0, depth = 1, hs = 1, ws = 1;
+    if (valid) {
+        const long long* da = vols + (long long)va * 4;
+        const long long* db = vols + (long long)vb * 4;
+        off_a = da[0], depth = da[1], hs = da[2], ws = da[3], off_b = db[0];
+        valid = descriptor_ok(off_a, depth, hs, ws, pool_elems) && descriptor_ok(off_b, db[1], db[2], db[3], pool_elems) && db[1] == depth &&
+                db[2] == hs && db[3] == ws && idx >= 0 && idx < depth;
+    }
+    return {valid, row, off_a, off_b, depth, hs, ws, idx, valid ? t : 1};
 }
 
 template <typename S, typename T, int RUN>
@@ -64,16 +95,99 @@ __global__ __launch_bounds__(VOL_THREADS) void batch_assemble_kernel(T* __restri
     store_run<T, RUN>((plane < k ? a + (((long long)i * k + plane) * h + y) * w : b + ((long long)i * h + y) * w) + x0, v, x0, w);
 }
 
+// scipy.ndimage's 'reflect' for an integer coordinate: (d c b a | a b c d | d c b a), any number of periods.  2n and |i| fit an int (the entry point
+// bounds h + w, the kernel the offsets)
+__device__ __forceinline__ int reflect_index(int i, int n) {
+    i = i < 0 ? -i - 1 : i;                                                    // the pattern is even about -1/2
+    if (i < n) return i;                                                       // inside, or one mirror below 0: nearly every pixel of a rotation
+    const unsigned period = 2u * (unsigned)n;
+    const unsigned m = (unsigned)i < period ? (unsigned)i : (unsigned)i % period;     // the division only past the first period
+    return (int)(m < (unsigned)n ? m : period - 1u - m);
+}
+
+// One parameter row of the augment table (flip_h, flip_w, k, angle, c, s, off_y, off_x): the output pixel's source in the item plane, the chain of
+// transforms.py walked backwards -- RandomRotate (nearest, reflect), RandomRotate90, RandomFlip
+struct augment_row {
+    bool valid, identity, flip_h, flip_w;
+    int quarter;
+    double c, s, off_y, off_x;
+    __device__ __forceinline__ void source(double yc, double ys, int x, int h, int w, int& sy, int& sx) const {
+        const double iy = (yc + (double)x * s) + off_y;                        // yc = y * c, ys = y * (-s): once per run
+        const double ix = (ys + (double)x * c) + off_x;
+        const int ry = reflect_index((int)floor(iy + 0.5), h), rx = reflect_index((int)floor(ix + 0.5), w);
+        int py = ry, px = rx;                                                  // numpy.rot90(p1, quarter)[ry][rx] = p1[py][px]; h == w for odd turns
+        if (quarter == 1) py = rx, px = w - 1 - ry;
+        if (quarter == 2) py = h - 1 - ry, px = w - 1 - rx;
+        if (quarter == 3) py = h - 1 - rx, px = ry;
+        sy = flip_h ? h - 1 - py : py;
+        sx = flip_w ? w - 1 - px : px;
+    }
+};
+__device__ __forceinline__ augment_row augment_row_of(const double* __restrict__ p, int h, int w) {
+    const double fh = p[0], fw = p[1], q = p[2], c = p[4], s = p[5], oy = p[6], ox = p[7];
+    const double reach = (double)h + (double)w;
+    // every comparison is false for a NaN
+    const bool valid = (fh == 0.0 || fh == 1.0) && (fw == 0.0 || fw == 1.0) && (q == 0.0 || q == 2.0 || ((q == 1.0 || q == 3.0) && h == w)) &&
+                       fabs(c) <= 1.0 && fabs(s) <= 1.0 && fabs(oy) <= reach && fabs(ox) <= reach;
+    const bool identity = fh == 0.0 && fw == 0.0 && q == 0.0 && c == 1.0 && s == 0.0 && oy == 0.0 && ox == 0.0;
+    return {valid, identity, fh == 1.0, fw == 1.0, valid ? (int)q : 0, c, s, oy, ox};
+}
+
+template <typename S, typename T, int RUN>
+__global__ __launch_bounds__(VOL_THREADS) void batch_augment_kernel(T* __restrict__ a, T* __restrict__ b, float* __restrict__ slice_idx,
+                                                                    const S* __restrict__ pool, long long pool_elems,
+                                                                    const long long* __restrict__ vols, int n_vols, const int* __restrict__ items,
+                                                                    int n_items, const double* __restrict__ augment,
+                                                                    const long long* __restrict__ cursor, int first, int k, int h, int w, int runs,
+                                                                    long long total, double lo, double range) {
+    const long long e = (long long)blockIdx.x * VOL_THREADS + threadIdx.x;
+    if (e >= total) return;
+    const int x0 = (int)(e % runs) * RUN;
+    long long r = e / runs;
+    const int y = (int)(r % h);
+    r /= h;
+    const int plane = (int)(r % (k + 1));                                      // plane k: the target B
+    const int i = (int)(r / (k + 1));
+
+    const batch_item it = item_of(i, pool_elems, vols, n_vols, items, n_items, cursor, first, k);
+    augment_row g = {false, false, false, false, 0, 1.0, 0.0, 0.0, 0.0};
+    if (it.valid) g = augment_row_of(augment + it.row * 8, h, w);              // the item row's own r: inside [0, n_items)
+    const bool valid = it.valid && g.valid;
+    const thick_slice at = thick_slice_of(it.idx, it.t, plane < k ? k : 1, plane);
+    if (plane == 0 && y == 0 && x0 == 0) slice_idx[i] = valid ? at.label() : __builtin_nanf("");
+
+    const S* __restrict__ volume = pool + (plane < k ? it.off_a : it.off_b);
+    float v[RUN];
+    if (!valid) {
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) v[j] = __builtin_nanf("");
+    } else if (g.identity || at.pos < 0 || at.pos > it.depth - 1) {            // the contiguous read; a plane outside the volume is a constant
+        assembled_run<S, RUN>(v, volume, it.depth, it.hs, it.ws, it.hs * it.ws, at.pos, y, x0, h, w, lo, range);
+    } else {
+        const double yc = (double)y * g.c, ys = (double)y * (-g.s);
+        const long long oy = crop_offset(it.hs, h), ox = crop_offset(it.ws, w), slice = at.pos * (it.hs * it.ws);
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) {
+            v[j] = 0.0f;
+            if (x0 + j < w) {                                                  // elements past the row are never stored and read nothing
+                int sy, sx;
+                g.source(yc, ys, x0 + j, h, w, sy, sx);
+                const long long yv = sy + oy, xv = sx + ox;                    // the item plane's pixel in the volume's slice, or in the padding
+                v[j] = normalised<S>(volume, slice + yv * it.ws + xv, yv >= 0 && yv < it.hs && xv >= 0 && xv < it.ws, lo, range);
+            }
+        }
+    }
+    store_run<T, RUN>((plane < k ? a + (((long long)i * k + plane) * h + y) * w : b + ((long long)i * h + y) * w) + x0, v, x0, w);
+}
+
 __global__ void cursor_advance_kernel(long long* __restrict__ cursor, long long by) {
     if (blockIdx.x == 0 && threadIdx.x == 0) cursor[0] += by;
 }
 
-}  // namespace afcm
-
-extern "C" int afcm_batch_assemble(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
-                                   int32_t n_vols, const int32_t* items, int32_t n_items, const int64_t* cursor, int32_t first, int32_t count, int32_t k,
-                                   int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream) {
-    using namespace afcm;
+// both entry points: the checks, the (source, output) dispatch and the launch; augment null: the plain kernel
+static int launch_batch(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols, int32_t n_vols,
+                        const int32_t* items, int32_t n_items, const double* augment, const int64_t* cursor, int32_t first, int32_t count, int32_t k,
+                        int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream) {
     AFCM_REQUIRE(a != nullptr && b != nullptr && slice_idx != nullptr && pool != nullptr && vols != nullptr && items != nullptr,
                  "batch_assemble: null output, label, pool or table");
     AFCM_REQUIRE(src_dtype >= AFCM_SRC_U8 && src_dtype <= AFCM_SRC_F64, "batch_assemble: source dtype %d is not AFCM_SRC_U8 / I16 / F32 / F64", src_dtype);
@@ -84,6 +198,8 @@ extern "C" int afcm_batch_assemble(void* a, void* b, float* slice_idx, const voi
     AFCM_REQUIRE(first >= 0, "batch_assemble: first row %d is negative", first);
     AFCM_REQUIRE(k == 1 || k == 4, "batch_assemble: slice number %d is not 1 or 4", k);
     AFCM_REQUIRE(max_value > min_value, "batch_assemble: max_value %g is not above min_value %g", max_value, min_value);
+    AFCM_REQUIRE(augment == nullptr || (long long)h + w <= (1LL << 28),
+                 "batch_assemble_aug: a patch of [%d, %d]: h + w above 2^28 takes the rotated coordinates out of the int32 range", h, w);
     const double range = max_value - min_value;
     return dispatch_src_out(src_dtype, out_dtype, [&](auto s_tag, auto t_tag) -> int {
         using S = typename decltype(s_tag)::type;
@@ -94,11 +210,35 @@ extern "C" int afcm_batch_assemble(void* a, void* b, float* slice_idx, const voi
         AFCM_REQUIRE(threads / VOL_THREADS < 2147483647.0, "batch_assemble: %.0f workgroups exceed the grid", threads / VOL_THREADS);
         const long long total = (long long)count * (k + 1) * h * runs;
         const long long groups = (total + VOL_THREADS - 1) / VOL_THREADS;
-        hipLaunchKernelGGL((batch_assemble_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, (hipStream_t)stream, (T*)a, (T*)b, slice_idx,
-                           (const S*)pool, (long long)pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items, (const long long*)cursor,
-                           first, k, h, w, runs, total, min_value, range);
+        if (augment == nullptr)
+            hipLaunchKernelGGL((batch_assemble_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, (hipStream_t)stream, (T*)a, (T*)b,
+                               slice_idx, (const S*)pool, (long long)pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items,
+                               (const long long*)cursor, first, k, h, w, runs, total, min_value, range);
+        else
+            hipLaunchKernelGGL((batch_augment_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, (hipStream_t)stream, (T*)a, (T*)b,
+                               slice_idx, (const S*)pool, (long long)pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items, augment,
+                               (const long long*)cursor, first, k, h, w, runs, total, min_value, range);
         return hip_status(hipGetLastError());
     });
+}
+
+}  // namespace afcm
+
+extern "C" int afcm_batch_assemble(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                                   int32_t n_vols, const int32_t* items, int32_t n_items, const int64_t* cursor, int32_t first, int32_t count, int32_t k,
+                                   int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream) {
+    return afcm::launch_batch(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, nullptr, cursor, first, count, k, h, w,
+                              out_dtype, min_value, max_value, stream);
+}
+
+extern "C" int afcm_batch_assemble_aug(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                                       int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment, const int64_t* cursor, int32_t first,
+                                       int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value,
+                                       void* stream) {
+    using namespace afcm;
+    AFCM_REQUIRE(augment != nullptr, "batch_assemble_aug: null augment table");
+    return launch_batch(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, augment, cursor, first, count, k, h, w, out_dtype,
+                        min_value, max_value, stream);
 }
 
 extern "C" int afcm_cursor_advance(int64_t* cursor, int64_t by, void* stream) {

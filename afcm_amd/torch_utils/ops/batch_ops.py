@@ -1,5 +1,5 @@
-"""assemble_batch / advance_cursor: a training batch from a device-resident pool of volumes (C ABI ``afcm_batch_assemble`` / ``afcm_cursor_advance``,
-include/afcm_hip.h; kernels in csrc/batch.hip).
+"""assemble_batch / advance_cursor: a training batch from a device-resident pool of volumes (C ABI ``afcm_batch_assemble`` /
+``afcm_batch_assemble_aug`` / ``afcm_cursor_advance``, include/afcm_hip.h; kernels in csrc/batch.hip).
 
 ``assemble_batch`` is ``SliceDataset(phase='train').__getitem__`` for ``count`` rows of a device-side item table -- ``A``, ``B`` and ``slice_idx`` in
 one launch, bit-identical to the stacked host items.  The tables live on the device, so the kernel checks every row itself: an invalid row comes out
@@ -16,13 +16,17 @@ def _table(t, what, dtype, cols):
         raise RuntimeError(f'assemble_batch: {what} must be a contiguous {dtype} [n, {cols}] with n >= 1, got {got}')
 
 
-def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_value=0., max_value=255., dtype=torch.float32, out=None, cursor=None):
+def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_value=0., max_value=255., dtype=torch.float32, out=None, cursor=None,
+                   augment=None):
     """``pool``: 1-D DEVICE tensor (uint8 / int16 / float32 / float64) holding every volume; ``vols``: DEVICE int64 [n_vols, 4] (element offset into the
     pool, depth, hs, ws); ``items``: DEVICE int32 [n_items, 4] (vol_a, vol_b, idx, thickness; thickness -1: none, ``slice_num`` 1 only).  Sample ``i`` is
     table row ``(cursor[0] if cursor is not None else 0) + first + i``.  Returns ``A [count, slice_num, H, W]``, ``B [count, 1, H, W]`` of ``dtype``
     and ``slice_idx [count, 1]`` float32 with ``patch_hw = (H, W)``: per volume centre crop / constant pad, the thick slices at -1, 0, +1, +2
     ``thickness`` around the target's own (``slice_num`` 4) or the slice itself (1), ``data.normalize``.  ``out=(A, B, slice_idx)`` writes into existing
-    tensors (a captured graph needs stable addresses); ``cursor``: DEVICE int64 scalar tensor, see ``advance_cursor``."""
+    tensors (a captured graph needs stable addresses); ``cursor``: DEVICE int64 scalar tensor, see ``advance_cursor``.
+    ``augment``: DEVICE float64 [n_items, 8], one parameter row ``(flip_h, flip_w, k, angle, c, s, off_y, off_x)`` beside every item row
+    (``afcm_amd.augment.augment_rows``): the item's planes flipped, turned by quarters and rotated as the reference's ``RandomFlip``,
+    ``RandomRotate90`` and ``RandomRotate`` do (``afcm_batch_assemble_aug``); an invalid parameter row is a NaN item as an invalid item row is."""
     h, w = (int(v) for v in patch_hw)
     first, count = int(first), int(count)
     _lib.require_slice_num(slice_num, 'assemble_batch')
@@ -31,6 +35,10 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     code = _lib.source_code(pool.dtype, 'assemble_batch')
     _table(vols, 'the volume table', torch.int64, 4)
     _table(items, 'the item table', torch.int32, 4)
+    if augment is not None:
+        _table(augment, 'the augment table', torch.float64, 8)
+        if augment.shape[0] != items.shape[0]:
+            raise RuntimeError(f'assemble_batch: the augment table has {augment.shape[0]} rows, the item table {items.shape[0]}: one parameter row per item row')
     _lib.require_out_dtype(dtype, 'assemble_batch')
     if count < 1 or first < 0 or h < 1 or w < 1:
         raise RuntimeError(f'assemble_batch: {count} items from row {first} at [{h}, {w}]: count and the patch must be positive, first not negative')
@@ -50,13 +58,17 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
             if tuple(t.shape) != shape or t.dtype != want or not t.is_contiguous():
                 raise RuntimeError(f'assemble_batch: out {name} must be a contiguous {want} {shape}, got {t.dtype} {tuple(t.shape)} '
                                    f'with strides {tuple(t.stride())}')
-    tensors = (pool, vols, items, a, b, slice_idx) + (() if cursor is None else (cursor,))
+    tensors = (pool, vols, items, a, b, slice_idx) + (() if cursor is None else (cursor,)) + (() if augment is None else (augment,))
     _lib.require_gpu(*tensors)
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f'assemble_batch: pool, tables, outputs and cursor must be on one device, got {sorted({str(t.device) for t in tensors})}')
-    rc = _lib.load().afcm_batch_assemble(a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), code,
-                                         vols.data_ptr(), int(vols.shape[0]), items.data_ptr(), int(items.shape[0]), _lib.ptr(cursor), first, count,
-                                         slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
+    head = (a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), code, vols.data_ptr(), int(vols.shape[0]), items.data_ptr(),
+            int(items.shape[0]))
+    tail = (_lib.ptr(cursor), first, count, slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
+    if augment is None:
+        rc = _lib.load().afcm_batch_assemble(*head, *tail)
+    else:
+        rc = _lib.load().afcm_batch_assemble_aug(*head, augment.data_ptr(), *tail)
     _lib.launched(rc, 'batch_assemble')
     return a, b, slice_idx
 

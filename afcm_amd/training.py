@@ -5,12 +5,15 @@
 ``(vol_a, vol_b, idx, thickness)`` rows; ``afcm_batch_assemble`` (torch_utils/ops/batch_ops.py) turns ``count`` rows of that table into the batch
 ``SliceDataset(phase='train')`` items would stack to, bit for bit.  ``train_epoch`` is the loop ``for data in dataset: set_input; optimize_parameters;
 EMA`` with the batches from the device (or, ``where='host'``, from ``SliceDataset``: the comparison arm).  ``TrainingGraph`` is that loop's body as one
-replayed graph that reads its batch through a device-side cursor: no host data work between steps.
+replayed graph that reads its batch through a device-side cursor: no host data work between steps.  With ``DeviceSliceSet(augment=AugmentConfig(...))``
+a float64 table of parameter rows (afcm_amd/augment.py) travels beside the item table and every batch comes out of ``afcm_batch_assemble_aug``
+flipped, turned and rotated as the reference's training transforms do it, inside the same launch.
 """
 import numpy as np
 import torch
 
 from . import _lib
+from .augment import AugmentConfig, apply_host, augment_rows, checked_rows, identity_rows
 from .data import SliceDataset, open_volumes
 from .intensity import rescale_intensity_host
 from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch
@@ -27,10 +30,13 @@ class DeviceSliceSet:
     ``device=None`` builds the host-side tables only (``epoch_items`` and ``host_batch`` work, nothing is uploaded).
     ``rescale=(q_lo, q_hi)``: the sources are raw scanner volumes; each is uploaded as it is and passed through ``rescale_intensity`` with those
     percentiles into a uint8 pool, volume by volume, so the subjects' raw dtypes may differ; ``host_batch`` rescales with
-    ``rescale_intensity_host``, the same bits.  None: the volumes are pooled as they are."""
+    ``rescale_intensity_host``, the same bits.  None: the volumes are pooled as they are.
+    ``augment``: an ``AugmentConfig`` (afcm_amd/augment.py; 'train' only) -- the set keeps a float64 [len(self), 8] device table of parameter rows
+    beside the item table, ``epoch_augment`` draws an epoch's rows, ``load_epoch`` uploads them and every batch goes through
+    ``afcm_batch_assemble_aug``.  None: no table, ``afcm_batch_assemble``."""
 
     def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
-                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None):
+                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None):
         if phase not in ('train', 'val', 'test'):
             raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
         if cat_inputs:
@@ -39,6 +45,13 @@ class DeviceSliceSet:
         if len(patch_shape) != 3 or patch_shape[0] != 1 or min(patch_shape) < 1:
             raise RuntimeError(f'DeviceSliceSet: patch_shape must be (1, H, W), got {patch_shape}')
         _lib.require_slice_num(slice_num, 'DeviceSliceSet')
+        if augment is not None:
+            if not isinstance(augment, AugmentConfig):
+                raise RuntimeError(f'DeviceSliceSet: augment must be an AugmentConfig or None, got {type(augment).__name__}')
+            if phase != 'train':
+                raise RuntimeError(f"DeviceSliceSet: augmentation belongs to the 'train' phase, got phase {phase!r}")
+            augment.check_patch(patch_shape[1:], 'DeviceSliceSet')
+        self.augment = augment
         self.phase, self.patch_shape, self.rand_output, self.slice_num = phase, patch_shape, bool(rand_output), int(slice_num)
         self.raw_internal_path_in, self.raw_internal_path_out = list(raw_internal_path_in), list(raw_internal_path_out)
         self.thickness = [int(t) for t in thickness]
@@ -80,7 +93,7 @@ class DeviceSliceSet:
         self._idx = np.concatenate([np.arange(d, dtype=np.int64) for d in self.depths])
         self._host_sets, self._host_rescaled = {}, {}
         self.device = None if device is None else torch.device(device)
-        self.pool = self.vols = self.items = self.cursor = None
+        self.pool = self.vols = self.items = self.cursor = self.augment_table = None
         self.rows = self.position = 0
         if self.device is not None:
             if self.device.type != 'cuda':
@@ -98,6 +111,8 @@ class DeviceSliceSet:
             # persistent (a captured graph holds their addresses): the epoch's table, refreshed in place, and the row a graph's next batch starts at
             self.items = torch.full((len(self), 4), -1, dtype=torch.int32, device=self.device)
             self.cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+            if self.augment is not None:                                                 # persistent as the item table is: row r belongs to item row r
+                self.augment_table = torch.from_numpy(identity_rows(len(self))).to(self.device)
 
     def __len__(self):
         return int(self._idx.shape[0])
@@ -133,14 +148,36 @@ class DeviceSliceSet:
             raise RuntimeError(f'DeviceSliceSet: an item table is int32 [n, 4] with n >= 1, got {items.dtype} {items.shape}')
         return items
 
-    def load_epoch(self, items):
-        """Uploads the table into the persistent device table (rows past it are marked invalid) and puts the cursor back to row 0."""
+    def epoch_augment(self, seed_or_generator=None, rows=None):
+        """The float64 [rows, 8] parameter table of one epoch (``rows``: ``len(self)`` when None), drawn by ``augment.augment_rows`` from the
+        set's ``AugmentConfig``; call it after ``epoch_items`` on the same generator, as ``train_epochs`` does."""
+        if self.augment is None:
+            raise RuntimeError('DeviceSliceSet.epoch_augment: this set was built without augment=AugmentConfig(...)')
+        rng = seed_or_generator if isinstance(seed_or_generator, np.random.Generator) else np.random.default_rng(seed_or_generator)
+        return augment_rows(self.augment, len(self) if rows is None else rows, self.patch_shape[1:], rng)
+
+    def _checked_augment(self, augment, n, what):
+        """The parameter table that goes with an item table of ``n`` rows: ``augment`` checked, identity rows for None, None for a set without
+        augmentation (which refuses a table)."""
+        if self.augment is None:
+            if augment is not None:
+                raise RuntimeError(f'DeviceSliceSet.{what}: an augment table for a set built without augment=AugmentConfig(...)')
+            return None
+        return identity_rows(n) if augment is None else checked_rows(augment, n, f'DeviceSliceSet.{what}')
+
+    def load_epoch(self, items, augment=None):
+        """Uploads the table into the persistent device table (rows past it are marked invalid) and puts the cursor back to row 0.  A set built
+        with ``augment`` takes the epoch's parameter rows (``epoch_augment``) the same way, identity rows when none are given."""
         self._need_device('load_epoch')
         items = self._checked_items(items)
         if items.shape[0] > self.items.shape[0]:
             raise RuntimeError(f'DeviceSliceSet.load_epoch: {items.shape[0]} rows do not fit the device table of {self.items.shape[0]} (one per slice)')
+        augment = self._checked_augment(augment, items.shape[0], 'load_epoch')
         self.items[:items.shape[0]].copy_(torch.from_numpy(items), non_blocking=False)
         self.items[items.shape[0]:].fill_(-1)
+        if augment is not None:
+            self.augment_table[:items.shape[0]].copy_(torch.from_numpy(augment), non_blocking=False)
+            self.augment_table[items.shape[0]:].copy_(torch.from_numpy(identity_rows(len(self) - items.shape[0])))
         self.rows = int(items.shape[0])
         self.rewind()
 
@@ -160,7 +197,7 @@ class DeviceSliceSet:
         if not use_cursor and (count < 1 or first < 0 or first + count > self.rows):
             raise RuntimeError(f'DeviceSliceSet.batch: rows [{first}, {first + count}) are not inside the loaded epoch of {self.rows} (load_epoch first)')
         return assemble_batch(self.pool, self.vols, self.items, first, count, self.patch_shape[1:], slice_num=self.slice_num, min_value=self.min_value,
-                              max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None)
+                              max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None, augment=self.augment_table)
 
     def batches(self, batch_size, drop_last=False, dtype=torch.float32):
         """The loaded epoch batch by batch; the last batch is partial unless ``drop_last``, as the reference's loader leaves it."""
@@ -181,13 +218,15 @@ class DeviceSliceSet:
             self._host_rescaled[subject] = {p: rescale_intensity_host(v, self.rescale)[0] for p, v in self.volumes[subject].items()}
         return self._host_rescaled[subject]
 
-    def host_batch(self, items, first, count, device=None):
+    def host_batch(self, items, first, count, device=None, augment=None):
         """The same batch through ``SliceDataset(phase='train', thickness=[t])`` items, stacked and uploaded: the comparison arm of tests and
-        benchmark.  A row the kernel would refuse raises here."""
+        benchmark.  ``augment``: the parameter table that goes with ``items`` (a set built with ``augment`` only); ``augment.apply_host`` applies
+        row ``first + j`` to ``A`` and ``B`` of item ``first + j``.  A row the kernel would refuse raises here."""
         items = self._checked_items(items)
+        augment = None if augment is None else self._checked_augment(augment, items.shape[0], 'host_batch')
         m = len(self.paths)
         a, b, c = [], [], []
-        for vol_a, vol_b, idx, t in items[first:first + count].tolist():
+        for j, (vol_a, vol_b, idx, t) in enumerate(items[first:first + count].tolist()):
             subject, column_b = divmod(vol_b, m)
             if not (0 <= vol_b < m * len(self.volumes)) or vol_a != subject * m + self.paths.index(self.raw_internal_path_in[0]):
                 raise RuntimeError(f'DeviceSliceSet.host_batch: row ({vol_a}, {vol_b}, {idx}, {t}) does not pair the input and an output of one subject')
@@ -201,6 +240,8 @@ class DeviceSliceSet:
             if not 0 <= idx < len(ds):
                 raise RuntimeError(f'DeviceSliceSet.host_batch: slice {idx} of a subject of {len(ds)}')
             item = ds[idx]
+            if augment is not None:
+                item['A'], item['B'] = apply_host(item['A'], augment[first + j]), apply_host(item['B'], augment[first + j])
             a.append(item['A'])
             b.append(item['B'])
             c.append(torch.from_numpy(item['slice_idx']))
@@ -226,13 +267,15 @@ def _fed_step(step, schedule, batch_size, batch, gen_z, cur_nimg=None):
         step.update_ema()
 
 
-def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None):
+def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None, augment=None):
     """The inner loop of the reference's train.py:45-77 over the epoch table ``items`` (``DeviceSliceSet.epoch_items``): per batch
     ``total_iters += batch_size``, ``step.set_input(A, B, gen_c=slice_idx)``, ``step.optimize_parameters(cur_nimg=total_iters)`` and, when the step
     has an EMA copy and ``ema_kimgs`` is given, ``step.update_ema(batch_size, total_iters, ema_kimgs, ramp)``.  The last batch is partial, as the
     reference's loader leaves it.  ``where='device'``: the batches come from ``afcm_batch_assemble``, nothing is read back from the device;
     ``where='host'``: from ``SliceDataset`` items (``DeviceSliceSet.host_batch``), the same bits.  Both arms draw ``gen_z`` in the same order
-    (``gen_z``: a fixed [batch_size, z_dim] tensor instead of a draw per batch).  Works with ``StyleGAN3GeneratorStep`` and ``StyleGAN3Step`` alike.
+    (``gen_z``: a fixed [batch_size, z_dim] tensor instead of a draw per batch).  ``augment``: the epoch's parameter table
+    (``DeviceSliceSet.epoch_augment``) for a set built with ``augment``; both arms apply it.  Works with ``StyleGAN3GeneratorStep`` and
+    ``StyleGAN3Step`` alike.
     Returns the new ``total_iters``."""
     if where not in ('device', 'host'):
         raise ValueError(f"where must be 'device' or 'host', got {where!r}")
@@ -242,12 +285,13 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     items = dataset._checked_items(items)
     n = int(items.shape[0])
     device = next(step.netG.parameters()).device
+    augment = dataset._checked_augment(augment, n, 'train_epoch')
     if where == 'device':
-        dataset.load_epoch(items)
+        dataset.load_epoch(items, augment)
     schedule = getattr(step, 'schedule', None) if where == 'device' else None
     for first in range(0, n, batch_size):
         count = min(batch_size, n - first)
-        batch = (lambda: dataset.batch(first, count)) if where == 'device' else (lambda: dataset.host_batch(items, first, count, device=device))
+        batch = (lambda: dataset.batch(first, count)) if where == 'device' else (lambda: dataset.host_batch(items, first, count, device=device, augment=augment))
         total_iters += batch_size
         _fed_step(step, schedule, batch_size, batch, None if gen_z is None else gen_z[:count], cur_nimg=total_iters)
         if schedule is None and ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
@@ -269,7 +313,8 @@ class TrainingGraph:
     and the schedule an ``ema_kimgs``, ends with ``step.update_ema()``; sigma, beta and the learning rates are read from the schedule block at every
     replay, and the warm-up leaves the block as it found it.  ``undo_warmup=True`` puts the networks' parameters and buffers and the optimizers' state
     back as well (in place: the graph keeps pointing at them), so that the warm-up's real steps leave no trace; the default keeps them, as
-    ``capture_step`` does.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None."""
+    ``capture_step`` does.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None.  A dataset built with ``augment``
+    is captured with ``afcm_batch_assemble_aug``: the parameter table is persistent as the item table is, and the cursor moves through both."""
 
     def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None, undo_warmup=False):
         require_capturable(step, 'TrainingGraph')
@@ -319,8 +364,8 @@ class TrainingGraph:
 
         self.graph = capture_graph(lambda: _fed_step(step, schedule, batch_size, cursor_batch, self.gen_z), warmup, next_rows, leave_no_trace)
 
-    def load_epoch(self, items):
-        self.dataset.load_epoch(items)
+    def load_epoch(self, items, augment=None):
+        self.dataset.load_epoch(items, augment)
 
     def rewind(self):
         self.dataset.rewind()
@@ -338,7 +383,8 @@ class TrainingGraph:
 def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True, on_epoch=None, gen_z=None):
     """The outer loop of the reference's train.py:38-45 for a step built with a ``DeviceSchedule``.  ``epochs``: an iterable of epoch numbers
     (``range(epoch_count, n_epochs + n_epochs_decay + 1)``).  Per epoch: ``step.set_lr(lr_schedule.lr_at(k))`` for G and D, k = 1 for the first
-    (``update_learning_rate()`` at the top of every epoch); ``dataset.epoch_items(rng)`` and ``load_epoch``; then replays of ONE ``TrainingGraph``
+    (``update_learning_rate()`` at the top of every epoch); ``dataset.epoch_items(rng)``, for a set built with ``augment`` ``epoch_augment(rng)``
+    right after it, and ``load_epoch``; then replays of ONE ``TrainingGraph``
     built in the first epoch (``graph=False``: eager steps, the same kernels) until fewer than ``batch_size`` rows remain; ``on_epoch(epoch, step)``
     -- validation and checkpoints are the caller's, through ``validation.validate`` and ``step.save_networks``.  ``rng``: a seed or a
     ``numpy.random.Generator``; an int seeds one generator for the whole run.  ``gen_z``: one fixed [batch_size, z_dim] latent batch for every step
@@ -356,7 +402,7 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
         lr = lr_schedule.lr_at(k)
         step.set_lr(lr, lr)
         items = dataset.epoch_items(rng)
-        dataset.load_epoch(items)
+        dataset.load_epoch(items, dataset.epoch_augment(rng) if dataset.augment is not None else None)
         if dataset.rows < batch_size:
             raise RuntimeError(f'train_epochs: an epoch of {dataset.rows} rows is shorter than a batch of {batch_size}')
         if graph and runner is None:

@@ -640,6 +640,33 @@ int afcm_batch_assemble(void* a, void* b, float* slice_idx, const void* pool, in
 int afcm_cursor_advance(int64_t* cursor, int64_t by, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Augmented training batches: afcm_batch_assemble with the train phase's geometric transforms (data/augment/transforms.py: RandomFlip 25-50,
+ * RandomRotate90 53-80, RandomRotate 83-112 with axes [[2, 1]], order 0, mode 'reflect'; configs/defaults.py:62-76), applied in that order to the
+ * cropped / padded, normalised [1, h, w] plane as Transformer.raw_transform() composes them (transforms.py:729-769).
+ * augment: DEVICE float64 [n_items][8], row r of sample i the same r as the item row: (flip_h, flip_w, k, angle, c, s, off_y, off_x).  All planes of
+ * an item, the target included, share the row.  For an item plane p0 [h, w] (afcm_batch_assemble's):
+ *   p1 = p0 flipped along h if flip_h, along w if flip_w                                     (numpy.flip)
+ *   p2 = numpy.rot90(p1, k), k in 0..3; odd k needs h == w
+ *   p3[y][x] = p2[reflect(floor(iy + 0.5), h)][reflect(floor(ix + 0.5), w)] with, in float64 and every operation rounded on its own,
+ *              iy = (y * c + x * s) + off_y,  ix = (y * (-s) + x * c) + off_x,
+ *              reflect(i, n) = m < n ? m : 2n - 1 - m with m = i mod 2n taken non-negative (half-sample symmetric, any number of periods):
+ *              scipy.ndimage.rotate(p2, angle, reshape=False, order=0, mode='reflect') when c = cosdg(angle), s = sindg(angle) and
+ *              off = centre - [[c, s], [-s, c]] centre, centre = ((h - 1) / 2, (w - 1) / 2).  The HOST computes c, s and off; the kernel evaluates no
+ *              trigonometric function and does not read `angle`, which is carried for the record.
+ * The kernel walks the chain backwards per output pixel -- rotation, quarter turns, flips -- and reads the resulting item-plane coordinate through
+ * afcm_batch_assemble's crop / pad / normalise: the reflect acts at the border of the [h, w] item plane, padding included.  A thick-slice plane
+ * outside the volume stays the constant it is.  A row with no flip, k = 0, c = 1, s = 0 and both offsets 0 takes afcm_batch_assemble's own
+ * contiguous path: the same bits.
+ * The kernel checks the row as it checks the item row.  A row is valid when flip_h and flip_w are 0 or 1; k is 0, 1, 2 or 3, and even unless h == w;
+ * c, s, off_y, off_x are finite with |c|, |s| <= 1 and |off_y|, |off_x| <= h + w, so that no coordinate leaves the int32 range before the reflect.
+ * An item whose item row or parameter row is invalid reads nothing from the pool and is NaN throughout, label included.
+ * Thread shape, stores, stream behaviour and AFCM_E_INVALID as afcm_batch_assemble; also AFCM_E_INVALID: a null augment, h + w > 2^28.
+ * ---------------------------------------------------------------------------------------- */
+int afcm_batch_assemble_aug(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                            int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment, const int64_t* cursor, int32_t first,
+                            int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * The training loop's time-dependent scalars on the device (r11), so that ONE captured graph stays right for a whole run.
  * The schedule block is a DEVICE array of 8 doubles:
  *   [0] total_iters  images seen: the reference's total_iters / cur_nimg (train.py:50-53), exact in a double

@@ -3,6 +3,7 @@ against the fixed-input one.  Two steps, each its own process (run each under it
 
     python tools/bench_train_feed.py feed  [--repeats 5]   # (a) host arm against device arm, ms per batch; (b) the launch alone, device events
     python tools/bench_train_feed.py step  [--repeats 3]   # TrainingGraph.replay() against capture_step's replay on fixed inputs, full-width bf16
+    python tools/bench_train_feed.py feed --augment        # afcm_batch_assemble_aug (identity and random rows) beside the plain launch; the host arm
 
 (a) alternates ``DeviceSliceSet.host_batch`` (SliceDataset items in numpy, stacked, uploaded) and ``DeviceSliceSet.batch`` (one launch) over the same
 rows of a synthetic uint8 set after a warm-up of each, the alternation repeated; wall time by a host clock ended by a synchronise.  (b) times
@@ -111,6 +112,84 @@ def feed(args):
     return 0 if equal else 1
 
 
+def feed_augment(args):
+    """``feed --augment``: the augmented launch (identity rows: the contiguous path; full random rows: the gather) beside the plain launch, device
+    events, the arms alternated inside every repeat; and the host arm -- stacked ``SliceDataset`` items + ``augment.apply_host`` -- by a host clock."""
+    import torch
+    from afcm_amd import _lib
+    import numpy as np
+    from afcm_amd.augment import AugmentConfig, identity_rows, make_rows
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_train_feed.py needs a GPU: a time taken without one says nothing')
+    dev = torch.device('cuda:0')
+    ds = synthetic_set(args.subjects, args.depth, args.res, dev, augment=AugmentConfig(flip_axes=(1, 2), rotate90=True, angle_spectrum=45))
+    items, random_rows = ds.epoch_items(0), ds.epoch_augment(1)
+    # flip_w alone: the gather's whole coordinate arithmetic on rows that are read contiguously (backwards) -- what separates the arithmetic from the
+    # scattered reads of a rotation
+    tables = {'identity': torch.from_numpy(identity_rows(len(items))).to(dev), 'flip_w': torch.from_numpy(make_rows(0, 1, 0, np.zeros(len(items)), (args.res, args.res))).to(dev),
+              'random': torch.from_numpy(random_rows).to(dev)}
+    ds.load_epoch(items, random_rows)
+    batches = min(args.batches, len(items) // args.batch)
+    lib, launches = _lib.load(), {}
+    for out_name, out_dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
+        a = torch.empty((args.batch, 4, args.res, args.res), dtype=out_dtype, device=dev)
+        b = torch.empty((args.batch, 1, args.res, args.res), dtype=out_dtype, device=dev)
+        c = torch.empty((args.batch, 1), dtype=torch.float32, device=dev)
+        out_bytes = a.numel() * a.element_size() + b.numel() * b.element_size()
+        head = (a.data_ptr(), b.data_ptr(), c.data_ptr(), ds.pool.data_ptr(), ds.pool.numel(), _lib.SRC_U8, ds.vols.data_ptr(), int(ds.vols.shape[0]),
+                ds.items.data_ptr(), int(ds.items.shape[0]))
+        tail = (None, 0, args.batch, 4, args.res, args.res, _lib.dtype_code(a), 0., 255., _lib.stream_ptr(a))
+
+        def plain():
+            assert lib.afcm_batch_assemble(*head, *tail) == 0
+
+        def augmented(table):
+            def launch():
+                assert lib.afcm_batch_assemble_aug(*head, table.data_ptr(), *tail) == 0
+            return launch
+
+        arms = {'plain': plain, 'aug_identity': augmented(tables['identity']), 'aug_flip_w': augmented(tables['flip_w']),
+                'aug_random': augmented(tables['random'])}
+        us = {name: [] for name in arms}
+        for _ in range(args.repeats):
+            for name, fn in arms.items():
+                us[name].append(events_us(fn))
+        for name, v in us.items():
+            launches[f'{name}_{out_name}'] = dict(per_repeat_us=v, mean_us=sum(v) / len(v), spread_us=spread(v),
+                                                  ns_per_kib=sum(v) / len(v) * 1e3 / (out_bytes / 1024))
+
+    def clock(rows):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for j in range(batches):
+            out = ds.host_batch(items, j * args.batch, args.batch, augment=rows)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / batches, out
+
+    host = {'host_plain': None, 'host_random': random_rows}
+    stats, last = {name: [] for name in host}, {}
+    for name, rows in host.items():
+        clock(rows)
+    for _ in range(args.repeats):
+        for name, rows in host.items():
+            ms, last[name] = clock(rows)
+            stats[name].append(ms)
+    device_last = ds.batch((batches - 1) * args.batch, args.batch)
+    equal = all(torch.equal(x, y) for x, y in zip(last['host_random'], device_last))
+    print(f'augmented training batches of {args.batch} x (4 + 1) planes at {args.res}^2 from {args.subjects} uint8 subjects of ({args.depth}, {args.res}, '
+          f'{args.res}); flips, quarter turns and angles in -45 ... 44 drawn per item; {args.repeats} repeats, the arms alternated inside each')
+    for name, s in launches.items():
+        print(f'{name:20s} us per launch {"  ".join(f"{x:7.2f}" for x in s["per_repeat_us"])}   mean {s["mean_us"]:7.2f}   spread {s["spread_us"]:.2f}   '
+              f'{s["ns_per_kib"]:.3f} ns per KiB of output')
+    arms = {}
+    for name, v in stats.items():
+        arms[name] = dict(per_repeat_ms=v, mean_ms=sum(v) / len(v), spread_ms=spread(v))
+        print(f'{name:20s} ms/batch per repeat {"  ".join(f"{x:8.3f}" for x in v)}   mean {arms[name]["mean_ms"]:8.3f}   spread {arms[name]["spread_ms"]:.3f}')
+    print(f'the host arm\'s and the device\'s last augmented batch are {"bit-identical" if equal else "DIFFERENT"}')
+    print(json.dumps(dict(bench='train_feed_augment', res=args.res, batch=args.batch, launches=launches, arms=arms, equal=equal)))
+    return 0 if equal else 1
+
+
 def step(args):
     import torch
     from afcm_amd import layer_schedule as sched
@@ -177,8 +256,11 @@ def main():
     ap.add_argument('--batches', type=int, default=8)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--augment', action='store_true', help='feed: time the augmented launch and the augmenting host arm instead')
     args = ap.parse_args()
-    return {'feed': feed, 'step': step}[args.what](args)
+    if args.augment and args.what != 'feed':
+        raise SystemExit('--augment belongs to the feed step')
+    return {'feed': feed_augment if args.augment else feed, 'step': step}[args.what](args)
 
 
 if __name__ == '__main__':
