@@ -161,6 +161,10 @@ SIGNATURES = {
     'afcm_rescale_plan': (C.c_int, [_i64, _i32, C.POINTER(_i32)]),
     'afcm_rescale_workspace_bytes': (C.c_int64, [_i64, _i32]),
     'afcm_rescale_intensity': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _f64, _f64, _vp]),
+    'afcm_percentile_plan': (C.c_int, [_i64, _i32, C.POINTER(_i32)]),
+    'afcm_percentile_workspace_bytes': (C.c_int64, [_i64, _i32]),
+    'afcm_percentile_bounds': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _f64, _f64, _i32, _vp]),
+    'afcm_clip_normalize': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp]),
     'afcm_group_chunk_bytes': (C.c_int32, []),
     'afcm_group_expand': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
 }

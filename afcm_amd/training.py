@@ -15,10 +15,10 @@ import torch
 from . import _lib
 from .augment import AugmentConfig, apply_host, augment_rows, checked_rows, identity_rows
 from .data import SliceDataset, open_volumes
-from .intensity import rescale_intensity_host
+from .intensity import percentile_clip_host, rescale_intensity_host
 from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch
 from .stylegan3_model import capture_graph, require_capturable
-from .torch_utils.ops.intensity_ops import percentile_fractions, rescale_intensity
+from .torch_utils.ops.intensity_ops import percentile_clip, percentile_fractions, rescale_intensity
 
 
 class DeviceSliceSet:
@@ -31,12 +31,14 @@ class DeviceSliceSet:
     ``rescale=(q_lo, q_hi)``: the sources are raw scanner volumes; each is uploaded as it is and passed through ``rescale_intensity`` with those
     percentiles into a uint8 pool, volume by volume, so the subjects' raw dtypes may differ; ``host_batch`` rescales with
     ``rescale_intensity_host``, the same bits.  None: the volumes are pooled as they are.
+    ``clip=(p_min, p_max)``: the same with ``percentile_clip`` / ``percentile_clip_host`` (each volume its own reference, the lower bound not below
+    0), the normalisation of ``dataset_mode: cmsrnii``.  ``clip`` and ``rescale`` exclude each other.
     ``augment``: an ``AugmentConfig`` (afcm_amd/augment.py; 'train' only) -- the set keeps a float64 [len(self), 8] device table of parameter rows
     beside the item table, ``epoch_augment`` draws an epoch's rows, ``load_epoch`` uploads them and every batch goes through
     ``afcm_batch_assemble_aug``.  None: no table, ``afcm_batch_assemble``."""
 
     def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
-                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None):
+                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None, clip=None):
         if phase not in ('train', 'val', 'test'):
             raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
         if cat_inputs:
@@ -66,14 +68,20 @@ class DeviceSliceSet:
         if not self.volumes:
             raise RuntimeError('DeviceSliceSet: no subjects')
         self.rescale = None if rescale is None else tuple(float(q) for q in rescale)
+        self.clip = None if clip is None else tuple(float(q) for q in clip)
+        if self.rescale is not None and self.clip is not None:
+            raise RuntimeError('DeviceSliceSet: rescale= and clip= are two normalisations of raw sources; give one')
         if self.rescale is not None:
             percentile_fractions(self.rescale, 'DeviceSliceSet: rescale')
+        if self.clip is not None:
+            percentile_fractions(self.clip, 'DeviceSliceSet: clip')
+        normalised = self.rescale is not None or self.clip is not None
         dtypes = sorted({str(v.dtype) for subject in self.volumes for v in subject.values()})
-        if self.rescale is None and len(dtypes) != 1:
+        if not normalised and len(dtypes) != 1:
             raise RuntimeError(f'DeviceSliceSet: mixed source dtypes {dtypes}: the pool holds one dtype, convert the volumes first')
         for name in dtypes:
             _lib.source_code(np.dtype(name), 'DeviceSliceSet')
-        self.source_dtype = np.dtype(np.uint8) if self.rescale is not None else np.dtype(dtypes[0])
+        self.source_dtype = np.dtype(np.uint8) if normalised else np.dtype(dtypes[0])
         rows, offset, self.depths = [], 0, []
         for s, subject in enumerate(self.volumes):
             shapes = {p: tuple(int(n) for n in subject[p].shape) for p in self.paths}
@@ -98,15 +106,18 @@ class DeviceSliceSet:
         if self.device is not None:
             if self.device.type != 'cuda':
                 raise RuntimeError(f'DeviceSliceSet needs a ROCm device (got {self.device}); device=None builds the host-side tables only')
-            if self.rescale is None:
+            if not normalised:
                 pool = np.concatenate([np.ascontiguousarray(subject[p]).reshape(-1) for subject in self.volumes for p in self.paths])
                 self.pool = torch.from_numpy(pool).to(self.device)                       # the one upload of the training set
             else:
                 self.pool = torch.empty(self.pool_elems, dtype=torch.uint8, device=self.device)
                 raw = [subject[p] for subject in self.volumes for p in self.paths]
-                for (at, d, hs, ws), v in zip(rows, raw):                                # each volume raw, rescaled into its place in the pool
-                    rescale_intensity(torch.from_numpy(np.ascontiguousarray(v)).to(self.device), self.rescale,
-                                      out=self.pool[at:at + d * hs * ws].view(d, hs, ws))
+                for (at, d, hs, ws), v in zip(rows, raw):                                # each volume raw, normalised into its place in the pool
+                    uploaded, place = torch.from_numpy(np.ascontiguousarray(v)).to(self.device), self.pool[at:at + d * hs * ws].view(d, hs, ws)
+                    if self.rescale is not None:
+                        rescale_intensity(uploaded, self.rescale, out=place)
+                    else:
+                        percentile_clip(uploaded, self.clip, out=place)
             self.vols = torch.from_numpy(self.vols_host).to(self.device)
             # persistent (a captured graph holds their addresses): the epoch's table, refreshed in place, and the row a graph's next batch starts at
             self.items = torch.full((len(self), 4), -1, dtype=torch.int32, device=self.device)
@@ -211,11 +222,12 @@ class DeviceSliceSet:
             yield self.batch(first, count, dtype=dtype)
 
     def _host_volumes(self, subject):
-        """The subject's volumes as the pool holds them: as given, or rescaled by the host function."""
-        if self.rescale is None:
+        """The subject's volumes as the pool holds them: as given, or rescaled / clipped by the host function."""
+        if self.rescale is None and self.clip is None:
             return self.volumes[subject]
         if subject not in self._host_rescaled:
-            self._host_rescaled[subject] = {p: rescale_intensity_host(v, self.rescale)[0] for p, v in self.volumes[subject].items()}
+            self._host_rescaled[subject] = {p: rescale_intensity_host(v, self.rescale)[0] if self.rescale is not None else percentile_clip_host(v, self.clip)[0]
+                                            for p, v in self.volumes[subject].items()}
         return self._host_rescaled[subject]
 
     def host_batch(self, items, first, count, device=None, augment=None):

@@ -11,9 +11,9 @@ import torch
 
 from . import evaluation
 from .data import SliceDataset, open_volumes
-from .intensity import rescale_intensity_host
+from .intensity import percentile_clip_host, rescale_intensity_host
 from .predictor import SlidingWindowPredictor, patch_indices, validate_halo
-from .torch_utils.ops.intensity_ops import percentile_fractions, rescale_intensity
+from .torch_utils.ops.intensity_ops import percentile_clip, percentile_fractions, rescale_intensity
 from .torch_utils.ops.plane_metrics import plane_stats
 from .torch_utils.ops.volume_metrics import volume_ssim_layers
 from .torch_utils.ops.volume_ops import assemble_slices, halo_accumulate
@@ -151,7 +151,7 @@ def _input_head(real_A):
 
 @torch.no_grad()
 def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4, patch_hw, batch_size, patch_halo=(0, 8, 8), heads=('prediction',),
-                   where='device', min_value=0., max_value=255., rescale=None, share_encoder=False):
+                   where='device', min_value=0., max_value=255., rescale=None, clip=None, share_encoder=False):
     """One subject through the EMA generator: ``source`` (a mapping {internal path: array [D, Hs, Ws]} or an HDF5 file name) -> {head: [C, D, H, W]}
     with ``heads`` out of 'prediction' (``fake_B``) and 'input' (the thick slice each target falls into).  ``step`` needs
     ``set_test_input(real_A, slice_idx)``, ``test()``, ``real_A`` and ``fake_B`` [B, C, H, W] (``StyleGAN3GeneratorStep`` built with ``ema=True``).
@@ -161,6 +161,9 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     ``rescale=(q_lo, q_hi)``: the source is a raw scanner volume and goes through ``intensity.rescale_intensity`` with those percentiles first -- on
     the device after the upload (``where='device'``, still no host read) or through ``rescale_intensity_host`` -- so the loop sees a uint8 volume, the
     same one in both arms.  None: the source is taken as it is.
+    ``clip=(p_min, p_max)``: the same for a subject that is normalised the ``cmsrnii`` way -- ``intensity.percentile_clip`` with those percentiles
+    (and its defaults: the volume is its own reference, the lower bound not below 0) on the device, ``percentile_clip_host`` on the host.  ``clip``
+    and ``rescale`` exclude each other.
     ``share_encoder=True`` (``where='device'`` only): with four-slice inputs the ``thickness`` consecutive targets of one thick slice carry the same
     ``A`` bit for bit, so the step is told which rows of a batch are equal (``set_test_input(a, slice_idx, groups, leaders)``) and runs the
     generator's encoder once per group instead of once per sample.  The batch partition does not change; a group that straddles a batch boundary
@@ -178,8 +181,12 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
         raise ValueError(f'batch_size {batch_size}')
     patch_shape, stride_shape = (1, int(patch_hw[0]), int(patch_hw[1])), (1, 1, 1)      # one patch per slice: the y / x strides never come into play
     validate_halo(patch_halo, patch_shape, stride_shape)
+    if rescale is not None and clip is not None:
+        raise ValueError('predict_volume: rescale= and clip= are two normalisations of a raw source; give one')
     if rescale is not None:
         percentile_fractions(rescale, 'predict_volume: rescale')
+    if clip is not None:
+        percentile_fractions(clip, 'predict_volume: clip')
     out_channels = {}
 
     def channels(head, t):                                    # the map's channel count is the head's, known at the first batch
@@ -188,6 +195,8 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     if where == 'host':
         if rescale is not None:
             source = {path: rescale_intensity_host(open_volumes(source, [path])[path], rescale)[0]}
+        if clip is not None:
+            source = {path: percentile_clip_host(open_volumes(source, [path])[path], clip)[0]}
         ds = SliceDataset(source, phase='test', patch_shape=patch_shape, stride_shape=stride_shape, raw_internal_path_in=[path], raw_internal_path_out=[path],
                           thickness=[] if thickness is None else [thickness], slice_num=slice_num, min_value=min_value, max_value=max_value)
         volume_shape = tuple(ds.raw[path].shape)
@@ -211,6 +220,8 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     volume = torch.from_numpy(np.ascontiguousarray(src)).to(device)                    # the loop's one upload of the subject
     if rescale is not None:
         volume = rescale_intensity(volume, rescale)[0]
+    if clip is not None:
+        volume = percentile_clip(volume, clip)[0]
     volume_shape = (int(volume.shape[0]),) + patch_shape[1:]
     plan = PatchPlan(volume_shape, patch_indices(volume_shape, patch_shape, stride_shape))
     predictors = {}
@@ -261,7 +272,8 @@ def evaluate_volume(step, source, target, *, from_network_range=True, with_3d=Fa
     are gathered on the device and copied once: that copy is the only device -> host transfer and the only synchronise of the whole call.
     ``with_3d=True`` adds ``evaluate_3D`` (volume PSNR and the 7^3-window SSIM evaluate.py:81 reports first) as ``'3d'``: the layer sums of
     ``afcm_volume_ssim`` travel in that same copy, behind the three tables.  ``rescale=(q_lo, q_hi)`` (a ``predict_volume`` keyword) takes a raw
-    scanner volume as the source and rescales it on the device after the upload, still without a host read.
+    scanner volume as the source and rescales it on the device after the upload, still without a host read; ``clip=(p_min, p_max)`` does the same
+    with the percentile clip.
     Returns {'slice': (psnr, ssim, mae), 'one': (psnr, ssim, mae), 'prediction': [C, D, H, W] device tensor} and, on request, '3d': (psnr, ssim, mae)."""
     if predict_kwargs.get('where', 'device') != 'device':
         raise ValueError("evaluate_volume runs on the device; for host arrays use predict_volume(where='host') and afcm_amd.evaluation")

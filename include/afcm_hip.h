@@ -745,6 +745,45 @@ int afcm_rescale_intensity(uint8_t* out, double* stats, void* workspace, const v
                            int64_t src_stride_z, double q_lo, double q_hi, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Percentile-clip normalisation: StandardNIIDataset.__percentile_clip of data/cmsrnii_dataset.py:79-114 with its caller's (x * 255).astype('uint8')
+ * (`dataset_mode: cmsrnii`), for volumes that live on the device.  Two entry points: afcm_percentile_bounds takes the two bounds from a reference
+ * volume r, afcm_clip_normalize maps a volume x with them; x and r may differ in shape and dtype (the reference's reference_tensor; r = x by default).
+ * Both volumes are laid out as afcm_rescale_intensity's: [depth][h][w] of AFCM_SRC_U8 / I16 / F32 / F64, rows contiguous, any stride in z, any
+ * element offset, fewer than 2^31 voxels.
+ *   bounds       EVERY voxel of r takes part -- zeros, negatives, +-inf, denormals and -0.0.  n = depth * h * w.  For q in (q_lo, q_hi), FRACTIONS
+ *                in [0, 1]: vi = q * (n - 1), i = floor(vi), g = vi - i, a = s[i], b = s[min(i + 1, n - 1)] of the sorted voxels s widened exactly to
+ *                double, d = b - a, p = g >= 0.5 ? b - d * (1 - g) : a + d * g -- numpy's `linear` method with its _lerp, every operation double and
+ *                rounded on its own.
+ *   NaN          if r holds any NaN, lo and hi are both NaN (numpy partitions NaNs to the end and checks the last element).
+ *   zeros        -0.0 and +0.0 are one key; which of them a bound carries is not pinned (they are equal numerically, and the map gives equal bytes).
+ *   strictly_positive   non-zero: lo < 0 becomes 0.0 (a NaN fails the comparison and stays).
+ *   map          level = (uint8) trunc(((min(max(v, lo), hi) - lo) / (hi - lo)) * 255.0), double for every source type, each operation rounded on
+ *                its own; min / max as numpy's (a NaN voxel stays NaN; lo > hi, which strictly_positive over an all-negative r gives, yields hi).
+ *                A NaN result -- NaN bounds, a NaN voxel, hi == lo, inf / inf -- becomes 0.  The reference leaves that cast to numpy, where it is 0
+ *                on x86-64 but undefined in C: it is this library's statement, not a pin.
+ * The reference function agrees with this statement bit for bit for all four source dtypes wherever numpy returns float64 bounds for a list q (numpy
+ * 2.x does, float32 arrays included).  Where it can differ: numpy forms b - a of two neighbouring order statistics in the array's own type before
+ * it widens -- in int16 that wraps when they are more than 32767 apart, in float32 it rounds when they are far apart -- and here both are widened
+ * first.
+ * stats: DEVICE double[4] = lo, hi, (double)n, (double)(number of NaNs in r), written by afcm_percentile_bounds and read by afcm_clip_normalize when
+ * its kernel runs.  out: uint8 [depth][h][w], contiguous.
+ * The select is afcm_rescale_intensity's, on keys that order values of either sign: a float's bits with -0.0 mapped to +0.0, then the sign bit
+ * flipped for non-negatives and every bit inverted for negatives; int16 biased by 32768; uint8 as it is.  NaNs get no key: the first histogram pass
+ * counts them apart, in one more word of each workgroup's slot, and the scan adds them.  All digits are 8 bits: uint8 one pass, int16 two (one pass
+ * of 2^16 bins would need 256 KB of LDS), float32 four, float64 eight.  afcm_percentile_plan / afcm_percentile_workspace_bytes: as
+ * afcm_rescale_plan / afcm_rescale_workspace_bytes (pure host, the same 11 values).  The map has afcm_rescale_intensity's run structure.
+ * No global atomic, no host read, no allocation, no synchronise, no scratch; `workspace` needs no initialisation.  Bit-identical from call to call.
+ * AFCM_E_INVALID: null pointers, an unknown dtype, extents < 1, N >= 2^31, a negative z stride, fractions outside 0 <= q_lo <= q_hi <= 1 (NaN
+ * included), a workspace or stats pointer that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------- */
+int afcm_percentile_plan(int64_t n, int32_t src_dtype, int32_t* plan);
+int64_t afcm_percentile_workspace_bytes(int64_t n, int32_t src_dtype);
+int afcm_percentile_bounds(double* stats, void* workspace, const void* volume, int32_t src_dtype, int32_t depth, int32_t h, int32_t w,
+                           int64_t src_stride_z, double q_lo, double q_hi, int32_t strictly_positive, void* stream);
+int afcm_clip_normalize(uint8_t* out, const double* stats, const void* volume, int32_t src_dtype, int32_t depth, int32_t h, int32_t w,
+                        int64_t src_stride_z, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * afcm_group_expand: whole per-sample blocks of several tensors repeated by a DEVICE index, in one launch -- the encoder state of G conditioning
  * images handed to a decoder batch of `batch` samples (SynthesisNetwork.decode with `groups`).  For every row k of the table and every sample b
  *   dst_k[b * block_bytes, + block_bytes) = src_k[groups[b] * block_bytes, + block_bytes)     byte for byte.
