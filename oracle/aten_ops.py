@@ -64,12 +64,16 @@ def bias_act(x, b=None, dim=1, act='linear', alpha=None, gain=None, clamp=None):
     return x
 
 
-def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
+def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1, store=None):
     """Zero-insert upsample, pad/crop, FIR, decimate.  Follows _upfirdn2d_ref, SG3OPS/upfirdn2d.py:167-211.
 
     1-D `f` is applied separably (along W, then along H); the gain is split as
     gain**(ndim/2) per pass (line 196).  The FIR is a true convolution unless `flip_filter`
     (line 198-199: aten's conv is a correlation, so the taps are reversed when flip_filter is False).
+
+    Test instrumentation (not part of the reference signature): ``store`` (callable ``(tensor, tag) -> tensor``) is applied to the taps
+    with their gain ('taps') and to the result of the first of two separable passes ('pass') -- what a kernel that keeps its
+    coefficients and its intermediate in a narrower type rounds.
     """
     assert x.ndim == 4
     n, c, h, w = x.shape
@@ -87,6 +91,8 @@ def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
     z = F.pad(z, [px0, px1, py0, py1])
 
     taps = (f * (gain ** (f.ndim / 2))).to(x.dtype)
+    if store is not None:
+        taps = store(taps, 'taps')
     if not flip_filter:
         taps = taps.flip(list(range(taps.ndim)))
     if taps.ndim == 2:
@@ -94,6 +100,8 @@ def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1):
         z = F.conv2d(z, k, groups=c)
     else:
         z = F.conv2d(z, taps.reshape(1, 1, 1, -1).expand(c, 1, 1, -1), groups=c)
+        if store is not None:
+            z = store(z, 'pass')
         z = F.conv2d(z, taps.reshape(1, 1, -1, 1).expand(c, 1, -1, 1), groups=c)
     return z[:, :, ::dny, ::dnx]                                                   # [line 210]
 
@@ -131,7 +139,7 @@ def downsample2d(x, f, down=2, padding=0, flip_filter=False, gain=1):
 
 
 def filtered_lrelu(x, fu=None, fd=None, b=None, up=1, down=1, padding=0, gain=SQRT2, slope=0.2, clamp=None,
-                   flip_filter=False, codes=None, record=None):
+                   flip_filter=False, codes=None, record=None, store=None):
     """bias -> upfirdn(up, gain up^2) -> leaky-ReLU * gain -> clamp -> upfirdn(down).
 
     Follows _filtered_lrelu_ref, SG3OPS/filtered_lrelu.py:121-153.
@@ -140,6 +148,9 @@ def filtered_lrelu(x, fu=None, fd=None, b=None, up=1, down=1, padding=0, gain=SQ
     upsampled grid; ``codes`` (uint8 [N, C, >= rows used, >= cols], bit 0 = negative branch, bit 1 = clamped -- the meaning of the
     plugin's 2-bit codes, SG3OPS/filtered_lrelu.cu:494-505) imposes the branch decisions of another implementation, so that a
     gradient comparison can separate "a pre-activation within rounding distance of 0 took the other branch" from real errors.
+    ``store`` (callable ``(tensor, tag) -> tensor``) is applied to every intermediate a fused kernel may keep in a narrower type than it
+    accumulates in: x + b ('xb'), the two filters' taps and first passes ('up.taps', 'up.pass', 'down.taps', 'down.pass'), the
+    pre-activation ('pre') and the activation ('act').
     """
     px0, px1, py0, py1 = _pad4(padding)
     fuw, fuh = _fsize(fu)
@@ -147,8 +158,13 @@ def filtered_lrelu(x, fu=None, fd=None, b=None, up=1, down=1, padding=0, gain=SQ
     n, c, h, w = x.shape
     ow = (w * up + px0 + px1 - (fuw - 1) - (fdw - 1) + (down - 1)) // down        # [line 141]
     oh = (h * up + py0 + py1 - (fuh - 1) - (fdh - 1) + (down - 1)) // down        # [line 142]
+    sub = (lambda pre: None) if store is None else (lambda pre: (lambda t, tag: store(t, pre + tag)))
     y = bias_act(x, b)
-    y = upfirdn2d(y, fu, up=up, padding=[px0, px1, py0, py1], gain=up ** 2, flip_filter=flip_filter)
+    if store is not None:
+        y = store(y, 'xb')
+    y = upfirdn2d(y, fu, up=up, padding=[px0, px1, py0, py1], gain=up ** 2, flip_filter=flip_filter, store=sub('up.'))
+    if store is not None:
+        y = store(y, 'pre')
     if record is not None:
         record.append(y.detach())
     if codes is None:
@@ -165,18 +181,24 @@ def filtered_lrelu(x, fu=None, fd=None, b=None, up=1, down=1, padding=0, gain=SQ
         if clamp is not None and clamp >= 0:
             v = torch.where((full & 2) != 0, v.detach().clamp(-clamp, clamp), v)
         y = v
-    y = upfirdn2d(y, fd, down=down, flip_filter=flip_filter)
+    if store is not None:
+        y = store(y, 'act')
+    y = upfirdn2d(y, fd, down=down, flip_filter=flip_filter, store=sub('down.'))
     assert tuple(y.shape) == (n, c, oh, ow), (y.shape, (n, c, oh, ow))
     return y
 
 
-def modulated_conv2d(x, w, s, demodulate=True, padding=0, input_gain=None):
-    """Per-sample weight (de)modulated convolution, literal grouped-conv form.  Follows NET:25-64."""
+def modulated_conv2d(x, w, s, demodulate=True, padding=0, input_gain=None, store=None):
+    """Per-sample weight (de)modulated convolution, literal grouped-conv form.  Follows NET:25-64.
+    ``store`` (test instrumentation, callable ``(tensor, tag) -> tensor``): applied to the sample-independent weight ('weight') -- the
+    tensor an implementation that applies styles and demodulation per plane hands to its matrix units."""
     n = x.shape[0]
     o, i, kh, kw = w.shape
     if demodulate:
         w = w * w.square().mean([1, 2, 3], keepdim=True).rsqrt()                   # [line 42]
         s = s * s.square().mean().rsqrt()                                          # [line 43]  (whole batch)
+    if store is not None:
+        w = store(w, 'weight')
     wn = w[None] * s[:, None, :, None, None]                                       # [N,O,I,k,k]  [line 46-47]
     if demodulate:
         d = (wn.square().sum(dim=[2, 3, 4]) + 1e-8).rsqrt()                        # [line 51]

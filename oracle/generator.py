@@ -100,13 +100,32 @@ def plan(img_resolution, img_channels_in, img_channels_out, synthesis_kwargs=Non
                 cond_mod=kw['cond_mod'], c0=int(ch[0]), num_ws=n_layers + 2, kw=kw)
 
 
-def fully_connected(x, weight, bias, act='linear', lr_mul=1.0):
-    """FullyConnectedLayer.forward (NET:89-101)."""
+def fully_connected(x, weight, bias, act='linear', lr_mul=1.0, name=None, codes=None, preact=None):
+    """FullyConnectedLayer.forward (NET:89-101).  ``name`` / ``codes`` / ``preact``: see _plain_lrelu (act='lrelu' only)."""
     w = weight * (lr_mul / math.sqrt(weight.shape[1]))
     b = bias * lr_mul if bias is not None else None
     if act == 'linear' and b is not None:
         return torch.addmm(b[None], x, w.t())
+    if act == 'lrelu' and name is not None:
+        return _plain_lrelu(x @ w.t(), b, name, codes, preact)
     return ops.bias_act(x @ w.t(), b, act=act)
+
+
+def _plain_lrelu(u, b, name, codes, preact):
+    """ops.bias_act(u, b, act='lrelu') of the bottleneck's two plain activations (e_16x16, fc_in) with the instrumentation the layers have:
+    ``preact[name]`` receives u + b; ``codes[name]`` (non-zero = negative branch, of u's shape) imposes another implementation's branch
+    decisions.  Neither given: the plain call."""
+    imposed = codes is not None and name in codes
+    if preact is None and not imposed:
+        return ops.bias_act(u, b, act='lrelu')
+    v = ops.bias_act(u, b)
+    if preact is not None:
+        preact.setdefault(name, []).append(v.detach())
+    if not imposed:
+        return ops.bias_act(v, act='lrelu')
+    neg = codes[name].to(v.device) != 0
+    assert neg.shape == v.shape, (name, tuple(neg.shape), tuple(v.shape))
+    return v * torch.where(neg, torch.full_like(v, 0.2), torch.ones_like(v)) * math.sqrt(2)
 
 
 def mapping(sd, z, c, num_ws, num_layers, lr_mul=0.01, prefix='mapping.'):
@@ -123,8 +142,10 @@ def mapping(sd, z, c, num_ws, num_layers, lr_mul=0.01, prefix='mapping.'):
     return x[:, None].repeat(1, num_ws, 1)
 
 
-def _instr(name, codes, preact):
+def _instr(name, codes, preact, store=None):
     kw = {}
+    if store is not None:
+        kw['store'] = lambda t, tag: store(t, name + '.flr.' + tag)
     if codes is not None and name in codes:
         kw['codes'] = codes[name]
     if preact is not None:
@@ -132,26 +153,38 @@ def _instr(name, codes, preact):
     return kw
 
 
-def synthesis(sd, pl, ws, img_in, dropout_mask=None, prefix='synthesis.', taps=None, codes=None, preact=None):
+def synthesis(sd, pl, ws, img_in, dropout_mask=None, prefix='synthesis.', taps=None, codes=None, preact=None, store=None):
     """SynthesisNetwork.forward (NET:666-705) with update_emas=False.
 
     ``dropout_mask`` (already scaled by 1/(1-p)) stands in for torch's Dropout in training mode;
     ``None`` is eval mode.  ``taps`` optionally receives every resampling layer's output; ``preact`` (dict) every layer's
     pre-activation tensor and ``codes`` (dict name -> uint8 codes) imposes another implementation's leaky-ReLU branch decisions
-    (see oracle.aten_ops.filtered_lrelu).
+    (see oracle.aten_ops.filtered_lrelu).  ``store`` (callable ``(tensor, name) -> tensor``, default None = not called) is applied to every
+    activation tensor a 16-bit implementation keeps in memory: the padded input image ('input'), every layer's conv output
+    ('<layer>.conv', also 'e_16x16.conv' and its activation 'e_16x16') and every layer's filtered_lrelu output after the skip add
+    ('<layer>'), to the weight each conv is run on ('<layer>.weight', 'e_16x16.weight'), and, as '<layer>.flr.<tag>', to the intermediates inside filtered_lrelu (oracle.aten_ops.filtered_lrelu) -- for a model of
+    storage rounding, or any other per-tensor intervention (tests/gen16_grad_ref.py).  ``codes`` / ``preact`` also take the keys 'e_16x16'
+    and 'fc_in': the bottleneck's two plain leaky ReLUs (_plain_lrelu).
     """
     dt = sd[prefix + 'fc_in.weight'].dtype
     ws = ws.to(dt).unbind(1)
     m = pl['margin']
     x = F.pad(img_in.to(dt), [m] * 4)
+    if store is not None:
+        x = store(x, 'input')
     feats = {}
     clamp = pl['conv_clamp']
     for L in pl['enc']:                                                    # EncoderLayer.forward NET:491-516
         p = prefix + L['name'] + '.'
-        w = sd[p + 'weight'] * (1 / math.sqrt(L['cin'] * L['k'] ** 2))
+        w = sd[p + 'weight'] if store is None else store(sd[p + 'weight'], L['name'] + '.weight')
+        w = w * (1 / math.sqrt(L['cin'] * L['k'] ** 2))
         x = ops.conv2d(x, w, padding=L['k'] - 1)
+        if store is not None:
+            x = store(x, L['name'] + '.conv')
         x = ops.filtered_lrelu(x, fu=L['fu'], fd=L['fd'], b=sd[p + 'bias'], up=L['up'], down=L['down'], padding=L['padding'],
-                               gain=math.sqrt(2), slope=0.2, clamp=clamp, **_instr(L['name'], codes, preact))
+                               gain=math.sqrt(2), slope=0.2, clamp=clamp, **_instr(L['name'], codes, preact, store))
+        if store is not None:
+            x = store(x, L['name'])
         if taps is not None:
             taps[L['name']] = x
         if L['store']:
@@ -159,11 +192,15 @@ def synthesis(sd, pl, ws, img_in, dropout_mask=None, prefix='synthesis.', taps=N
 
     # bottleneck (NET:682-686): Conv2dLayer 3x3 lrelu (CoModGAN/layers.py:153-162) -> 4x4 avg-pool -> FC lrelu -> dropout
     p = prefix + 'e_16x16.'
-    w = sd[p + 'weight']
+    w = sd[p + 'weight'] if store is None else store(sd[p + 'weight'], 'e_16x16.weight')
     g = ops.conv2d(x, w * (1 / math.sqrt(w.shape[1] * w.shape[2] ** 2)), padding=w.shape[2] // 2)
-    g = ops.bias_act(g, sd[p + 'bias'], act='lrelu')
+    if store is not None:
+        g = store(g, 'e_16x16.conv')
+    g = _plain_lrelu(g, sd[p + 'bias'], 'e_16x16', codes, preact)
+    if store is not None:
+        g = store(g, 'e_16x16')
     g = F.adaptive_avg_pool2d(g, (4, 4)).flatten(1)
-    g = fully_connected(g, sd[prefix + 'fc_in.weight'], sd[prefix + 'fc_in.bias'], act='lrelu')
+    g = fully_connected(g, sd[prefix + 'fc_in.weight'], sd[prefix + 'fc_in.bias'], act='lrelu', name='fc_in', codes=codes, preact=preact)
     if dropout_mask is not None:
         g = g * dropout_mask
 
@@ -175,12 +212,17 @@ def synthesis(sd, pl, ws, img_in, dropout_mask=None, prefix='synthesis.', taps=N
             styles = styles * (1 / math.sqrt(L['cin'] * L['k'] ** 2))
         input_gain = sd[p + 'magnitude_ema'].rsqrt()
         x = ops.modulated_conv2d(x, sd[p + 'weight'], styles, demodulate=not L['torgb'], padding=L['k'] - 1,
-                                 input_gain=input_gain)
+                                 input_gain=input_gain, **({} if store is None else
+                                                           dict(store=lambda t, tag, name=L['name']: store(t, name + '.' + tag))))
+        if store is not None:
+            x = store(x, L['name'] + '.conv')
         x = ops.filtered_lrelu(x, fu=L['fu'], fd=L['fd'], b=sd[p + 'bias'], up=L['up'], down=L['down'], padding=L['padding'],
                                gain=1.0 if L['torgb'] else math.sqrt(2), slope=1.0 if L['torgb'] else 0.2, clamp=clamp,
-                               **_instr(L['name'], codes, preact))
+                               **_instr(L['name'], codes, preact, store))
         if L['skip']:
             x = x + feats[L['skip_key']]
+        if store is not None:
+            x = store(x, L['name'])
         if taps is not None:
             taps[L['name']] = x
     if pl['output_scale'] != 1:
@@ -188,10 +230,10 @@ def synthesis(sd, pl, ws, img_in, dropout_mask=None, prefix='synthesis.', taps=N
     return x.to(dt)
 
 
-def generator(sd, pl, z, c, cond_img, mapping_layers, dropout_mask=None, taps=None, codes=None, preact=None):
+def generator(sd, pl, z, c, cond_img, mapping_layers, dropout_mask=None, taps=None, codes=None, preact=None, store=None):
     """Stylegan3Generator.forward (NET:737-740)."""
     ws = mapping(sd, z, c, pl['num_ws'], mapping_layers)
-    return synthesis(sd, pl, ws, cond_img, dropout_mask=dropout_mask, taps=taps, codes=codes, preact=preact)
+    return synthesis(sd, pl, ws, cond_img, dropout_mask=dropout_mask, taps=taps, codes=codes, preact=preact, store=store)
 
 
 def random_state_dict(pl, z_dim, c_dim, w_dim, mapping_layers, seed=0, lr_mul=0.01):
