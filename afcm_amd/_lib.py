@@ -153,6 +153,7 @@ SIGNATURES = {
     'afcm_halo_accumulate': (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i32, _i32, _i32] + [_i32] * 17 + [_vp]),
     'afcm_batch_assemble': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp] + [_i32] * 6 + [_f64, _f64, _vp]),
     'afcm_batch_assemble_aug': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp] + [_i32] * 6 + [_f64, _f64, _vp]),
+    'afcm_batch_assemble_noise': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp] + [_i32] * 6 + [_f64, _f64, _vp]),
     'afcm_cursor_advance': (C.c_int, [_vp, _i64, _vp]),
     'afcm_schedule_advance': (C.c_int, [_vp, _i64, _f64, _f64, _f64, _f64, _vp]),
     'afcm_gauss_blur_rmax': (C.c_int32, []),

@@ -4,6 +4,8 @@
 //                           output row (item, plane and row decoding, the table reads and the guards happen once per run) and stores it at once
 //   batch_augment_kernel    the same launch with the item's flips, quarter turns and nearest-neighbour rotation (data/augment/transforms.py:25-112)
 //                           from a DEVICE table of float64 parameter rows: a gather through the same crop / pad / normalise read
+//   batch_intensity_kernel  either of the two with the item's contrast change, Gaussian and Poisson noise (transforms.py:115-133, 619-644) from a
+//                           DEVICE table of float64 rows: a Philox4x32-10 field keyed per item, normals and counts from IEEE operations only
 //   cursor_advance_kernel   cursor[0] += by, one thread: the table position of a captured graph moves on the device
 // The tables cannot be checked on the host, so the kernels check every row before they read the pool; an invalid item reads nothing and comes out as
 // NaN.  No LDS, no atomics; every pool offset is 64-bit.  See include/afcm_hip.h for the semantics kept.
@@ -180,14 +182,208 @@ __global__ __launch_bounds__(VOL_THREADS) void batch_augment_kernel(T* __restric
     store_run<T, RUN>((plane < k ? a + (((long long)i * k + plane) * h + y) * w : b + ((long long)i * h + y) * w) + x0, v, x0, w);
 }
 
+// ---- intensity augmentation: RandomContrast, AdditiveGaussianNoise, AdditivePoissonNoise (data/augment/transforms.py:115-133, 619-644) -----------
+// Philox4x32-10 (Salmon et al. 2011): four 32-bit words from a 128-bit counter and a 64-bit key
+struct philox_words {
+    unsigned w[4];
+};
+__device__ __forceinline__ philox_words philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    return {{c0, c1, c2, c3}};
+}
+
+// ln(x) of a positive normal double from + - x / only (afcm_amd/augment_intensity.py: log_series, the statement both arms evaluate operation by
+// operation): frexp by bits, m into [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1), the odd series by Horner from 1/23 down
+__device__ __forceinline__ double log_series(double x) {
+    const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
+    double m = __longlong_as_double((long long)((bits & 0x800FFFFFFFFFFFFFull) | 0x3FE0000000000000ull));   // [1/2, 1)
+    int e = (int)((bits >> 52) & 0x7FF) - 1022;
+    if (m < 0.7071067811865476) m *= 2.0, e -= 1;
+    const double s = (m - 1.0) / (m + 1.0), s2 = s * s;
+    double acc = 1.0 / 23.0;
+#pragma unroll
+    for (int k = 21; k >= 1; k -= 2) acc = acc * s2 + 1.0 / (double)k;
+    return (double)e * 0.6931471805599453 + 2.0 * (s * acc);
+}
+
+constexpr double inv_factorial(int n) {
+    double f = 1.0;
+    for (int i = 2; i <= n; ++i) f *= (double)i;                               // exact up to 21! < 2^66 with 2^18 | 21!: 48 significant bits
+    return 1.0 / f;
+}
+
+// sin and cos of 2 pi u, u in [0, 1): the quadrant of 4u, Taylor series of the remainder in [0, pi / 2) by Horner (sincos_turns)
+__device__ __forceinline__ void sincos_turns(double u, double& sn, double& cs) {
+    const double t = u * 4.0, q = floor(t);
+    const double r = (t - q) * 1.5707963267948966, r2 = r * r;
+    double a = inv_factorial(21);
+#pragma unroll
+    for (int n = 19; n >= 1; n -= 2) a = inv_factorial(n) - r2 * a;
+    const double s = r * a;
+    double c = inv_factorial(20);
+#pragma unroll
+    for (int n = 18; n >= 0; n -= 2) c = inv_factorial(n) - r2 * c;
+    const int quadrant = (int)q & 3;
+    sn = quadrant == 0 ? s : (quadrant == 1 ? c : (quadrant == 2 ? -s : -c));
+    cs = quadrant == 0 ? c : (quadrant == 1 ? -s : (quadrant == 2 ? -c : s));
+}
+
+// Box-Muller on one word pair: two standard normals; the square root and the division are the correctly rounded ones
+__device__ __forceinline__ void normal_pair(unsigned wa, unsigned wb, double& z0, double& z1) {
+    const double u1 = ((double)wa + 0.5) * (1.0 / 4294967296.0), u2 = (double)wb * (1.0 / 4294967296.0);
+    const double r = __dsqrt_rn(-2.0 * log_series(u1));
+    double sn, cs;
+    sincos_turns(u2, sn, cs);
+    z0 = r * cs, z1 = r * sn;
+}
+
+// One row of the intensity table (include/afcm_hip.h): 0-2 contrast flag, alpha, mean; 3-4 Gaussian flag, std; 5-6 Poisson flag, lam; 7-8 the key;
+// 9 J; 10-33 the cut points T_0 ... T_23
+constexpr int INTENSITY_ROW = 36, INTENSITY_CUTS = 24;
+struct intensity_row {
+    bool valid, contrast, gaussian, poisson;
+    double alpha, mean, std;
+    unsigned key_lo, key_hi;
+    int cuts;
+};
+__device__ __forceinline__ bool whole_in(double v, double hi) { return v >= 0.0 && v <= hi && floor(v) == v; }
+__device__ __forceinline__ intensity_row intensity_row_of(const double* __restrict__ p) {
+    const double fc = p[0], alpha = p[1], mean = p[2], fg = p[3], std = p[4], fp = p[5], k0 = p[7], k1 = p[8], cuts = p[9];
+    const double big = 1.7976931348623157e308;
+    // every comparison is false for a NaN
+    bool valid = (fc == 0.0 || fc == 1.0) && (fg == 0.0 || fg == 1.0) && (fp == 0.0 || fp == 1.0) && fabs(alpha) <= big && fabs(mean) <= big &&
+                 std >= 0.0 && std <= big && whole_in(k0, 4294967295.0) && whole_in(k1, 4294967295.0) && whole_in(cuts, (double)INTENSITY_CUTS);
+    const int n = valid ? (int)cuts : 0;
+    for (int j = 0; j < n; j += 4) {                                           // four loads in flight; j + u <= 23 stays inside the row
+#pragma unroll
+        for (int u = 0; u < 4; ++u) valid = valid && (j + u >= n || whole_in(p[10 + j + u], 4294967296.0));
+    }
+    return {valid, fc == 1.0, fg == 1.0, fp == 1.0, alpha, mean, std, valid ? (unsigned)k0 : 0u, valid ? (unsigned)k1 : 0u, n};
+}
+
+// batch_augment_kernel's item (the gather with an augment table, the contiguous read without one), then contrast, Gaussian and Poisson noise in
+// float64 on the float32 item, one rounding back.  Pixel (y, x) of plane pl takes lane x & 3 of Philox(counter (x >> 2, y, stream | P << 1, 0),
+// key of the row): a run starts at a multiple of 4, so a thread makes RUN / 4 calls per stream, and only in an item whose row sets the flag.
+template <typename S, typename T, int RUN>
+__global__ __launch_bounds__(VOL_THREADS) void batch_intensity_kernel(T* __restrict__ a, T* __restrict__ b, float* __restrict__ slice_idx,
+                                                                      const S* __restrict__ pool, long long pool_elems,
+                                                                      const long long* __restrict__ vols, int n_vols, const int* __restrict__ items,
+                                                                      int n_items, const double* __restrict__ augment,
+                                                                      const double* __restrict__ intensity, int independent_planes,
+                                                                      const long long* __restrict__ cursor, int first, int k, int h, int w, int runs,
+                                                                      long long total, double lo, double range) {
+    static_assert(RUN % 4 == 0, "a run is whole Philox calls");
+    const long long e = (long long)blockIdx.x * VOL_THREADS + threadIdx.x;
+    if (e >= total) return;
+    const int x0 = (int)(e % runs) * RUN;
+    long long r = e / runs;
+    const int y = (int)(r % h);
+    r /= h;
+    const int plane = (int)(r % (k + 1));                                      // plane k: the target B
+    const int i = (int)(r / (k + 1));
+
+    const batch_item it = item_of(i, pool_elems, vols, n_vols, items, n_items, cursor, first, k);
+    augment_row g = {augment == nullptr, true, false, false, 0, 1.0, 0.0, 0.0, 0.0};   // no table: the identity
+    intensity_row n = {false, false, false, false, 1.0, 0.0, 0.0, 0u, 0u, 0};
+    const double* __restrict__ row = intensity + (it.valid ? it.row : 0) * INTENSITY_ROW;    // the item row's own r: inside [0, n_items)
+    if (it.valid) {
+        if (augment != nullptr) g = augment_row_of(augment + it.row * 8, h, w);
+        n = intensity_row_of(row);
+    }
+    const bool valid = it.valid && g.valid && n.valid;
+    const thick_slice at = thick_slice_of(it.idx, it.t, plane < k ? k : 1, plane);
+    if (plane == 0 && y == 0 && x0 == 0) slice_idx[i] = valid ? at.label() : __builtin_nanf("");
+
+    const S* __restrict__ volume = pool + (plane < k ? it.off_a : it.off_b);
+    float v[RUN];
+    if (!valid) {
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) v[j] = __builtin_nanf("");
+    } else if (g.identity || at.pos < 0 || at.pos > it.depth - 1) {            // the contiguous read; a plane outside the volume is a constant
+        assembled_run<S, RUN>(v, volume, it.depth, it.hs, it.ws, it.hs * it.ws, at.pos, y, x0, h, w, lo, range);
+    } else {
+        const double yc = (double)y * g.c, ys = (double)y * (-g.s);
+        const long long oy = crop_offset(it.hs, h), ox = crop_offset(it.ws, w), slice = at.pos * (it.hs * it.ws);
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) {
+            v[j] = 0.0f;
+            if (x0 + j < w) {                                                  // elements past the row are never stored and read nothing
+                int sy, sx;
+                g.source(yc, ys, x0 + j, h, w, sy, sx);
+                const long long yv = sy + oy, xv = sx + ox;                    // the item plane's pixel in the volume's slice, or in the padding
+                v[j] = normalised<S>(volume, slice + yv * it.ws + xv, yv >= 0 && yv < it.hs && xv >= 0 && xv < it.ws, lo, range);
+            }
+        }
+    }
+    if (valid && (n.contrast || n.gaussian || n.poisson)) {                    // a row without a flag: the bits of the launch without the table
+        double t[RUN];
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) t[j] = (double)v[j];
+        if (n.contrast) {
+#pragma unroll
+            for (int j = 0; j < RUN; ++j) {
+                const double c = n.mean + n.alpha * (t[j] - n.mean);
+                t[j] = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);                  // a NaN stays
+            }
+        }
+        const unsigned field = independent_planes ? (unsigned)plane << 1 : 0u;
+        if (n.gaussian) {
+#pragma unroll
+            for (int q = 0; q < RUN / 4; ++q) {
+                const philox_words p = philox4x32((unsigned)(x0 >> 2) + q, (unsigned)y, field, 0u, n.key_lo, n.key_hi);
+                double z[4];
+                normal_pair(p.w[0], p.w[1], z[0], z[1]);
+                normal_pair(p.w[2], p.w[3], z[2], z[3]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) t[4 * q + j] = t[4 * q + j] + n.std * z[j];
+            }
+        }
+        if (n.poisson) {
+            unsigned word[RUN];
+            int hits[RUN];
+#pragma unroll
+            for (int q = 0; q < RUN / 4; ++q) {
+                const philox_words p = philox4x32((unsigned)(x0 >> 2) + q, (unsigned)y, field | 1u, 0u, n.key_lo, n.key_hi);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) word[4 * q + j] = p.w[j], hits[4 * q + j] = 0;
+            }
+            for (int c = 0; c < n.cuts; c += 4) {                              // inversion by sequential search: the cut points at or below the word
+                double cut[4];                                                 // four loads in flight; c + u <= 23 stays inside the row
+#pragma unroll
+                for (int u = 0; u < 4; ++u) cut[u] = row[10 + c + u];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {                                  // a whole cut point: the comparison in integers; 2^32, or past J: never
+                    const bool live = c + u < n.cuts && cut[u] <= 4294967295.0;
+                    const unsigned t_u = live ? (unsigned)cut[u] : 0xFFFFFFFFu;
+#pragma unroll
+                    for (int j = 0; j < RUN; ++j) hits[j] += live && word[j] >= t_u ? 1 : 0;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < RUN; ++j) t[j] = t[j] + (double)hits[j];
+        }
+#pragma unroll
+        for (int j = 0; j < RUN; ++j) v[j] = (float)t[j];
+    }
+    store_run<T, RUN>((plane < k ? a + (((long long)i * k + plane) * h + y) * w : b + ((long long)i * h + y) * w) + x0, v, x0, w);
+}
+
 __global__ void cursor_advance_kernel(long long* __restrict__ cursor, long long by) {
     if (blockIdx.x == 0 && threadIdx.x == 0) cursor[0] += by;
 }
 
-// both entry points: the checks, the (source, output) dispatch and the launch; augment null: the plain kernel
+// all three entry points: the checks, the (source, output) dispatch and the launch; augment and intensity null: the plain kernel; intensity given:
+// the noise kernel, with or without an augment table
 static int launch_batch(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols, int32_t n_vols,
-                        const int32_t* items, int32_t n_items, const double* augment, const int64_t* cursor, int32_t first, int32_t count, int32_t k,
-                        int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream) {
+                        const int32_t* items, int32_t n_items, const double* augment, const double* intensity, int32_t independent_planes,
+                        const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value,
+                        double max_value, void* stream) {
     AFCM_REQUIRE(a != nullptr && b != nullptr && slice_idx != nullptr && pool != nullptr && vols != nullptr && items != nullptr,
                  "batch_assemble: null output, label, pool or table");
     AFCM_REQUIRE(src_dtype >= AFCM_SRC_U8 && src_dtype <= AFCM_SRC_F64, "batch_assemble: source dtype %d is not AFCM_SRC_U8 / I16 / F32 / F64", src_dtype);
@@ -210,7 +406,11 @@ static int launch_batch(void* a, void* b, float* slice_idx, const void* pool, in
         AFCM_REQUIRE(threads / VOL_THREADS < 2147483647.0, "batch_assemble: %.0f workgroups exceed the grid", threads / VOL_THREADS);
         const long long total = (long long)count * (k + 1) * h * runs;
         const long long groups = (total + VOL_THREADS - 1) / VOL_THREADS;
-        if (augment == nullptr)
+        if (intensity != nullptr)
+            hipLaunchKernelGGL((batch_intensity_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, (hipStream_t)stream, (T*)a, (T*)b,
+                               slice_idx, (const S*)pool, (long long)pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items, augment,
+                               intensity, (int)independent_planes, (const long long*)cursor, first, k, h, w, runs, total, min_value, range);
+        else if (augment == nullptr)
             hipLaunchKernelGGL((batch_assemble_kernel<S, T, RUN>), dim3((unsigned)groups), dim3(VOL_THREADS), 0, (hipStream_t)stream, (T*)a, (T*)b,
                                slice_idx, (const S*)pool, (long long)pool_elems, (const long long*)vols, n_vols, (const int*)items, n_items,
                                (const long long*)cursor, first, k, h, w, runs, total, min_value, range);
@@ -227,8 +427,8 @@ static int launch_batch(void* a, void* b, float* slice_idx, const void* pool, in
 extern "C" int afcm_batch_assemble(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
                                    int32_t n_vols, const int32_t* items, int32_t n_items, const int64_t* cursor, int32_t first, int32_t count, int32_t k,
                                    int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream) {
-    return afcm::launch_batch(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, nullptr, cursor, first, count, k, h, w,
-                              out_dtype, min_value, max_value, stream);
+    return afcm::launch_batch(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, nullptr, nullptr, 0, cursor, first, count, k,
+                              h, w, out_dtype, min_value, max_value, stream);
 }
 
 extern "C" int afcm_batch_assemble_aug(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
@@ -237,8 +437,19 @@ extern "C" int afcm_batch_assemble_aug(void* a, void* b, float* slice_idx, const
                                        void* stream) {
     using namespace afcm;
     AFCM_REQUIRE(augment != nullptr, "batch_assemble_aug: null augment table");
-    return launch_batch(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, augment, cursor, first, count, k, h, w, out_dtype,
-                        min_value, max_value, stream);
+    return launch_batch(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, augment, nullptr, 0, cursor, first, count, k, h, w,
+                        out_dtype, min_value, max_value, stream);
+}
+
+extern "C" int afcm_batch_assemble_noise(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                                         int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment, const double* intensity,
+                                         int32_t independent_planes, const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h,
+                                         int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream) {
+    using namespace afcm;
+    AFCM_REQUIRE(intensity != nullptr, "batch_assemble_noise: null intensity table");
+    AFCM_REQUIRE(independent_planes == 0 || independent_planes == 1, "batch_assemble_noise: independent_planes %d is not 0 or 1", independent_planes);
+    return launch_batch(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, augment, intensity, independent_planes, cursor, first,
+                        count, k, h, w, out_dtype, min_value, max_value, stream);
 }
 
 extern "C" int afcm_cursor_advance(int64_t* cursor, int64_t by, void* stream) {

@@ -1,5 +1,5 @@
 """assemble_batch / advance_cursor: a training batch from a device-resident pool of volumes (C ABI ``afcm_batch_assemble`` /
-``afcm_batch_assemble_aug`` / ``afcm_cursor_advance``, include/afcm_hip.h; kernels in csrc/batch.hip).
+``afcm_batch_assemble_aug`` / ``afcm_batch_assemble_noise`` / ``afcm_cursor_advance``, include/afcm_hip.h; kernels in csrc/batch.hip).
 
 ``assemble_batch`` is ``SliceDataset(phase='train').__getitem__`` for ``count`` rows of a device-side item table -- ``A``, ``B`` and ``slice_idx`` in
 one launch, bit-identical to the stacked host items.  The tables live on the device, so the kernel checks every row itself: an invalid row comes out
@@ -17,7 +17,7 @@ def _table(t, what, dtype, cols):
 
 
 def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_value=0., max_value=255., dtype=torch.float32, out=None, cursor=None,
-                   augment=None):
+                   augment=None, intensity=None, independent_planes=False):
     """``pool``: 1-D DEVICE tensor (uint8 / int16 / float32 / float64) holding every volume; ``vols``: DEVICE int64 [n_vols, 4] (element offset into the
     pool, depth, hs, ws); ``items``: DEVICE int32 [n_items, 4] (vol_a, vol_b, idx, thickness; thickness -1: none, ``slice_num`` 1 only).  Sample ``i`` is
     table row ``(cursor[0] if cursor is not None else 0) + first + i``.  Returns ``A [count, slice_num, H, W]``, ``B [count, 1, H, W]`` of ``dtype``
@@ -26,7 +26,11 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     tensors (a captured graph needs stable addresses); ``cursor``: DEVICE int64 scalar tensor, see ``advance_cursor``.
     ``augment``: DEVICE float64 [n_items, 8], one parameter row ``(flip_h, flip_w, k, angle, c, s, off_y, off_x)`` beside every item row
     (``afcm_amd.augment.augment_rows``): the item's planes flipped, turned by quarters and rotated as the reference's ``RandomFlip``,
-    ``RandomRotate90`` and ``RandomRotate`` do (``afcm_batch_assemble_aug``); an invalid parameter row is a NaN item as an invalid item row is."""
+    ``RandomRotate90`` and ``RandomRotate`` do (``afcm_batch_assemble_aug``); an invalid parameter row is a NaN item as an invalid item row is.
+    ``intensity``: DEVICE float64 [n_items, 36], one row beside every item row (``afcm_amd.augment_intensity.intensity_rows``): contrast change,
+    Gaussian and Poisson noise as the reference's ``RandomContrast``, ``AdditiveGaussianNoise`` and ``AdditivePoissonNoise`` apply them, after the
+    geometric transforms, from a Philox field generated in the kernel (``afcm_batch_assemble_noise``, with or without ``augment``);
+    ``independent_planes``: every plane of an item its own field.  An invalid row is a NaN item."""
     h, w = (int(v) for v in patch_hw)
     first, count = int(first), int(count)
     _lib.require_slice_num(slice_num, 'assemble_batch')
@@ -39,6 +43,14 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
         _table(augment, 'the augment table', torch.float64, 8)
         if augment.shape[0] != items.shape[0]:
             raise RuntimeError(f'assemble_batch: the augment table has {augment.shape[0]} rows, the item table {items.shape[0]}: one parameter row per item row')
+    if intensity is not None:
+        _table(intensity, 'the intensity table', torch.float64, 36)
+        if intensity.shape[0] != items.shape[0]:
+            raise RuntimeError(f'assemble_batch: the intensity table has {intensity.shape[0]} rows, the item table {items.shape[0]}: one row per item row')
+    if not isinstance(independent_planes, bool):
+        raise RuntimeError(f'assemble_batch: independent_planes must be a bool, got {independent_planes!r}')
+    if independent_planes and intensity is None:
+        raise RuntimeError('assemble_batch: independent_planes without an intensity table')
     _lib.require_out_dtype(dtype, 'assemble_batch')
     if count < 1 or first < 0 or h < 1 or w < 1:
         raise RuntimeError(f'assemble_batch: {count} items from row {first} at [{h}, {w}]: count and the patch must be positive, first not negative')
@@ -58,14 +70,17 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
             if tuple(t.shape) != shape or t.dtype != want or not t.is_contiguous():
                 raise RuntimeError(f'assemble_batch: out {name} must be a contiguous {want} {shape}, got {t.dtype} {tuple(t.shape)} '
                                    f'with strides {tuple(t.stride())}')
-    tensors = (pool, vols, items, a, b, slice_idx) + (() if cursor is None else (cursor,)) + (() if augment is None else (augment,))
+    tensors = (pool, vols, items, a, b, slice_idx) + (() if cursor is None else (cursor,)) + (() if augment is None else (augment,)) + \
+        (() if intensity is None else (intensity,))
     _lib.require_gpu(*tensors)
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f'assemble_batch: pool, tables, outputs and cursor must be on one device, got {sorted({str(t.device) for t in tensors})}')
     head = (a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), code, vols.data_ptr(), int(vols.shape[0]), items.data_ptr(),
             int(items.shape[0]))
     tail = (_lib.ptr(cursor), first, count, slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
-    if augment is None:
+    if intensity is not None:
+        rc = _lib.load().afcm_batch_assemble_noise(*head, _lib.ptr(augment), intensity.data_ptr(), int(independent_planes), *tail)
+    elif augment is None:
         rc = _lib.load().afcm_batch_assemble(*head, *tail)
     else:
         rc = _lib.load().afcm_batch_assemble_aug(*head, augment.data_ptr(), *tail)

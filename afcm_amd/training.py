@@ -7,12 +7,15 @@
 EMA`` with the batches from the device (or, ``where='host'``, from ``SliceDataset``: the comparison arm).  ``TrainingGraph`` is that loop's body as one
 replayed graph that reads its batch through a device-side cursor: no host data work between steps.  With ``DeviceSliceSet(augment=AugmentConfig(...))``
 a float64 table of parameter rows (afcm_amd/augment.py) travels beside the item table and every batch comes out of ``afcm_batch_assemble_aug``
-flipped, turned and rotated as the reference's training transforms do it, inside the same launch.
+flipped, turned and rotated as the reference's training transforms do it, inside the same launch.  With
+``DeviceSliceSet(intensity=IntensityConfig(...))`` a second float64 table (afcm_amd/augment_intensity.py) carries the item's contrast change and the key
+and parameters of its Gaussian and Poisson noise, generated inside ``afcm_batch_assemble_noise``.
 """
 import numpy as np
 import torch
 
 from . import _lib
+from . import augment_intensity
 from .augment import AugmentConfig, apply_host, augment_rows, checked_rows, identity_rows
 from .data import SliceDataset, open_volumes
 from .intensity import percentile_clip_host, rescale_intensity_host
@@ -35,10 +38,14 @@ class DeviceSliceSet:
     0), the normalisation of ``dataset_mode: cmsrnii``.  ``clip`` and ``rescale`` exclude each other.
     ``augment``: an ``AugmentConfig`` (afcm_amd/augment.py; 'train' only) -- the set keeps a float64 [len(self), 8] device table of parameter rows
     beside the item table, ``epoch_augment`` draws an epoch's rows, ``load_epoch`` uploads them and every batch goes through
-    ``afcm_batch_assemble_aug``.  None: no table, ``afcm_batch_assemble``."""
+    ``afcm_batch_assemble_aug``.  None: no table, ``afcm_batch_assemble``.
+    ``intensity``: an ``IntensityConfig`` (afcm_amd/augment_intensity.py; 'train' only, with or without ``augment``) -- a float64 [len(self), 36]
+    device table beside the others, ``epoch_intensity`` draws an epoch's rows, ``load_epoch`` uploads them and every batch goes through
+    ``afcm_batch_assemble_noise``.  None: no table, the launches above."""
 
     def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
-                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None, clip=None):
+                 rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None, clip=None,
+                 intensity=None):
         if phase not in ('train', 'val', 'test'):
             raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
         if cat_inputs:
@@ -54,6 +61,12 @@ class DeviceSliceSet:
                 raise RuntimeError(f"DeviceSliceSet: augmentation belongs to the 'train' phase, got phase {phase!r}")
             augment.check_patch(patch_shape[1:], 'DeviceSliceSet')
         self.augment = augment
+        if intensity is not None:
+            if not isinstance(intensity, augment_intensity.IntensityConfig):
+                raise RuntimeError(f'DeviceSliceSet: intensity must be an IntensityConfig or None, got {type(intensity).__name__}')
+            if phase != 'train':
+                raise RuntimeError(f"DeviceSliceSet: augmentation belongs to the 'train' phase, got phase {phase!r}")
+        self.intensity = intensity
         self.phase, self.patch_shape, self.rand_output, self.slice_num = phase, patch_shape, bool(rand_output), int(slice_num)
         self.raw_internal_path_in, self.raw_internal_path_out = list(raw_internal_path_in), list(raw_internal_path_out)
         self.thickness = [int(t) for t in thickness]
@@ -101,7 +114,7 @@ class DeviceSliceSet:
         self._idx = np.concatenate([np.arange(d, dtype=np.int64) for d in self.depths])
         self._host_sets, self._host_rescaled = {}, {}
         self.device = None if device is None else torch.device(device)
-        self.pool = self.vols = self.items = self.cursor = self.augment_table = None
+        self.pool = self.vols = self.items = self.cursor = self.augment_table = self.intensity_table = None
         self.rows = self.position = 0
         if self.device is not None:
             if self.device.type != 'cuda':
@@ -124,6 +137,8 @@ class DeviceSliceSet:
             self.cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
             if self.augment is not None:                                                 # persistent as the item table is: row r belongs to item row r
                 self.augment_table = torch.from_numpy(identity_rows(len(self))).to(self.device)
+            if self.intensity is not None:
+                self.intensity_table = torch.from_numpy(augment_intensity.identity_rows(len(self))).to(self.device)
 
     def __len__(self):
         return int(self._idx.shape[0])
@@ -176,19 +191,40 @@ class DeviceSliceSet:
             return None
         return identity_rows(n) if augment is None else checked_rows(augment, n, f'DeviceSliceSet.{what}')
 
-    def load_epoch(self, items, augment=None):
+    def epoch_intensity(self, seed_or_generator=None, rows=None):
+        """The float64 [rows, 36] intensity table of one epoch (``rows``: ``len(self)`` when None), drawn by ``augment_intensity.intensity_rows``
+        from the set's ``IntensityConfig``; call it after ``epoch_items`` and ``epoch_augment`` on the same generator, as ``train_epochs`` does."""
+        if self.intensity is None:
+            raise RuntimeError('DeviceSliceSet.epoch_intensity: this set was built without intensity=IntensityConfig(...)')
+        rng = seed_or_generator if isinstance(seed_or_generator, np.random.Generator) else np.random.default_rng(seed_or_generator)
+        return augment_intensity.intensity_rows(self.intensity, len(self) if rows is None else rows, rng)
+
+    def _checked_intensity(self, intensity, n, what):
+        """``_checked_augment`` for the intensity table."""
+        if self.intensity is None:
+            if intensity is not None:
+                raise RuntimeError(f'DeviceSliceSet.{what}: an intensity table for a set built without intensity=IntensityConfig(...)')
+            return None
+        return augment_intensity.identity_rows(n) if intensity is None else augment_intensity.checked_rows(intensity, n, f'DeviceSliceSet.{what}')
+
+    def load_epoch(self, items, augment=None, intensity=None):
         """Uploads the table into the persistent device table (rows past it are marked invalid) and puts the cursor back to row 0.  A set built
-        with ``augment`` takes the epoch's parameter rows (``epoch_augment``) the same way, identity rows when none are given."""
+        with ``augment`` takes the epoch's parameter rows (``epoch_augment``) the same way, identity rows when none are given; one built with
+        ``intensity`` its intensity rows (``epoch_intensity``) likewise."""
         self._need_device('load_epoch')
         items = self._checked_items(items)
         if items.shape[0] > self.items.shape[0]:
             raise RuntimeError(f'DeviceSliceSet.load_epoch: {items.shape[0]} rows do not fit the device table of {self.items.shape[0]} (one per slice)')
         augment = self._checked_augment(augment, items.shape[0], 'load_epoch')
+        intensity = self._checked_intensity(intensity, items.shape[0], 'load_epoch')
         self.items[:items.shape[0]].copy_(torch.from_numpy(items), non_blocking=False)
         self.items[items.shape[0]:].fill_(-1)
         if augment is not None:
             self.augment_table[:items.shape[0]].copy_(torch.from_numpy(augment), non_blocking=False)
             self.augment_table[items.shape[0]:].copy_(torch.from_numpy(identity_rows(len(self) - items.shape[0])))
+        if intensity is not None:
+            self.intensity_table[:items.shape[0]].copy_(torch.from_numpy(intensity), non_blocking=False)
+            self.intensity_table[items.shape[0]:].copy_(torch.from_numpy(augment_intensity.identity_rows(len(self) - items.shape[0])))
         self.rows = int(items.shape[0])
         self.rewind()
 
@@ -208,7 +244,8 @@ class DeviceSliceSet:
         if not use_cursor and (count < 1 or first < 0 or first + count > self.rows):
             raise RuntimeError(f'DeviceSliceSet.batch: rows [{first}, {first + count}) are not inside the loaded epoch of {self.rows} (load_epoch first)')
         return assemble_batch(self.pool, self.vols, self.items, first, count, self.patch_shape[1:], slice_num=self.slice_num, min_value=self.min_value,
-                              max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None, augment=self.augment_table)
+                              max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None, augment=self.augment_table,
+                              intensity=self.intensity_table, independent_planes=self.intensity is not None and self.intensity.independent_planes)
 
     def batches(self, batch_size, drop_last=False, dtype=torch.float32):
         """The loaded epoch batch by batch; the last batch is partial unless ``drop_last``, as the reference's loader leaves it."""
@@ -230,12 +267,14 @@ class DeviceSliceSet:
                                             for p, v in self.volumes[subject].items()}
         return self._host_rescaled[subject]
 
-    def host_batch(self, items, first, count, device=None, augment=None):
+    def host_batch(self, items, first, count, device=None, augment=None, intensity=None):
         """The same batch through ``SliceDataset(phase='train', thickness=[t])`` items, stacked and uploaded: the comparison arm of tests and
         benchmark.  ``augment``: the parameter table that goes with ``items`` (a set built with ``augment`` only); ``augment.apply_host`` applies
-        row ``first + j`` to ``A`` and ``B`` of item ``first + j``.  A row the kernel would refuse raises here."""
+        row ``first + j`` to ``A`` and ``B`` of item ``first + j``.  ``intensity``: the intensity table that goes with ``items`` (a set built with
+        ``intensity`` only), applied after it by ``augment_intensity.apply_host``.  A row the kernel would refuse raises here."""
         items = self._checked_items(items)
         augment = None if augment is None else self._checked_augment(augment, items.shape[0], 'host_batch')
+        intensity = None if intensity is None else self._checked_intensity(intensity, items.shape[0], 'host_batch')
         m = len(self.paths)
         a, b, c = [], [], []
         for j, (vol_a, vol_b, idx, t) in enumerate(items[first:first + count].tolist()):
@@ -254,6 +293,10 @@ class DeviceSliceSet:
             item = ds[idx]
             if augment is not None:
                 item['A'], item['B'] = apply_host(item['A'], augment[first + j]), apply_host(item['B'], augment[first + j])
+            if intensity is not None:
+                independent = self.intensity.independent_planes
+                item['A'] = augment_intensity.apply_host(item['A'], intensity[first + j], independent, 0)
+                item['B'] = augment_intensity.apply_host(item['B'], intensity[first + j], independent, self.slice_num)
             a.append(item['A'])
             b.append(item['B'])
             c.append(torch.from_numpy(item['slice_idx']))
@@ -279,14 +322,16 @@ def _fed_step(step, schedule, batch_size, batch, gen_z, cur_nimg=None):
         step.update_ema()
 
 
-def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None, augment=None):
+def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None, augment=None,
+                intensity=None):
     """The inner loop of the reference's train.py:45-77 over the epoch table ``items`` (``DeviceSliceSet.epoch_items``): per batch
     ``total_iters += batch_size``, ``step.set_input(A, B, gen_c=slice_idx)``, ``step.optimize_parameters(cur_nimg=total_iters)`` and, when the step
     has an EMA copy and ``ema_kimgs`` is given, ``step.update_ema(batch_size, total_iters, ema_kimgs, ramp)``.  The last batch is partial, as the
     reference's loader leaves it.  ``where='device'``: the batches come from ``afcm_batch_assemble``, nothing is read back from the device;
     ``where='host'``: from ``SliceDataset`` items (``DeviceSliceSet.host_batch``), the same bits.  Both arms draw ``gen_z`` in the same order
     (``gen_z``: a fixed [batch_size, z_dim] tensor instead of a draw per batch).  ``augment``: the epoch's parameter table
-    (``DeviceSliceSet.epoch_augment``) for a set built with ``augment``; both arms apply it.  Works with ``StyleGAN3GeneratorStep`` and
+    (``DeviceSliceSet.epoch_augment``) for a set built with ``augment``, ``intensity``: the epoch's intensity table (``epoch_intensity``) for one built with ``intensity``; both arms
+    apply them.  Works with ``StyleGAN3GeneratorStep`` and
     ``StyleGAN3Step`` alike.
     Returns the new ``total_iters``."""
     if where not in ('device', 'host'):
@@ -298,12 +343,14 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     n = int(items.shape[0])
     device = next(step.netG.parameters()).device
     augment = dataset._checked_augment(augment, n, 'train_epoch')
+    intensity = dataset._checked_intensity(intensity, n, 'train_epoch')
     if where == 'device':
-        dataset.load_epoch(items, augment)
+        dataset.load_epoch(items, augment, intensity)
     schedule = getattr(step, 'schedule', None) if where == 'device' else None
     for first in range(0, n, batch_size):
         count = min(batch_size, n - first)
-        batch = (lambda: dataset.batch(first, count)) if where == 'device' else (lambda: dataset.host_batch(items, first, count, device=device, augment=augment))
+        batch = (lambda: dataset.batch(first, count)) if where == 'device' else (
+            lambda: dataset.host_batch(items, first, count, device=device, augment=augment, intensity=intensity))
         total_iters += batch_size
         _fed_step(step, schedule, batch_size, batch, None if gen_z is None else gen_z[:count], cur_nimg=total_iters)
         if schedule is None and ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
@@ -326,7 +373,8 @@ class TrainingGraph:
     replay, and the warm-up leaves the block as it found it.  ``undo_warmup=True`` puts the networks' parameters and buffers and the optimizers' state
     back as well (in place: the graph keeps pointing at them), so that the warm-up's real steps leave no trace; the default keeps them, as
     ``capture_step`` does.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None.  A dataset built with ``augment``
-    is captured with ``afcm_batch_assemble_aug``: the parameter table is persistent as the item table is, and the cursor moves through both."""
+    is captured with ``afcm_batch_assemble_aug``: the parameter table is persistent as the item table is, and the cursor moves through both; one built with
+    ``intensity`` with ``afcm_batch_assemble_noise``, its table persistent in the same way."""
 
     def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None, undo_warmup=False):
         require_capturable(step, 'TrainingGraph')
@@ -376,8 +424,8 @@ class TrainingGraph:
 
         self.graph = capture_graph(lambda: _fed_step(step, schedule, batch_size, cursor_batch, self.gen_z), warmup, next_rows, leave_no_trace)
 
-    def load_epoch(self, items, augment=None):
-        self.dataset.load_epoch(items, augment)
+    def load_epoch(self, items, augment=None, intensity=None):
+        self.dataset.load_epoch(items, augment, intensity)
 
     def rewind(self):
         self.dataset.rewind()
@@ -396,7 +444,7 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
     """The outer loop of the reference's train.py:38-45 for a step built with a ``DeviceSchedule``.  ``epochs``: an iterable of epoch numbers
     (``range(epoch_count, n_epochs + n_epochs_decay + 1)``).  Per epoch: ``step.set_lr(lr_schedule.lr_at(k))`` for G and D, k = 1 for the first
     (``update_learning_rate()`` at the top of every epoch); ``dataset.epoch_items(rng)``, for a set built with ``augment`` ``epoch_augment(rng)``
-    right after it, and ``load_epoch``; then replays of ONE ``TrainingGraph``
+    right after it, for one built with ``intensity`` ``epoch_intensity(rng)`` after that, and ``load_epoch``; then replays of ONE ``TrainingGraph``
     built in the first epoch (``graph=False``: eager steps, the same kernels) until fewer than ``batch_size`` rows remain; ``on_epoch(epoch, step)``
     -- validation and checkpoints are the caller's, through ``validation.validate`` and ``step.save_networks``.  ``rng``: a seed or a
     ``numpy.random.Generator``; an int seeds one generator for the whole run.  ``gen_z``: one fixed [batch_size, z_dim] latent batch for every step
@@ -414,7 +462,8 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
         lr = lr_schedule.lr_at(k)
         step.set_lr(lr, lr)
         items = dataset.epoch_items(rng)
-        dataset.load_epoch(items, dataset.epoch_augment(rng) if dataset.augment is not None else None)
+        augment = dataset.epoch_augment(rng) if dataset.augment is not None else None
+        dataset.load_epoch(items, augment, dataset.epoch_intensity(rng) if dataset.intensity is not None else None)
         if dataset.rows < batch_size:
             raise RuntimeError(f'train_epochs: an epoch of {dataset.rows} rows is shorter than a batch of {batch_size}')
         if graph and runner is None:

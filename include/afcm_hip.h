@@ -667,6 +667,46 @@ int afcm_batch_assemble_aug(void* a, void* b, float* slice_idx, const void* pool
                             int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Training batches with intensity augmentation: afcm_batch_assemble (augment null) or afcm_batch_assemble_aug (augment given) followed, per item, by
+ * the train phase's intensity transforms (data/augment/transforms.py: RandomContrast 115-133, AdditiveGaussianNoise 619-630, AdditivePoissonNoise
+ * 633-644; configs/defaults.py:83-88), in that order, after the geometric ones as the configuration lists them.
+ * intensity: DEVICE float64 [n_items][36], row r of sample i the same r as the item row:
+ *   0-2   contrast flag, alpha, mean      3-4  Gaussian flag, std      5-6  Poisson flag, lam (carried for the record)
+ *   7-8   key_lo, key_hi, integers in [0, 2^32)      9  J      10-33  T_0 ... T_23, integer cut points      34-35  zero, not read
+ * p: the float32 value the launch without the table produces, widened to double.  All arithmetic is float64, every operation rounded on its own:
+ *   contrast   t = mean + alpha * (t - mean), then t < -1 ? -1 : (t > 1 ? 1 : t): a NaN stays
+ *   Gaussian   t = t + std * z
+ *   Poisson    t = t + (double)count
+ * No clip after the noise (the reference has none).  The result is rounded once to float32, then to out_dtype as the other launches round.
+ * The reference adds in float64 BEFORE its float32 cast; here the float32 item is widened back: pixels of an item that executed a transform may differ
+ * from the reference's arithmetic by one float32 unit in the last place.
+ * The field: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds; counter 0 / key 0 gives
+ * 6627e8d5 e169c58d bc57ac4c 9b00dbd8).  Output pixel (y, x) of plane pl (0 ... k - 1: a; k: b) uses word x & 3 of
+ * Philox(counter = (x >> 2, y, stream | P << 1, 0), key = (key_lo, key_hi)), stream 0: Gaussian, 1: Poisson, P = pl with independent_planes, else 0:
+ * every plane of an item, the target and the zero planes outside the volume included, then receives the same field, as the reference's
+ * equally seeded per-plane transformers give it.
+ * z: Box-Muller per word pair, (w0, w1) -> lanes 0, 1 and (w2, w3) -> lanes 2, 3: u1 = (w0 + 0.5) 2^-32, u2 = w1 2^-32, r = sqrt(-2 LOG(u1)) with the
+ * correctly rounded square root, z = r COS(2 pi u2), r SIN(2 pi u2), with
+ *   LOG(x)      m, e = frexp(x); m < 0.7071067811865476: m *= 2, e -= 1; s = (m - 1) / (m + 1), s2 = s * s; acc = 1.0 / 23.0, then
+ *               acc = acc * s2 + 1.0 / k for k = 21, 19 ... 1; e * 0.6931471805599453 + 2.0 * (s * acc)
+ *   SIN, COS    t = u * 4, q = floor(t), r = (t - q) * 1.5707963267948966, r2 = r * r; a = 1 / 21!, then a = 1 / n! - r2 * a for n = 19, 17 ... 1, S = r * a;
+ *               C = 1 / 20!, then C = 1 / n! - r2 * C for n = 18, 16 ... 0; (sin, cos) = (S, C), (C, -S), (-S, -C), (-C, S) for q = 0, 1, 2, 3
+ * IEEE + - x / sqrt floor only, so afcm_amd/augment_intensity.py evaluates the same operations in numpy and gets the same bits.
+ * count: the number of j < J with word >= T_j.  The host fills T_j = min(floor(F(j) 2^32), 2^32), F the running float64 sum of p_0 = exp(-lam),
+ * p_j = p_{j-1} lam / j, up to the first T_j >= 2^32 - 1 (lam <= 4 needs 23).
+ * The kernel checks the row as it checks the item row and the augment row, before it reads the pool.  A row is valid when the three flags are 0 or
+ * 1; alpha and mean are finite; std is finite and >= 0; key_lo, key_hi are whole numbers in [0, 2^32 - 1]; J is a whole number in [0, 24]; T_j is a
+ * whole number in [0, 2^32] for j < J.  A NaN fails every comparison.  An item with an invalid row of any table reads nothing from the pool and is NaN
+ * throughout, label included.  A row with all three flags 0 gives the bits of the launch without the table, and pays for no Philox call.
+ * Thread shape, stores, stream behaviour and AFCM_E_INVALID as afcm_batch_assemble(_aug); augment may be null; also AFCM_E_INVALID: a null
+ * intensity, independent_planes not 0 or 1.
+ * ---------------------------------------------------------------------------------------- */
+int afcm_batch_assemble_noise(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                              int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment, const double* intensity,
+                              int32_t independent_planes, const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w,
+                              int32_t out_dtype, double min_value, double max_value, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * The training loop's time-dependent scalars on the device (r11), so that ONE captured graph stays right for a whole run.
  * The schedule block is a DEVICE array of 8 doubles:
  *   [0] total_iters  images seen: the reference's total_iters / cur_nimg (train.py:50-53), exact in a double

@@ -4,6 +4,8 @@ against the fixed-input one.  Two steps, each its own process (run each under it
     python tools/bench_train_feed.py feed  [--repeats 5]   # (a) host arm against device arm, ms per batch; (b) the launch alone, device events
     python tools/bench_train_feed.py step  [--repeats 3]   # TrainingGraph.replay() against capture_step's replay on fixed inputs, full-width bf16
     python tools/bench_train_feed.py feed --augment        # afcm_batch_assemble_aug (identity and random rows) beside the plain launch; the host arm
+    python tools/bench_train_feed.py feed --intensity      # afcm_batch_assemble_noise (identity rows, each transform, all three, the reference's
+                                                           # probabilities) beside the plain and the augmented launch; the host arm
 
 (a) alternates ``DeviceSliceSet.host_batch`` (SliceDataset items in numpy, stacked, uploaded) and ``DeviceSliceSet.batch`` (one launch) over the same
 rows of a synthetic uint8 set after a warm-up of each, the alternation repeated; wall time by a host clock ended by a synchronise.  (b) times
@@ -190,6 +192,100 @@ def feed_augment(args):
     return 0 if equal else 1
 
 
+def feed_intensity(args):
+    """``feed --intensity``: the noise launch beside the plain and the augmented one, device events, the arms alternated inside every repeat --
+    identity rows (the row check alone; once more with 23 cut points to check), every item executing one transform (contrast: the float64 round trip; Gaussian: one Philox call per four
+    pixels, two logarithms, two sine / cosine pairs and two square roots; Poisson at lam 1 and 4: one call and 13 / 23 cut points), every item
+    executing all three, and the reference's execution probabilities (0.2 each); and the host arm by a host clock."""
+    import torch
+    from afcm_amd import _lib
+    import numpy as np
+    from afcm_amd.augment import AugmentConfig
+    from afcm_amd.augment_intensity import IntensityConfig, identity_rows, make_rows
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_train_feed.py needs a GPU: a time taken without one says nothing')
+    dev = torch.device('cuda:0')
+    reference = IntensityConfig(contrast=(0.5, 1.5, 0.0, 0.2), gaussian=(0.0, 1.0, 0.2), poisson=(0.0, 1.0, 0.2))
+    ds = synthetic_set(args.subjects, args.depth, args.res, dev, augment=AugmentConfig(flip_axes=(1, 2), rotate90=True, angle_spectrum=45), intensity=reference)
+    items, geo_rows, reference_rows = ds.epoch_items(0), ds.epoch_augment(1), ds.epoch_intensity(2)
+    n = len(items)
+    keys = np.random.default_rng(3).integers(0, 2 ** 32, (n, 2))
+    std, lam = np.random.default_rng(4).uniform(0.0, 1.0, n), np.random.default_rng(5).uniform(0.0, 1.0, n)
+    all_rows = make_rows(contrast=(1, 1.25, 0.0), gaussian=(1, std), poisson=(1, lam), keys=keys, n=n)
+    tables = {'noise_identity': identity_rows(n), 'noise_contrast': make_rows(contrast=(1, 1.25, 0.0), keys=keys, n=n),
+              'noise_gaussian': make_rows(gaussian=(1, std), keys=keys, n=n), 'noise_poisson_lam1': make_rows(poisson=(1, 1.0), keys=keys, n=n),
+              'noise_poisson_lam4': make_rows(poisson=(1, 4.0), keys=keys, n=n), 'noise_all_three': all_rows, 'noise_reference_0.2': reference_rows}
+    # no flag set, but the 23 cut points of lam 4 in the row: the row check's reads and comparisons alone, without a Philox call or a search
+    checked = make_rows(poisson=(1, 4.0), keys=keys, n=n)
+    checked[:, 5] = 0.0
+    tables['noise_identity_23_cuts'] = checked
+    tables = {name: torch.from_numpy(rows).to(dev) for name, rows in tables.items()}
+    geo = torch.from_numpy(geo_rows).to(dev)
+    ds.load_epoch(items, None, all_rows)
+    batches = min(args.batches, n // args.batch)
+    lib, launches = _lib.load(), {}
+    for out_name, out_dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
+        a = torch.empty((args.batch, 4, args.res, args.res), dtype=out_dtype, device=dev)
+        b = torch.empty((args.batch, 1, args.res, args.res), dtype=out_dtype, device=dev)
+        c = torch.empty((args.batch, 1), dtype=torch.float32, device=dev)
+        out_bytes = a.numel() * a.element_size() + b.numel() * b.element_size()
+        head = (a.data_ptr(), b.data_ptr(), c.data_ptr(), ds.pool.data_ptr(), ds.pool.numel(), _lib.SRC_U8, ds.vols.data_ptr(), int(ds.vols.shape[0]),
+                ds.items.data_ptr(), int(ds.items.shape[0]))
+        tail = (None, 0, args.batch, 4, args.res, args.res, _lib.dtype_code(a), 0., 255., _lib.stream_ptr(a))
+
+        def plain():
+            assert lib.afcm_batch_assemble(*head, *tail) == 0
+
+        def augmented():
+            assert lib.afcm_batch_assemble_aug(*head, geo.data_ptr(), *tail) == 0
+
+        def noisy(table, augment=None):
+            def launch():
+                assert lib.afcm_batch_assemble_noise(*head, augment, table.data_ptr(), 0, *tail) == 0
+            return launch
+
+        arms = dict({'plain': plain, 'aug_random': augmented}, **{name: noisy(table) for name, table in tables.items()})
+        arms['aug_random+noise_all_three'] = noisy(tables['noise_all_three'], geo.data_ptr())
+        us = {name: [] for name in arms}
+        for _ in range(args.repeats):
+            for name, fn in arms.items():
+                us[name].append(events_us(fn))
+        for name, v in us.items():
+            launches[f'{name}_{out_name}'] = dict(per_repeat_us=v, mean_us=sum(v) / len(v), spread_us=spread(v),
+                                                  ns_per_kib=sum(v) / len(v) * 1e3 / (out_bytes / 1024))
+
+    def clock(rows):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for j in range(batches):
+            out = ds.host_batch(items, j * args.batch, args.batch, intensity=rows)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / batches, out
+
+    host = {'host_plain': None, 'host_all_three': all_rows}
+    stats, last = {name: [] for name in host}, {}
+    for name, rows in host.items():
+        clock(rows)
+    for _ in range(args.repeats):
+        for name, rows in host.items():
+            ms, last[name] = clock(rows)
+            stats[name].append(ms)
+    device_last = ds.batch((batches - 1) * args.batch, args.batch)
+    equal = all(torch.equal(x, y) for x, y in zip(last['host_all_three'], device_last))
+    print(f'training batches of {args.batch} x (4 + 1) planes at {args.res}^2 from {args.subjects} uint8 subjects of ({args.depth}, {args.res}, {args.res}) with '
+          f'intensity augmentation; std and lam in [0, 1) per item unless named; {args.repeats} repeats, the arms alternated inside each')
+    for name, s in launches.items():
+        print(f'{name:34s} us per launch {"  ".join(f"{x:7.2f}" for x in s["per_repeat_us"])}   mean {s["mean_us"]:7.2f}   spread {s["spread_us"]:.2f}   '
+              f'{s["ns_per_kib"]:.3f} ns per KiB of output')
+    arms = {}
+    for name, v in stats.items():
+        arms[name] = dict(per_repeat_ms=v, mean_ms=sum(v) / len(v), spread_ms=spread(v))
+        print(f'{name:34s} ms/batch per repeat {"  ".join(f"{x:8.3f}" for x in v)}   mean {arms[name]["mean_ms"]:8.3f}   spread {arms[name]["spread_ms"]:.3f}')
+    print(f'the host arm\'s and the device\'s last noisy batch are {"bit-identical" if equal else "DIFFERENT"}')
+    print(json.dumps(dict(bench='train_feed_intensity', res=args.res, batch=args.batch, launches=launches, arms=arms, equal=equal)))
+    return 0 if equal else 1
+
+
 def step(args):
     import torch
     from afcm_amd import layer_schedule as sched
@@ -257,10 +353,13 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--augment', action='store_true', help='feed: time the augmented launch and the augmenting host arm instead')
+    ap.add_argument('--intensity', action='store_true', help='feed: time the noise launch and its host arm instead')
     args = ap.parse_args()
-    if args.augment and args.what != 'feed':
-        raise SystemExit('--augment belongs to the feed step')
-    return {'feed': feed_augment if args.augment else feed, 'step': step}[args.what](args)
+    if (args.augment or args.intensity) and args.what != 'feed':
+        raise SystemExit('--augment and --intensity belong to the feed step')
+    if args.augment and args.intensity:
+        raise SystemExit('--augment or --intensity, one at a time')
+    return {'feed': feed_intensity if args.intensity else (feed_augment if args.augment else feed), 'step': step}[args.what](args)
 
 
 if __name__ == '__main__':
