@@ -201,13 +201,15 @@ def philox4x32(counter, key):
     return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
 
 
-def field_words(key_lo, key_hi, h, w, stream, plane=0):
-    """uint32 [h, w]: the word of every pixel of one plane -- lane ``x & 3`` of Philox(counter (x >> 2, y, stream | plane << 1, 0))."""
+def field_words(key_lo, key_hi, h, w, stream, plane=0, word3=0):
+    """uint32 [h, w]: the word of every pixel of one plane -- lane ``x & 3`` of Philox(counter (x >> 2, y, stream | plane << 1, word3)).
+    ``word3`` is 0 for the intensity streams; the elastic deformation's fields take 1 and 2 (afcm_amd/augment_elastic.py)."""
     groups = (int(w) + 3) // 4
     counter = np.zeros((int(h), groups, 4), dtype=np.uint64)
     counter[..., 0] = np.arange(groups)[None, :]
     counter[..., 1] = np.arange(int(h))[:, None]
     counter[..., 2] = int(stream) | (int(plane) << 1)
+    counter[..., 3] = int(word3)
     words = philox4x32(counter, np.array([int(key_lo), int(key_hi)], dtype=np.uint64))
     return words.reshape(int(h), groups * 4)[:, :int(w)]
 
@@ -255,9 +257,9 @@ def normals_from_words(words):
     return np.stack([r * c, r * s], axis=-1).reshape(words.shape)
 
 
-def normal_field(key_lo, key_hi, h, w, plane=0):
+def normal_field(key_lo, key_hi, h, w, plane=0, word3=0):
     """float64 [h, w]: the standard normals of one plane (stream 0)."""
-    padded = field_words(key_lo, key_hi, h, 4 * ((int(w) + 3) // 4), 0, plane)
+    padded = field_words(key_lo, key_hi, h, 4 * ((int(w) + 3) // 4), 0, plane, word3)
     return normals_from_words(padded)[:, :int(w)]
 
 

@@ -1,10 +1,13 @@
 """assemble_batch / advance_cursor: a training batch from a device-resident pool of volumes (C ABI ``afcm_batch_assemble`` /
-``afcm_batch_assemble_aug`` / ``afcm_batch_assemble_noise`` / ``afcm_cursor_advance``, include/afcm_hip.h; kernels in csrc/batch.hip).
+``afcm_batch_assemble_aug`` / ``afcm_batch_assemble_noise`` / ``afcm_batch_assemble_elastic`` / ``afcm_cursor_advance``, include/afcm_hip.h; kernels
+in csrc/batch.hip and csrc/elastic.hip).
 
 ``assemble_batch`` is ``SliceDataset(phase='train').__getitem__`` for ``count`` rows of a device-side item table -- ``A``, ``B`` and ``slice_idx`` in
 one launch, bit-identical to the stacked host items.  The tables live on the device, so the kernel checks every row itself: an invalid row comes out
 as a NaN item and reads nothing.  Both calls are asynchronous on the current stream and can be captured into a graph.
 """
+import ctypes
+
 import torch
 
 from ... import _lib
@@ -17,7 +20,7 @@ def _table(t, what, dtype, cols):
 
 
 def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_value=0., max_value=255., dtype=torch.float32, out=None, cursor=None,
-                   augment=None, intensity=None, independent_planes=False):
+                   augment=None, intensity=None, independent_planes=False, elastic=None, elastic_ops=None, workspace=None):
     """``pool``: 1-D DEVICE tensor (uint8 / int16 / float32 / float64) holding every volume; ``vols``: DEVICE int64 [n_vols, 4] (element offset into the
     pool, depth, hs, ws); ``items``: DEVICE int32 [n_items, 4] (vol_a, vol_b, idx, thickness; thickness -1: none, ``slice_num`` 1 only).  Sample ``i`` is
     table row ``(cursor[0] if cursor is not None else 0) + first + i``.  Returns ``A [count, slice_num, H, W]``, ``B [count, 1, H, W]`` of ``dtype``
@@ -30,7 +33,13 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     ``intensity``: DEVICE float64 [n_items, 36], one row beside every item row (``afcm_amd.augment_intensity.intensity_rows``): contrast change,
     Gaussian and Poisson noise as the reference's ``RandomContrast``, ``AdditiveGaussianNoise`` and ``AdditivePoissonNoise`` apply them, after the
     geometric transforms, from a Philox field generated in the kernel (``afcm_batch_assemble_noise``, with or without ``augment``);
-    ``independent_planes``: every plane of an item its own field.  An invalid row is a NaN item."""
+    ``independent_planes``: every plane of an item its own field.  An invalid row is a NaN item.
+    ``elastic``: DEVICE float64 [n_items, 4], one row ``(flag, alpha, key_lo, key_hi)`` beside every item row
+    (``afcm_amd.augment_elastic.elastic_rows``): the item's planes deformed as the reference's ``ElasticDeformation`` does, after the geometric
+    transforms and before the intensity ones, in a fixed number of launches (``afcm_batch_assemble_elastic``, with or without the other two tables);
+    ``elastic_ops = (op_h, op_w, order)``: the DEVICE float64 [H, H] and [W, W] smoothing operators (``augment_elastic.smoothing_operator``) and
+    the spline order, 0, 1 or 3; ``workspace``: a DEVICE uint8 tensor of at least ``elastic_workspace_bytes(count, slice_num, H, W, order)`` (a
+    captured graph needs a persistent one), allocated per call when None.  An invalid row is a NaN item."""
     h, w = (int(v) for v in patch_hw)
     first, count = int(first), int(count)
     _lib.require_slice_num(slice_num, 'assemble_batch')
@@ -51,6 +60,21 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
         raise RuntimeError(f'assemble_batch: independent_planes must be a bool, got {independent_planes!r}')
     if independent_planes and intensity is None:
         raise RuntimeError('assemble_batch: independent_planes without an intensity table')
+    if (elastic is None) != (elastic_ops is None) or (elastic is None and workspace is not None):
+        raise RuntimeError('assemble_batch: elastic= (the table) and elastic_ops= (op_h, op_w, order) go together, workspace= only with them')
+    if elastic is not None:
+        _table(elastic, 'the elastic table', torch.float64, 4)
+        if elastic.shape[0] != items.shape[0]:
+            raise RuntimeError(f'assemble_batch: the elastic table has {elastic.shape[0]} rows, the item table {items.shape[0]}: one row per item row')
+        if not isinstance(elastic_ops, (tuple, list)) or len(elastic_ops) != 3:
+            raise RuntimeError(f'assemble_batch: elastic_ops must be (op_h, op_w, order), got {elastic_ops!r}')
+        op_h, op_w, order = elastic_ops
+        for name, op, n in (('op_h', op_h, h), ('op_w', op_w, w)):
+            if not isinstance(op, torch.Tensor) or op.dtype != torch.float64 or tuple(op.shape) != (n, n) or not op.is_contiguous():
+                got = f'{op.dtype} {tuple(op.shape)}' if isinstance(op, torch.Tensor) else type(op).__name__
+                raise RuntimeError(f'assemble_batch: elastic_ops {name} must be a contiguous torch.float64 [{n}, {n}] for a patch of [{h}, {w}], got {got}')
+        if isinstance(order, bool) or order not in (0, 1, 3):
+            raise RuntimeError(f'assemble_batch: the spline order must be 0, 1 or 3, got {order!r}')
     _lib.require_out_dtype(dtype, 'assemble_batch')
     if count < 1 or first < 0 or h < 1 or w < 1:
         raise RuntimeError(f'assemble_batch: {count} items from row {first} at [{h}, {w}]: count and the patch must be positive, first not negative')
@@ -72,13 +96,25 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
                                    f'with strides {tuple(t.stride())}')
     tensors = (pool, vols, items, a, b, slice_idx) + (() if cursor is None else (cursor,)) + (() if augment is None else (augment,)) + \
         (() if intensity is None else (intensity,))
+    if elastic is not None:
+        need = elastic_workspace_bytes(count, slice_num, h, w, order)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=pool.device)
+        elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or \
+                workspace.numel() < need:
+            got = f'{workspace.dtype} {tuple(workspace.shape)}' if isinstance(workspace, torch.Tensor) else type(workspace).__name__
+            raise RuntimeError(f'assemble_batch: the workspace must be a contiguous 1-D uint8 tensor of at least {need} bytes, got {got}')
+        tensors += (elastic, op_h, op_w, workspace)
     _lib.require_gpu(*tensors)
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f'assemble_batch: pool, tables, outputs and cursor must be on one device, got {sorted({str(t.device) for t in tensors})}')
     head = (a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), code, vols.data_ptr(), int(vols.shape[0]), items.data_ptr(),
             int(items.shape[0]))
     tail = (_lib.ptr(cursor), first, count, slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
-    if intensity is not None:
+    if elastic is not None:
+        rc = _lib.load().afcm_batch_assemble_elastic(*head, _lib.ptr(augment), _lib.ptr(intensity), int(independent_planes), elastic.data_ptr(),
+                                                     op_h.data_ptr(), op_w.data_ptr(), int(order), workspace.data_ptr(), workspace.numel(), *tail)
+    elif intensity is not None:
         rc = _lib.load().afcm_batch_assemble_noise(*head, _lib.ptr(augment), intensity.data_ptr(), int(independent_planes), *tail)
     elif augment is None:
         rc = _lib.load().afcm_batch_assemble(*head, *tail)
@@ -86,6 +122,14 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
         rc = _lib.load().afcm_batch_assemble_aug(*head, augment.data_ptr(), *tail)
     _lib.launched(rc, 'batch_assemble')
     return a, b, slice_idx
+
+
+def elastic_workspace_bytes(count, slice_num, h, w, order):
+    """The bytes ``afcm_batch_assemble_elastic`` needs for ``count`` items of ``slice_num`` + 1 planes of [h, w] at spline order ``order``
+    (``afcm_elastic_plan``): the float32 item, the two float64 fields and their half-smoothed copies and, at order 3, the float64 coefficients."""
+    need = ctypes.c_int64(0)
+    _lib.launched(_lib.load().afcm_elastic_plan(int(count), int(slice_num), int(h), int(w), int(order), ctypes.byref(need), None), 'elastic_plan')
+    return int(need.value)
 
 
 def advance_cursor(cursor, by):

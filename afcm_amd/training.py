@@ -9,17 +9,19 @@ replayed graph that reads its batch through a device-side cursor: no host data w
 a float64 table of parameter rows (afcm_amd/augment.py) travels beside the item table and every batch comes out of ``afcm_batch_assemble_aug``
 flipped, turned and rotated as the reference's training transforms do it, inside the same launch.  With
 ``DeviceSliceSet(intensity=IntensityConfig(...))`` a second float64 table (afcm_amd/augment_intensity.py) carries the item's contrast change and the key
-and parameters of its Gaussian and Poisson noise, generated inside ``afcm_batch_assemble_noise``.
+and parameters of its Gaussian and Poisson noise, generated inside ``afcm_batch_assemble_noise``.  With
+``DeviceSliceSet(elastic=ElasticConfig(...))`` a third float64 table (afcm_amd/augment_elastic.py) carries the decision, the scale and the key of
+the item's elastic deformation, and every batch goes through ``afcm_batch_assemble_elastic``: between the geometric and the intensity transforms.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from . import augment_intensity
+from . import augment_elastic, augment_intensity
 from .augment import AugmentConfig, apply_host, augment_rows, checked_rows, identity_rows
 from .data import SliceDataset, open_volumes
 from .intensity import percentile_clip_host, rescale_intensity_host
-from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch
+from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch, elastic_workspace_bytes
 from .stylegan3_model import capture_graph, require_capturable
 from .torch_utils.ops.intensity_ops import percentile_clip, percentile_fractions, rescale_intensity
 
@@ -41,11 +43,16 @@ class DeviceSliceSet:
     ``afcm_batch_assemble_aug``.  None: no table, ``afcm_batch_assemble``.
     ``intensity``: an ``IntensityConfig`` (afcm_amd/augment_intensity.py; 'train' only, with or without ``augment``) -- a float64 [len(self), 36]
     device table beside the others, ``epoch_intensity`` draws an epoch's rows, ``load_epoch`` uploads them and every batch goes through
-    ``afcm_batch_assemble_noise``.  None: no table, the launches above."""
+    ``afcm_batch_assemble_noise``.  None: no table, the launches above.
+    ``elastic``: an ``ElasticConfig`` (afcm_amd/augment_elastic.py; 'train' only, with or without the other two) -- a float64 [len(self), 4]
+    device table beside the others, ``epoch_elastic`` draws an epoch's rows, ``load_epoch`` uploads them and every batch goes through
+    ``afcm_batch_assemble_elastic``.  The set builds the two smoothing operators of its patch size once (``elastic_ops``, host and device) and owns
+    the launch's workspace, grown to the largest batch asked for (a captured graph keeps the one it was captured with).  None: no table, the
+    launches above."""
 
     def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
                  rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None, clip=None,
-                 intensity=None):
+                 intensity=None, elastic=None):
         if phase not in ('train', 'val', 'test'):
             raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
         if cat_inputs:
@@ -67,6 +74,15 @@ class DeviceSliceSet:
             if phase != 'train':
                 raise RuntimeError(f"DeviceSliceSet: augmentation belongs to the 'train' phase, got phase {phase!r}")
         self.intensity = intensity
+        if elastic is not None:
+            if not isinstance(elastic, augment_elastic.ElasticConfig):
+                raise RuntimeError(f'DeviceSliceSet: elastic must be an ElasticConfig or None, got {type(elastic).__name__}')
+            if phase != 'train':
+                raise RuntimeError(f"DeviceSliceSet: augmentation belongs to the 'train' phase, got phase {phase!r}")
+        self.elastic = elastic
+        # the smoothing operators of the patch size, once: host (the comparison arm) and device
+        self.elastic_ops_host = None if elastic is None else tuple(augment_elastic.smoothing_operator(elastic.sigma, n) for n in patch_shape[1:])
+        self.elastic_ops = self.elastic_workspace = None
         self.phase, self.patch_shape, self.rand_output, self.slice_num = phase, patch_shape, bool(rand_output), int(slice_num)
         self.raw_internal_path_in, self.raw_internal_path_out = list(raw_internal_path_in), list(raw_internal_path_out)
         self.thickness = [int(t) for t in thickness]
@@ -114,7 +130,7 @@ class DeviceSliceSet:
         self._idx = np.concatenate([np.arange(d, dtype=np.int64) for d in self.depths])
         self._host_sets, self._host_rescaled = {}, {}
         self.device = None if device is None else torch.device(device)
-        self.pool = self.vols = self.items = self.cursor = self.augment_table = self.intensity_table = None
+        self.pool = self.vols = self.items = self.cursor = self.augment_table = self.intensity_table = self.elastic_table = None
         self.rows = self.position = 0
         if self.device is not None:
             if self.device.type != 'cuda':
@@ -139,6 +155,9 @@ class DeviceSliceSet:
                 self.augment_table = torch.from_numpy(identity_rows(len(self))).to(self.device)
             if self.intensity is not None:
                 self.intensity_table = torch.from_numpy(augment_intensity.identity_rows(len(self))).to(self.device)
+            if self.elastic is not None:
+                self.elastic_table = torch.from_numpy(augment_elastic.identity_rows(len(self))).to(self.device)
+                self.elastic_ops = tuple(torch.from_numpy(op).to(self.device) for op in self.elastic_ops_host) + (self.elastic.spline_order,)
 
     def __len__(self):
         return int(self._idx.shape[0])
@@ -207,16 +226,34 @@ class DeviceSliceSet:
             return None
         return augment_intensity.identity_rows(n) if intensity is None else augment_intensity.checked_rows(intensity, n, f'DeviceSliceSet.{what}')
 
-    def load_epoch(self, items, augment=None, intensity=None):
+    def epoch_elastic(self, seed_or_generator=None, rows=None):
+        """The float64 [rows, 4] elastic table of one epoch (``rows``: ``len(self)`` when None), drawn by ``augment_elastic.elastic_rows`` from the
+        set's ``ElasticConfig``; call it after ``epoch_items``, ``epoch_augment`` and ``epoch_intensity`` on the same generator, as
+        ``train_epochs`` does."""
+        if self.elastic is None:
+            raise RuntimeError('DeviceSliceSet.epoch_elastic: this set was built without elastic=ElasticConfig(...)')
+        rng = seed_or_generator if isinstance(seed_or_generator, np.random.Generator) else np.random.default_rng(seed_or_generator)
+        return augment_elastic.elastic_rows(self.elastic, len(self) if rows is None else rows, rng)
+
+    def _checked_elastic(self, elastic, n, what):
+        """``_checked_augment`` for the elastic table."""
+        if self.elastic is None:
+            if elastic is not None:
+                raise RuntimeError(f'DeviceSliceSet.{what}: an elastic table for a set built without elastic=ElasticConfig(...)')
+            return None
+        return augment_elastic.identity_rows(n) if elastic is None else augment_elastic.checked_rows(elastic, n, f'DeviceSliceSet.{what}')
+
+    def load_epoch(self, items, augment=None, intensity=None, elastic=None):
         """Uploads the table into the persistent device table (rows past it are marked invalid) and puts the cursor back to row 0.  A set built
         with ``augment`` takes the epoch's parameter rows (``epoch_augment``) the same way, identity rows when none are given; one built with
-        ``intensity`` its intensity rows (``epoch_intensity``) likewise."""
+        ``intensity`` its intensity rows (``epoch_intensity``) likewise, one built with ``elastic`` its elastic rows (``epoch_elastic``)."""
         self._need_device('load_epoch')
         items = self._checked_items(items)
         if items.shape[0] > self.items.shape[0]:
             raise RuntimeError(f'DeviceSliceSet.load_epoch: {items.shape[0]} rows do not fit the device table of {self.items.shape[0]} (one per slice)')
         augment = self._checked_augment(augment, items.shape[0], 'load_epoch')
         intensity = self._checked_intensity(intensity, items.shape[0], 'load_epoch')
+        elastic = self._checked_elastic(elastic, items.shape[0], 'load_epoch')
         self.items[:items.shape[0]].copy_(torch.from_numpy(items), non_blocking=False)
         self.items[items.shape[0]:].fill_(-1)
         if augment is not None:
@@ -225,6 +262,9 @@ class DeviceSliceSet:
         if intensity is not None:
             self.intensity_table[:items.shape[0]].copy_(torch.from_numpy(intensity), non_blocking=False)
             self.intensity_table[items.shape[0]:].copy_(torch.from_numpy(augment_intensity.identity_rows(len(self) - items.shape[0])))
+        if elastic is not None:
+            self.elastic_table[:items.shape[0]].copy_(torch.from_numpy(elastic), non_blocking=False)
+            self.elastic_table[items.shape[0]:].copy_(torch.from_numpy(augment_elastic.identity_rows(len(self) - items.shape[0])))
         self.rows = int(items.shape[0])
         self.rewind()
 
@@ -243,9 +283,15 @@ class DeviceSliceSet:
         first, count = int(first), int(count)
         if not use_cursor and (count < 1 or first < 0 or first + count > self.rows):
             raise RuntimeError(f'DeviceSliceSet.batch: rows [{first}, {first + count}) are not inside the loaded epoch of {self.rows} (load_epoch first)')
+        more = {}
+        if self.elastic is not None:
+            need = elastic_workspace_bytes(count, self.slice_num, *self.patch_shape[1:], self.elastic.spline_order)
+            if self.elastic_workspace is None or self.elastic_workspace.numel() < need:   # a larger batch than any before: a new one; a graph keeps its own
+                self.elastic_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            more = dict(elastic=self.elastic_table, elastic_ops=self.elastic_ops, workspace=self.elastic_workspace)
         return assemble_batch(self.pool, self.vols, self.items, first, count, self.patch_shape[1:], slice_num=self.slice_num, min_value=self.min_value,
                               max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None, augment=self.augment_table,
-                              intensity=self.intensity_table, independent_planes=self.intensity is not None and self.intensity.independent_planes)
+                              intensity=self.intensity_table, independent_planes=self.intensity is not None and self.intensity.independent_planes, **more)
 
     def batches(self, batch_size, drop_last=False, dtype=torch.float32):
         """The loaded epoch batch by batch; the last batch is partial unless ``drop_last``, as the reference's loader leaves it."""
@@ -267,12 +313,14 @@ class DeviceSliceSet:
                                             for p, v in self.volumes[subject].items()}
         return self._host_rescaled[subject]
 
-    def host_batch(self, items, first, count, device=None, augment=None, intensity=None):
+    def host_batch(self, items, first, count, device=None, augment=None, intensity=None, elastic=None):
         """The same batch through ``SliceDataset(phase='train', thickness=[t])`` items, stacked and uploaded: the comparison arm of tests and
         benchmark.  ``augment``: the parameter table that goes with ``items`` (a set built with ``augment`` only); ``augment.apply_host`` applies
         row ``first + j`` to ``A`` and ``B`` of item ``first + j``.  ``intensity``: the intensity table that goes with ``items`` (a set built with
-        ``intensity`` only), applied after it by ``augment_intensity.apply_host``.  A row the kernel would refuse raises here."""
+        ``intensity`` only), applied after it by ``augment_intensity.apply_host``.  ``elastic``: the elastic table that goes with ``items`` (a set
+        built with ``elastic`` only), applied between the two by ``augment_elastic.apply_host``.  A row the kernel would refuse raises here."""
         items = self._checked_items(items)
+        elastic = None if elastic is None else self._checked_elastic(elastic, items.shape[0], 'host_batch')
         augment = None if augment is None else self._checked_augment(augment, items.shape[0], 'host_batch')
         intensity = None if intensity is None else self._checked_intensity(intensity, items.shape[0], 'host_batch')
         m = len(self.paths)
@@ -293,6 +341,9 @@ class DeviceSliceSet:
             item = ds[idx]
             if augment is not None:
                 item['A'], item['B'] = apply_host(item['A'], augment[first + j]), apply_host(item['B'], augment[first + j])
+            if elastic is not None:                                                      # all planes of the item, the target included: one deformation
+                both = augment_elastic.apply_host(torch.cat([item['A'], item['B']]), elastic[first + j], self.elastic, self.elastic_ops_host)
+                item['A'], item['B'] = both[:-1], both[-1:]
             if intensity is not None:
                 independent = self.intensity.independent_planes
                 item['A'] = augment_intensity.apply_host(item['A'], intensity[first + j], independent, 0)
@@ -323,15 +374,15 @@ def _fed_step(step, schedule, batch_size, batch, gen_z, cur_nimg=None):
 
 
 def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None, augment=None,
-                intensity=None):
+                intensity=None, elastic=None):
     """The inner loop of the reference's train.py:45-77 over the epoch table ``items`` (``DeviceSliceSet.epoch_items``): per batch
     ``total_iters += batch_size``, ``step.set_input(A, B, gen_c=slice_idx)``, ``step.optimize_parameters(cur_nimg=total_iters)`` and, when the step
     has an EMA copy and ``ema_kimgs`` is given, ``step.update_ema(batch_size, total_iters, ema_kimgs, ramp)``.  The last batch is partial, as the
     reference's loader leaves it.  ``where='device'``: the batches come from ``afcm_batch_assemble``, nothing is read back from the device;
     ``where='host'``: from ``SliceDataset`` items (``DeviceSliceSet.host_batch``), the same bits.  Both arms draw ``gen_z`` in the same order
     (``gen_z``: a fixed [batch_size, z_dim] tensor instead of a draw per batch).  ``augment``: the epoch's parameter table
-    (``DeviceSliceSet.epoch_augment``) for a set built with ``augment``, ``intensity``: the epoch's intensity table (``epoch_intensity``) for one built with ``intensity``; both arms
-    apply them.  Works with ``StyleGAN3GeneratorStep`` and
+    (``DeviceSliceSet.epoch_augment``) for a set built with ``augment``, ``intensity``: the epoch's intensity table (``epoch_intensity``) for one built with ``intensity``, ``elastic``: the epoch's elastic table
+    (``epoch_elastic``) for one built with ``elastic`` (the host arm is ``augment_elastic.apply_host``); both arms apply them.  Works with ``StyleGAN3GeneratorStep`` and
     ``StyleGAN3Step`` alike.
     Returns the new ``total_iters``."""
     if where not in ('device', 'host'):
@@ -344,13 +395,14 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     device = next(step.netG.parameters()).device
     augment = dataset._checked_augment(augment, n, 'train_epoch')
     intensity = dataset._checked_intensity(intensity, n, 'train_epoch')
+    elastic = dataset._checked_elastic(elastic, n, 'train_epoch')
     if where == 'device':
-        dataset.load_epoch(items, augment, intensity)
+        dataset.load_epoch(items, augment, intensity, elastic)
     schedule = getattr(step, 'schedule', None) if where == 'device' else None
     for first in range(0, n, batch_size):
         count = min(batch_size, n - first)
         batch = (lambda: dataset.batch(first, count)) if where == 'device' else (
-            lambda: dataset.host_batch(items, first, count, device=device, augment=augment, intensity=intensity))
+            lambda: dataset.host_batch(items, first, count, device=device, augment=augment, intensity=intensity, elastic=elastic))
         total_iters += batch_size
         _fed_step(step, schedule, batch_size, batch, None if gen_z is None else gen_z[:count], cur_nimg=total_iters)
         if schedule is None and ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
@@ -374,7 +426,9 @@ class TrainingGraph:
     back as well (in place: the graph keeps pointing at them), so that the warm-up's real steps leave no trace; the default keeps them, as
     ``capture_step`` does.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None.  A dataset built with ``augment``
     is captured with ``afcm_batch_assemble_aug``: the parameter table is persistent as the item table is, and the cursor moves through both; one built with
-    ``intensity`` with ``afcm_batch_assemble_noise``, its table persistent in the same way."""
+    ``intensity`` with ``afcm_batch_assemble_noise``, its table persistent in the same way; one built with ``elastic`` with the launches of
+    ``afcm_batch_assemble_elastic`` -- a fixed number, each skipping on the device the items whose flag is 0 -- and the graph keeps the workspace
+    it was captured with."""
 
     def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None, undo_warmup=False):
         require_capturable(step, 'TrainingGraph')
@@ -423,9 +477,10 @@ class TrainingGraph:
                     opt.restore(state)
 
         self.graph = capture_graph(lambda: _fed_step(step, schedule, batch_size, cursor_batch, self.gen_z), warmup, next_rows, leave_no_trace)
+        self.elastic_workspace = dataset.elastic_workspace    # the captured launches point into it, whatever the set allocates later
 
-    def load_epoch(self, items, augment=None, intensity=None):
-        self.dataset.load_epoch(items, augment, intensity)
+    def load_epoch(self, items, augment=None, intensity=None, elastic=None):
+        self.dataset.load_epoch(items, augment, intensity, elastic)
 
     def rewind(self):
         self.dataset.rewind()
@@ -444,7 +499,7 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
     """The outer loop of the reference's train.py:38-45 for a step built with a ``DeviceSchedule``.  ``epochs``: an iterable of epoch numbers
     (``range(epoch_count, n_epochs + n_epochs_decay + 1)``).  Per epoch: ``step.set_lr(lr_schedule.lr_at(k))`` for G and D, k = 1 for the first
     (``update_learning_rate()`` at the top of every epoch); ``dataset.epoch_items(rng)``, for a set built with ``augment`` ``epoch_augment(rng)``
-    right after it, for one built with ``intensity`` ``epoch_intensity(rng)`` after that, and ``load_epoch``; then replays of ONE ``TrainingGraph``
+    right after it, for one built with ``intensity`` ``epoch_intensity(rng)`` after that, for one built with ``elastic`` ``epoch_elastic(rng)`` last, and ``load_epoch``; then replays of ONE ``TrainingGraph``
     built in the first epoch (``graph=False``: eager steps, the same kernels) until fewer than ``batch_size`` rows remain; ``on_epoch(epoch, step)``
     -- validation and checkpoints are the caller's, through ``validation.validate`` and ``step.save_networks``.  ``rng``: a seed or a
     ``numpy.random.Generator``; an int seeds one generator for the whole run.  ``gen_z``: one fixed [batch_size, z_dim] latent batch for every step
@@ -463,7 +518,8 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
         step.set_lr(lr, lr)
         items = dataset.epoch_items(rng)
         augment = dataset.epoch_augment(rng) if dataset.augment is not None else None
-        dataset.load_epoch(items, augment, dataset.epoch_intensity(rng) if dataset.intensity is not None else None)
+        intensity = dataset.epoch_intensity(rng) if dataset.intensity is not None else None
+        dataset.load_epoch(items, augment, intensity, dataset.epoch_elastic(rng) if dataset.elastic is not None else None)
         if dataset.rows < batch_size:
             raise RuntimeError(f'train_epochs: an epoch of {dataset.rows} rows is shorter than a batch of {batch_size}')
         if graph and runner is None:

@@ -707,6 +707,55 @@ int afcm_batch_assemble_noise(void* a, void* b, float* slice_idx, const void* po
                               int32_t out_dtype, double min_value, double max_value, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Training batches with an elastic deformation: the reference's ElasticDeformation (data/augment/transforms.py:138-191; configs/defaults.py:77-79,
+ * spline_order 3, alpha 2000, sigma 50, execution_probability 0.1) on every [1, h, w] plane of the item, the target included, all planes with one
+ * deformation (the reference's equally seeded per-plane transformers).  With depth 1 the z displacement has no effect, so the statement is 2-D.
+ * Position in the chain: after the geometric transforms (augment, may be null), before the intensity transforms (intensity, may be null).  The
+ * reference lists ElasticDeformation after RandomRotate and before the noise transforms; RandomContrast is not in defaults.py, and this project places
+ * it AFTER the deformation -- its clip to [-1, 1] does not commute with the overshoot of a cubic spline.
+ * elastic: DEVICE float64 [n_items][4], row r of sample i the same r as the item row: (flag, alpha, key_lo, key_hi).
+ * smooth_h [h][h], smooth_w [w][w]: DEVICE float64, the Gaussian filter of the reference folded over its 'reflect' boundary by the HOST
+ * (afcm_amd/augment_elastic.py: smoothing_operator); the kernels evaluate no exponential.
+ * p: the float32 plane the launch without the elastic and intensity tables produces.  All arithmetic is float64, every operation rounded on its own:
+ *   fields   Fy, Fx [h][w]: the Box-Muller normals of afcm_batch_assemble_noise from Philox(counter (x >> 2, y, 0, 1) for Fy, (x >> 2, y, 0, 2) for
+ *            Fx, key (key_lo, key_hi)), lane x & 3.  Counter word 3 is 0 in the intensity streams, so the fields collide with neither.
+ *   smooth   T[i][x] = sum over m = 0 ... h - 1 ascending of smooth_h[i][m] * Fy[m][x]; S[y][j] = sum over m = 0 ... w - 1 ascending of
+ *            T[y][m] * smooth_w[j][m]; each sum starts at +0.0 and is acc = acc + product.  dy = alpha * S; dx likewise from Fx.
+ *   coords   cy = (double)y + dy[y][x], cx = (double)x + dx[y][x].  A coordinate that fails |c| <= 2^30 (a NaN fails) reads nothing: the pixel is
+ *            NaN.  The test comes before any conversion to an integer.
+ *   order 0  p[reflect(floor(cy + 0.5), h)][reflect(floor(cx + 0.5), w)], reflect as in afcm_batch_assemble_aug.
+ *   order 1  f = floor(c), t = c - f, weights (1 - t, t) at reflect(f), reflect(f + 1).
+ *   order 3  f = floor(c), t = c - f, u = 1 - t, weights ((u u) u) / 6, (((t t)(t - 2)) 3 + 4) / 6, (((u u)(u - 2)) 3 + 4) / 6, ((t t) t) / 6 at
+ *            reflect(f - 1 + l), l = 0 ... 3, on the coefficient plane C instead of p.
+ *   sum      per tap row a: r_a = wx_0 v_0, then r_a = r_a + wx_l v_l for l ascending; out = wy_0 r_0, then out = out + wy_a r_a for a ascending.
+ *   C        the cubic B-spline coefficients with the half-sample symmetric boundary, along y (every column), then along x (every row).  For a
+ *            line q[0 ... n) and z = -0.2679491924311227 (sqrt(3) - 2):  s = q[reflect(-40)]; s = q[reflect(-k)] + z * s for k = 39 ... 1;
+ *            c+[0] = q[0] + z * s; c+[k] = q[k] + z * c+[k - 1];  c[n - 1] = (z / (z - 1)) * c+[n - 1]; c[k] = z * (c[k + 1] - c+[k]) for
+ *            k = n - 2 ... 0; the line becomes c[k] * 6.  This is the exact interpolating spline at every length (scipy's own 'reflect'
+ *            prefilter is not below about n = 16; from there the two agree to rounding).
+ * The result is rounded once to float32; the intensity transforms, where a table is given, then act on that float32 value as
+ * afcm_batch_assemble_noise states; then one rounding to out_dtype.  The reference interpolates the float64 plane BEFORE its float32 cast; here
+ * the float32 item is widened back: a deformed pixel may differ from the reference's arithmetic by one float32 unit in the last place.
+ * IEEE + - x / sqrt floor only, so afcm_amd/augment_elastic.py evaluates the same operations in numpy and gets the same bits.  No atomics.
+ * A row is valid when flag is 0 or 1, alpha is finite with |alpha| <= 2^20, key_lo and key_hi are whole numbers in [0, 2^32 - 1].  An item with an
+ * invalid row of any table reads nothing from the pool and is NaN throughout, label included.  An item whose flag is 0 has the bits of the launch
+ * without the table, and every launch below skips it.
+ * Launches on `stream`, a fixed number per call whatever the flags are (afcm_elastic_plan: 6, or 8 with order 3), no allocation, no synchronise:
+ * the item rows' check, the float32 item into the workspace (afcm_batch_assemble / _aug's kernel), the fields, the two smoothing passes (16 x 64
+ * output tiles, operator rows staged in LDS), the two prefilter passes (order 3; one lane per line, rows through an LDS transpose), the gather.
+ * workspace: DEVICE, on a multiple of 256 bytes, at least the workspace_bytes afcm_elastic_plan gives for (count, k, h, w, order); no
+ * initialisation needed, nothing is kept between calls.
+ * AFCM_E_INVALID as afcm_batch_assemble_noise (augment and intensity may each be null); also a null elastic, operator or workspace, a workspace
+ * that is too small or misaligned, an order outside {0, 1, 3}, count above 32767, h or w above 32768.
+ * ---------------------------------------------------------------------------------------- */
+int afcm_elastic_plan(int32_t count, int32_t k, int32_t h, int32_t w, int32_t order, int64_t* workspace_bytes, int32_t* launches);
+int afcm_batch_assemble_elastic(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                                int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment, const double* intensity,
+                                int32_t independent_planes, const double* elastic, const double* smooth_h, const double* smooth_w,
+                                int32_t spline_order, void* workspace, int64_t workspace_bytes, const int64_t* cursor, int32_t first, int32_t count,
+                                int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * The training loop's time-dependent scalars on the device (r11), so that ONE captured graph stays right for a whole run.
  * The schedule block is a DEVICE array of 8 doubles:
  *   [0] total_iters  images seen: the reference's total_iters / cur_nimg (train.py:50-53), exact in a double

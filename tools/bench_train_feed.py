@@ -6,6 +6,8 @@ against the fixed-input one.  Two steps, each its own process (run each under it
     python tools/bench_train_feed.py feed --augment        # afcm_batch_assemble_aug (identity and random rows) beside the plain launch; the host arm
     python tools/bench_train_feed.py feed --intensity      # afcm_batch_assemble_noise (identity rows, each transform, all three, the reference's
                                                            # probabilities) beside the plain and the augmented launch; the host arm
+    python tools/bench_train_feed.py feed --elastic        # afcm_batch_assemble_elastic (no item, every item, the reference's probability 0.1;
+                                                           # orders 3, 1, 0) beside the plain launch; the host arm
 
 (a) alternates ``DeviceSliceSet.host_batch`` (SliceDataset items in numpy, stacked, uploaded) and ``DeviceSliceSet.batch`` (one launch) over the same
 rows of a synthetic uint8 set after a warm-up of each, the alternation repeated; wall time by a host clock ended by a synchronise.  (b) times
@@ -286,6 +288,90 @@ def feed_intensity(args):
     return 0 if equal else 1
 
 
+def feed_elastic(args):
+    """``feed --elastic``: the elastic launches (``afcm_batch_assemble_elastic``: 8 at order 3) beside the plain launch, device events over the
+    whole call, the arms alternated inside every repeat -- no item executing (the fixed cost: the scratch round trip and seven launches that exit
+    early), every item executing (orders 3, 1 and 0) and the reference's execution probability 0.1, with the reference's sigma 50 and alpha 2000;
+    and the host arm -- ``augment_elastic.apply_host`` -- by a host clock."""
+    import torch
+    from afcm_amd import _lib
+    import numpy as np
+    from afcm_amd.augment_elastic import ElasticConfig, elastic_rows, identity_rows
+    from afcm_amd.torch_utils.ops.batch_ops import elastic_workspace_bytes
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_train_feed.py needs a GPU: a time taken without one says nothing')
+    dev = torch.device('cuda:0')
+    ds = synthetic_set(args.subjects, args.depth, args.res, dev, elastic=ElasticConfig())
+    items = ds.epoch_items(0)
+    n = len(items)
+    every = elastic_rows(ElasticConfig(execution_probability=1.0), n, np.random.default_rng(1))
+    tables = {'elastic_none': identity_rows(n), 'elastic_every': every, 'elastic_reference_0.1': ds.epoch_elastic(2)}
+    tables = {name: torch.from_numpy(rows).to(dev) for name, rows in tables.items()}
+    ds.load_epoch(items, None, None, every)
+    batches = min(args.batches, n // args.batch)
+    lib, launches = _lib.load(), {}
+    op_h, op_w, _ = ds.elastic_ops
+    work = torch.empty(elastic_workspace_bytes(args.batch, 4, args.res, args.res, 3), dtype=torch.uint8, device=dev)
+    for out_name, out_dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
+        a = torch.empty((args.batch, 4, args.res, args.res), dtype=out_dtype, device=dev)
+        b = torch.empty((args.batch, 1, args.res, args.res), dtype=out_dtype, device=dev)
+        c = torch.empty((args.batch, 1), dtype=torch.float32, device=dev)
+        out_bytes = a.numel() * a.element_size() + b.numel() * b.element_size()
+        head = (a.data_ptr(), b.data_ptr(), c.data_ptr(), ds.pool.data_ptr(), ds.pool.numel(), _lib.SRC_U8, ds.vols.data_ptr(), int(ds.vols.shape[0]),
+                ds.items.data_ptr(), int(ds.items.shape[0]))
+        tail = (None, 0, args.batch, 4, args.res, args.res, _lib.dtype_code(a), 0., 255., _lib.stream_ptr(a))
+
+        def plain():
+            assert lib.afcm_batch_assemble(*head, *tail) == 0
+
+        def elastic(table, order):
+            def launch():
+                assert lib.afcm_batch_assemble_elastic(*head, None, None, 0, table.data_ptr(), op_h.data_ptr(), op_w.data_ptr(), order, work.data_ptr(),
+                                                       work.numel(), *tail) == 0
+            return launch
+
+        arms = dict({'plain': plain}, **{name: elastic(table, 3) for name, table in tables.items()})
+        arms['elastic_every_order1'], arms['elastic_every_order0'] = elastic(tables['elastic_every'], 1), elastic(tables['elastic_every'], 0)
+        us = {name: [] for name in arms}
+        for _ in range(args.repeats):
+            for name, fn in arms.items():
+                us[name].append(events_us(fn, launches=50))
+        for name, v in us.items():
+            launches[f'{name}_{out_name}'] = dict(per_repeat_us=v, mean_us=sum(v) / len(v), spread_us=spread(v),
+                                                  ns_per_kib=sum(v) / len(v) * 1e3 / (out_bytes / 1024))
+
+    def clock(rows):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for j in range(batches):
+            out = ds.host_batch(items, j * args.batch, args.batch, elastic=rows)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / batches, out
+
+    host = {'host_plain': None, 'host_every': every}
+    stats, last = {name: [] for name in host}, {}
+    for name, rows in host.items():
+        clock(rows)
+    for _ in range(args.repeats):
+        for name, rows in host.items():
+            ms, last[name] = clock(rows)
+            stats[name].append(ms)
+    device_last = ds.batch((batches - 1) * args.batch, args.batch)
+    equal = all(torch.equal(x, y) for x, y in zip(last['host_every'], device_last))
+    print(f'training batches of {args.batch} x (4 + 1) planes at {args.res}^2 from {args.subjects} uint8 subjects of ({args.depth}, {args.res}, {args.res}) with '
+          f'the elastic deformation, sigma 50, alpha 2000, order 3 unless named; {args.repeats} repeats, the arms alternated inside each')
+    for name, s in launches.items():
+        print(f'{name:30s} us per call {"  ".join(f"{x:8.2f}" for x in s["per_repeat_us"])}   mean {s["mean_us"]:8.2f}   spread {s["spread_us"]:.2f}   '
+              f'{s["ns_per_kib"]:.3f} ns per KiB of output')
+    arms = {}
+    for name, v in stats.items():
+        arms[name] = dict(per_repeat_ms=v, mean_ms=sum(v) / len(v), spread_ms=spread(v))
+        print(f'{name:30s} ms/batch per repeat {"  ".join(f"{x:8.3f}" for x in v)}   mean {arms[name]["mean_ms"]:8.3f}   spread {arms[name]["spread_ms"]:.3f}')
+    print(f'the host arm\'s and the device\'s last deformed batch are {"bit-identical" if equal else "DIFFERENT"}')
+    print(json.dumps(dict(bench='train_feed_elastic', res=args.res, batch=args.batch, launches=launches, arms=arms, equal=equal)))
+    return 0 if equal else 1
+
+
 def step(args):
     import torch
     from afcm_amd import layer_schedule as sched
@@ -354,12 +440,14 @@ def main():
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--augment', action='store_true', help='feed: time the augmented launch and the augmenting host arm instead')
     ap.add_argument('--intensity', action='store_true', help='feed: time the noise launch and its host arm instead')
+    ap.add_argument('--elastic', action='store_true', help='feed: time the elastic launches and their host arm instead')
     args = ap.parse_args()
-    if (args.augment or args.intensity) and args.what != 'feed':
-        raise SystemExit('--augment and --intensity belong to the feed step')
-    if args.augment and args.intensity:
-        raise SystemExit('--augment or --intensity, one at a time')
-    return {'feed': feed_intensity if args.intensity else (feed_augment if args.augment else feed), 'step': step}[args.what](args)
+    if (args.augment or args.intensity or args.elastic) and args.what != 'feed':
+        raise SystemExit('--augment, --intensity and --elastic belong to the feed step')
+    if args.augment + args.intensity + args.elastic > 1:
+        raise SystemExit('--augment, --intensity or --elastic, one at a time')
+    feeds = feed_elastic if args.elastic else (feed_intensity if args.intensity else (feed_augment if args.augment else feed))
+    return {'feed': feeds, 'step': step}[args.what](args)
 
 
 if __name__ == '__main__':
