@@ -288,7 +288,8 @@ int afcm_plane_dot_gated_ld(float* out, const void* a, const void* b, int32_t dt
  *                 d[n,o] = rsqrt(sum_i s_hat[n,i]^2 wsq[o,i] + 1e-8) (NET:50-52 factorised over the shared weights),
  *                 s_eff = s_hat * rsqrt(magnitude[0]) (input gain, NET:346,55-57; magnitude NULL: 1).
  *                 demodulate == 0 (ToRGB, NET:362): s_eff = t * gain only, d / wsq unused.
- *                 bwd: dt from g_s (dL/ds_eff) and g_d (dL/dd); g_wsq (may be NULL) = dL/dwsq.
+ *                 bwd: dt from g_s (dL/ds_eff, may be NULL) and g_d (dL/dd, may be NULL); NULL = zeros, both NULL: dt = 0.
+ *                 g_wsq (may be NULL: not computed, the buffer is not touched) = dL/dwsq.
  *                 workspace: n*cin + n*cout + n*ceil(cin/64) floats.
  * ---------------------------------------------------------------------------------------- */
 int afcm_weight_norm_fwd(float* w_hat, float* wsq, float* scale, const float* w, int32_t cout, int32_t cin, int32_t kk, void* stream);
