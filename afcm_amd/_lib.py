@@ -171,6 +171,9 @@ SIGNATURES = {
     'afcm_clip_normalize': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp]),
     'afcm_group_chunk_bytes': (C.c_int32, []),
     'afcm_group_expand': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    'afcm_trainlog_cols': (C.c_int32, []),
+    'afcm_grad_stats': (C.c_int, [_vp, _i32, _i64, _f32, _vp, _vp]),
+    'afcm_trainlog_append': (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
 
 

@@ -19,12 +19,25 @@ class FusedScrubAdam(torch.optim.Optimizer):
     """``g * grad_scale`` -> ``nan_to_num`` -> Adam, one launch per parameter group.  One step count per group (the largest in the group
     + 1; a parameter without a gradient is left alone).  ``capturable=True`` keeps that count on the device so that ``step()`` can be
     captured into a graph: replays advance the device count only, ``device_step()`` reads it, and ``state_dict()`` writes it into
-    ``state[p]['step']`` of the parameters the captured step updates, so a checkpoint taken after replays resumes at the right step."""
+    ``state[p]['step']`` of the parameters the captured step updates, so a checkpoint taken after replays resumes at the right step.
+    ``stats=True`` puts one ``afcm_grad_stats`` launch in front of every Adam launch: what the scrub is about to replace and the gradients' sum of
+    squares, per chunk, for ``grad_stats()`` and the training log (afcm_amd/trainlog.py)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, write_grad=False, capturable=False, lr_dev=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, write_grad=False, capturable=False, lr_dev=None,
+                 stats=False):
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
             raise ValueError('invalid Adam hyper-parameters')
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps))
+        # stats: every step() launches afcm_grad_stats (csrc/trainlog.hip) over the group's pointer table right before the Adam launch: per chunk the
+        # sum of squares of the finite scaled gradients and the counts of NaN / +inf / -inf the scrub is about to replace, into a persistent float64
+        # [chunks of ALL the group's parameters, 4] tensor made here (nothing is allocated during a capture).  False: nothing is launched or allocated
+        self.stats = bool(stats)
+        self._stats = {}           # group index -> [partials, chunks written by the last step, that step's count]
+        if self.stats:
+            chunk = _lib.load().afcm_adam_chunk_elems()
+            for gi, group in enumerate(self.param_groups):
+                rows = sum((p.numel() + chunk - 1) // chunk for p in group['params'])
+                self._stats[gi] = [torch.zeros((max(1, rows), 4), dtype=torch.float64, device=group['params'][0].device), 0, 0]
         self.scrub, self.posinf, self.neginf, self.write_grad = bool(scrub), float(posinf), float(neginf), bool(write_grad)
         self._tables = {}          # (group index, device) -> (rows, device table, pinned host copy)
         # capturable: the step count is a device scalar per group and the bias corrections are formed in the kernel (C ABI
@@ -125,6 +138,15 @@ class FusedScrubAdam(torch.optim.Optimizer):
                     table[:host.numel()].copy_(host, non_blocking=True)
                     self._tables[key] = ent = (rows, table, host)
             table = ent[1]
+            if self.stats:
+                # the same table, chunk count and scale as the Adam launch below, on the same stream, in front of it (it may write g back)
+                gs = self._stats.get(gi)
+                if gs is None or gs[0].device != dev or gs[0].shape[0] < chunks:
+                    raise RuntimeError('FusedScrubAdam(stats=True): the statistics tensor is made at construction from the parameters the group has '
+                                       'then, on their device; this group has changed since')
+                _lib.launched(lib.afcm_grad_stats(ctypes.c_void_p(table.data_ptr()), len(rows), chunks, float(grad_scale), ctypes.c_void_p(gs[0].data_ptr()),
+                                                  _lib.stream_ptr(table)), 'grad_stats')
+                gs[1], gs[2] = chunks, step_t
             if self.capturable:
                 sd = self._step_dev.get(key)
                 if sd is None:
@@ -183,17 +205,33 @@ class FusedScrubAdam(torch.optim.Optimizer):
     def snapshot(self):
         """Clones of the moments and step counts as they stand (parameters that have not stepped yet have none): for ``restore``."""
         moments = {p: {k: v.clone() for k, v in self.state[p].items()} for group in self.param_groups for p in group['params'] if p in self.state}
-        return moments, {key: t.clone() for key, t in self._step_dev.items()}
+        counts = {key: t.clone() for key, t in self._step_dev.items()}
+        if self.stats:                                       # with stats=True a third member: the statistics of the last step, as grad_stats() gives them
+            return moments, counts, {gi: [gs[0].clone(), gs[1], gs[2]] for gi, gs in self._stats.items()}
+        return moments, counts
 
     @torch.no_grad()
     def restore(self, snapshot):
         """Puts a ``snapshot`` back IN PLACE, so that pointer tables and a captured step stay valid; state made since the snapshot starts from zero."""
-        moments, counts = snapshot
+        moments, counts = snapshot[:2]
         for p, st in self.state.items():
             for k, v in st.items():
                 v.copy_(moments[p][k]) if p in moments else v.zero_()
         for key, t in self._step_dev.items():
             t.copy_(counts[key]) if key in counts else t.zero_()
+        if self.stats and len(snapshot) > 2:
+            for gi, (partials, chunks, count) in snapshot[2].items():
+                self._stats[gi][0].copy_(partials)
+                self._stats[gi][1:] = [chunks, count]
+
+    def grad_stats(self, group=0):
+        """``(partials, chunks)`` of the last step of a ``stats=True`` optimizer: the persistent float64 [*, 4] device tensor of per-chunk rows
+        ``{sumsq, n_nan, n_posinf, n_neginf}`` (C ABI ``afcm_grad_stats``) and how many of its rows that step wrote -- the chunks of the parameters
+        that had a gradient, in table order; 0 before the first step.  A replayed graph rewrites the rows of the step it captured."""
+        if not self.stats:
+            raise RuntimeError('FusedScrubAdam.grad_stats: this optimizer was built without stats=True')
+        gs = self._stats[group]
+        return gs[0], gs[1]
 
     def device_step(self, group=0):
         """The step count of a capturable optimizer (a device scalar; reading it synchronises)."""

@@ -28,8 +28,14 @@ from .optim import FusedScrubAdam, weighted_l1
 
 class StyleGAN3GeneratorStep:
     def __init__(self, netG, lr_G=0.0025, lambda_L1=100.0, distributed=False, bucket_bytes=25 * 1024 * 1024, style_mixing_prob=0,
-                 force_collectives=False, blur_init_sigma=0.0, blur_fade_kimg=0.0, ema=False, comm_dtype=None, eval_dtype='auto', capturable=False, schedule=None):
+                 force_collectives=False, blur_init_sigma=0.0, blur_fade_kimg=0.0, ema=False, comm_dtype=None, eval_dtype='auto', capturable=False, schedule=None, log=None):
         self.netG = netG
+        # `log`: a DeviceTrainLog (afcm_amd/trainlog.py).  The optimizers are then built with stats=True (one afcm_grad_stats launch in front of each Adam
+        # launch) and optimize_parameters() ends with ONE log.append(self): the step's losses, the schedule block, the step counts and what the scrub
+        # is replacing, as a row in device memory -- in eager steps and in every replay of a captured one.  None: the step launches what it always did
+        self.log = log
+        if log is not None and log.device != next(netG.parameters()).device:
+            raise RuntimeError(f'the log lives on {log.device}, the step on {next(netG.parameters()).device}: a step appends to a log on its own device')
         # `schedule`: a DeviceSchedule (afcm_amd/schedule.py).  The blur sigma, the EMA beta and the learning rates then live in its device block: _blur
         # is gauss_blur(img, schedule=...), the optimizers read their rate from the block, optimize_parameters() ignores cur_nimg (the caller advances
         # the schedule once per step) and update_ema() without arguments is one launch -- a captured step stays right while all three change
@@ -61,7 +67,7 @@ class StyleGAN3GeneratorStep:
         # nan_to_num of every gradient + Adam(betas=(0, 0.99)) (stylegan3_model.py:132-135, comodgan_model.py:19-20) as one HIP launch
         # (capturable: step count and bias corrections on the device, so that optimize_parameters() can be captured into a hipGraph: capture_step())
         self.optimizer_G = FusedScrubAdam(netG.parameters(), lr=lr_G, betas=(0.0, 0.99), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5, capturable=capturable,
-                                          lr_dev=None if schedule is None else schedule.lr_G_dev)
+                                          lr_dev=None if schedule is None else schedule.lr_G_dev, stats=log is not None)
         self.criterionL1 = torch.nn.L1Loss()
         self.lambda_L1 = lambda_L1
         self.style_mixing_prob = style_mixing_prob
@@ -189,7 +195,8 @@ class StyleGAN3GeneratorStep:
 
     def optimize_parameters(self, cur_nimg=None):
         """G half of models/stylegan3_model.py:113-135.  `cur_nimg` drives the blur fade as in the reference (:115-116);
-        None keeps the current blur_sigma.  A step with a schedule ignores it: sigma is the schedule block's."""
+        None keeps the current blur_sigma.  A step with a schedule ignores it: sigma is the schedule block's.  A step with a log ends with one
+        ``log.append(self)``."""
         if cur_nimg is not None and self.schedule is None:
             self.blur_sigma = (max(1 - cur_nimg / (self.blur_fade_kimg * 1e3), 0) * self.blur_init_sigma) if self.blur_fade_kimg > 0 else 0.0
         ev = getattr(self, 'phase_events', None)      # a dict: record CUDA events at the phase boundaries of THIS step (bench.py's bucket timeline)
@@ -204,6 +211,8 @@ class StyleGAN3GeneratorStep:
         # averaging (1 / world), the NaN/Inf scrub and the Adam update all happen inside the optimizer kernel; with buckets the
         # reduced gradients are read where the all-reduce left them
         self.optimizer_G.step(grads=grads, grad_scale=scale)
+        if self.log is not None:                      # (StyleGAN3Step's D half runs before this method: one row per iteration, after both updates)
+            self.log.append(self)
         mark('end')
 
 
@@ -292,7 +301,7 @@ class StyleGAN3Step(StyleGAN3GeneratorStep):
         self.combine_ab = bool(combine_ab)
         self.optimizer_D = FusedScrubAdam(netD.parameters(), lr=lr_D, betas=(0.0, 0.99), eps=1e-8, scrub=True, posinf=1e5, neginf=-1e5,
                                           capturable=kw.get('capturable', False),
-                                          lr_dev=None if kw.get('schedule') is None else kw['schedule'].lr_D_dev)
+                                          lr_dev=None if kw.get('schedule') is None else kw['schedule'].lr_D_dev, stats=self.log is not None)
         self.buckets_D = None
         if self.buckets is not None:
             self.buckets_D = GradientBuckets(netD.parameters(), bucket_bytes=kw.get('bucket_bytes', 25 * 1024 * 1024),

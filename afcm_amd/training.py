@@ -424,7 +424,8 @@ class TrainingGraph:
     and the schedule an ``ema_kimgs``, ends with ``step.update_ema()``; sigma, beta and the learning rates are read from the schedule block at every
     replay, and the warm-up leaves the block as it found it.  ``undo_warmup=True`` puts the networks' parameters and buffers and the optimizers' state
     back as well (in place: the graph keeps pointing at them), so that the warm-up's real steps leave no trace; the default keeps them, as
-    ``capture_step`` does.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None.  A dataset built with ``augment``
+    ``capture_step`` does.  A step built with ``log=DeviceTrainLog(...)`` appends a row in every warm-up step and in every replay; the warm-up always puts
+    the log's ``head`` back, and with ``undo_warmup=True`` the ring's contents and the optimizers' gradient statistics as well.  ``gen_z``: the initial (with ``fixed_z``: the only) latent batch; drawn when None.  A dataset built with ``augment``
     is captured with ``afcm_batch_assemble_aug``: the parameter table is persistent as the item table is, and the cursor moves through both; one built with
     ``intensity`` with ``afcm_batch_assemble_noise``, its table persistent in the same way; one built with ``elastic`` with the launches of
     ``afcm_batch_assemble_elastic`` -- a fixed number, each skipping on the device the items whose flag is 0 -- and the graph keeps the workspace
@@ -449,6 +450,8 @@ class TrainingGraph:
         schedule = getattr(step, 'schedule', None)
         saved = None if schedule is None else schedule.block.clone()
         optimizers = [opt for opt in (step.optimizer_G, getattr(step, 'optimizer_D', None)) if opt is not None]
+        log = getattr(step, 'log', None)
+        logged = None if log is None else log.snapshot()
         if undo_warmup:
             tensors = [t for name in step.model_names for net in [getattr(step, 'net' + name)] for t in list(net.parameters()) + list(net.buffers())]
             before = [t.detach().clone() for t in tensors], [opt.snapshot() for opt in optimizers]
@@ -469,6 +472,8 @@ class TrainingGraph:
             dataset.rewind()
             if saved is not None:
                 schedule.block.copy_(saved)               # the warm-up's steps are real ones, but total_iters stays where it was
+            if log is not None:                           # the warm-up's rows stay in the ring unless it is undone; the serials go on from where they were
+                log.restore(logged, head_only=not undo_warmup)
             if undo_warmup:
                 with torch.no_grad():
                     for t, v in zip(tensors, before[0]):
@@ -504,7 +509,8 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
     -- validation and checkpoints are the caller's, through ``validation.validate`` and ``step.save_networks``.  ``rng``: a seed or a
     ``numpy.random.Generator``; an int seeds one generator for the whole run.  ``gen_z``: one fixed [batch_size, z_dim] latent batch for every step
     instead of a draw per step.  The graph is built with ``undo_warmup=True``, so the run is the same steps on the same rows with and
-    without the graph.  Returns the number of steps run."""
+    without the graph.  A step built with ``log=DeviceTrainLog(...)`` leaves one row per step in device memory, the same rows with and without the graph;
+    nothing here reads them: ``step.log.read()`` inside ``on_epoch`` is one device -> host copy per epoch.  Returns the number of steps run."""
     schedule = getattr(step, 'schedule', None)
     if schedule is None:
         raise RuntimeError('train_epochs needs a step built with schedule=DeviceSchedule(...)')

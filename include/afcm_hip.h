@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AFCM_ABI_VERSION 13  /* 13: + afcm_rescale_intensity, afcm_rescale_workspace_bytes, afcm_rescale_plan (intensity rescaling; additions only, so the number stays).  13: + afcm_volume_ssim, afcm_volume_ssim_workspace_bytes (the 7^3-window SSIM map's layer sums; additions only, so the number stays).  13: + afcm_slice_assemble, afcm_halo_accumulate (whole-volume inference; additions only, so the number stays).  13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
+#define AFCM_ABI_VERSION 13  /* 13: + afcm_grad_stats, afcm_trainlog_append, afcm_trainlog_cols (the training log on the device, end of this header; additions to v13: no existing entry point or struct changes, so the number stays).  13: + afcm_rescale_intensity, afcm_rescale_workspace_bytes, afcm_rescale_plan (intensity rescaling; additions only, so the number stays).  13: + afcm_volume_ssim, afcm_volume_ssim_workspace_bytes (the 7^3-window SSIM map's layer sums; additions only, so the number stays).  13: + afcm_slice_assemble, afcm_halo_accumulate (whole-volume inference; additions only, so the number stays).  13: + afcm_adam_multi_capturable_d (an addition only, so the number stays).  13 (r08): + afcm_conv2d_plan, afcm_conv2d_wgrad_plan (pure-host queries of the dispatch; additions only, so the number stays).  13 (r07): + afcm_plane_metrics, afcm_plane_metrics_workspace_bytes (additions only: no existing entry point or struct changes, so the number stays).  13 (r06): + afcm_noop, afcm_pool_blocks_fwd / _bwd, afcm_adam_multi_capturable, afcm_conv2d_wgrad_dots_ld, afcm_mapping_input_bwd_workspace_bytes, afcm_axpy_planes, afcm_l1_partials, afcm_l1_grad, afcm_fc_act_fwd / _bwd, afcm_mapping_input_fwd / _bwd (additions only; see the end of this header for the r06 entry points).  12 (r05): + afcm_conv2d_block_k_ks, afcm_conv2d_pack_weights_bk; the packed layout's K-chunk depends on (dtype, kernel size): 16-bit 3x3 images are [nkc][9][rows_pad][32] for the v_mfma 16x16x32 kernel (the pack / conv entry points keep their signatures).  11 (r04): + afcm_amax_bits, afcm_split16, afcm_conv2d_pack_split, afcm_conv2d_split, afcm_unscale, afcm_plane_dot_parts (additions only).  10 (r04): + afcm_filtered_lrelu_args.clamp_flags (appended), afcm_plane_dot_gated_ld; the runtime getenv switches are gone.  9 (r03): + afcm_affine_bank_*, afcm_modulation_bank_*, afcm_conv2d_pack_bank, afcm_conv2d_stride2 (additions only; every v8 entry point and struct is unchanged) */
 
 enum { AFCM_F32 = 0, AFCM_F16 = 1, AFCM_BF16 = 2 };
 enum { AFCM_OK = 0, AFCM_E_NOKERNEL = -1, AFCM_E_INVALID = -2 };
@@ -902,6 +902,38 @@ typedef struct afcm_group_entry {
 int32_t afcm_group_chunk_bytes(void);
 int afcm_group_expand(const afcm_group_entry* table_dev, const afcm_group_entry* table_host, int32_t n, int32_t batch, const int32_t* groups,
                       void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * The training log on the device (additions to v13): one row of doubles per training step in a ring in DEVICE memory, written by one short launch
+ * inside the step, so that a replayed graph can be read once per epoch -- the reference's get_current_losses() (train.py; models/pix2pix_model.py:75
+ * names G_GAN, G_L1, D_real, D_fake; Dr1 sits beside them) plus what afcm_adam_multi's scrub replaced without saying so.
+ *
+ * afcm_grad_stats: over afcm_adam_multi's DEVICE pointer table (same n, total_chunks and grad_scale as the Adam launch it precedes), one 256-thread
+ * workgroup per chunk of afcm_adam_chunk_elems() elements.  It reads g only and writes partials[chunk][0..3] (DEVICE doubles, total_chunks rows):
+ *   { sumsq, n_nan, n_posinf, n_neginf }   of gr = g * grad_scale formed in float32 as the Adam kernel forms it (a finite g that overflows under
+ *   grad_scale counts as infinite); sumsq adds (double)gr * (double)gr of every FINITE gr (the product is exact).
+ * Order of sumsq: thread t adds its elements in ascending index from +0.0 -- elements 4 t + 1024 k + {0, 1, 2, 3} of the chunk where g is 16-byte
+ * aligned, t + 256 k where it is not (the Adam kernel's two paths, decided by g alone here) --, then one tree over the 256 threads:
+ * s[t] += s[t + o] for o = 128, 64, ..., 1.  No atomics: bit-identical from launch to launch.
+ * AFCM_E_INVALID: an empty table, total_chunks outside [1, 2^31), a null or misaligned partials.
+ *
+ * afcm_trainlog_append: one workgroup.  Each of the four columns of partials_G[chunks_G][4] and partials_D[chunks_D][4] is summed over the chunks --
+ * thread t adds rows t, t + 256, ... in ascending order from +0.0, then the same tree -- and ONE row of AFCM_TRAINLOG_COLS doubles is written at
+ * log[(head % capacity) * AFCM_TRAINLOG_COLS], then head[0] += 1 (one lane, a plain store; head is a DEVICE int64 that starts at 0):
+ *   [0]      serial: head before the append
+ *   [1..8]   the schedule block's 8 slots as they stand (total_iters, blur_sigma, blur_radius, ema_beta, lr_G, lr_D, two spare)
+ *   [9] [10] Adam step counts of G and D (step_G[0], step_D[0]: the capturable optimizers' device floats)
+ *   [11..15] G_GAN, G_L1, D_real, D_fake, Dr1 from losses[5] (float32; a NaN there means absent)
+ *   [16..19] G: sumsq, NaN count, +inf count, -inf count      [20..23] D: the same four
+ * A NULL pointer among block, step_G, step_D, losses, partials_G, partials_D means absent: its columns are NaN.
+ * Both launches go to `stream`; no stream, event, allocation or synchronise: capturable, and the captured graph stays one chain.
+ * AFCM_E_INVALID: a null log or head, capacity < 1, a negative chunk count.
+ * ---------------------------------------------------------------------------------------- */
+#define AFCM_TRAINLOG_COLS 24
+int32_t afcm_trainlog_cols(void);
+int afcm_grad_stats(const afcm_adam_entry* table, int32_t n, int64_t total_chunks, float grad_scale, double* partials, void* stream);
+int afcm_trainlog_append(double* log, int32_t capacity, int64_t* head, const double* block, const float* step_G, const float* step_D,
+                         const float* losses, const double* partials_G, int64_t chunks_G, const double* partials_D, int64_t chunks_D, void* stream);
 
 #ifdef __cplusplus
 }
