@@ -157,6 +157,10 @@ SIGNATURES = {
     'afcm_elastic_plan': (C.c_int, [_i32] * 5 + [C.POINTER(_i64), C.POINTER(_i32)]),
     'afcm_batch_assemble_elastic': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp] +
                                     [_i32] * 6 + [_f64, _f64, _vp]),
+    'afcm_blur_plan': (C.c_int, [_i32] * 5 + [C.POINTER(_i64), C.POINTER(_i32)]),
+    'afcm_blur_tiles': (None, [C.POINTER(_i32)] * 4),
+    'afcm_batch_assemble_blur': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp] +
+                                 [_i32] * 6 + [_f64, _f64, _vp]),
     'afcm_cursor_advance': (C.c_int, [_vp, _i64, _vp]),
     'afcm_schedule_advance': (C.c_int, [_vp, _i64, _f64, _f64, _f64, _f64, _vp]),
     'afcm_gauss_blur_rmax': (C.c_int32, []),

@@ -1,4 +1,4 @@
-// What the training-batch kernels share (batch.hip: the one-launch batch; elastic.hip: the batch with an elastic deformation, several launches): the
+// What the training-batch kernels share (batch.hip: the one-launch batch; elastic.hip and augment_blur.hip: the batch with an elastic deformation / a Gaussian blur, several launches): the
 // item row and its checks, the geometric and the intensity parameter rows, scipy's integer 'reflect', Philox4x32-10 with the normals made from it,
 // and the intensity transforms on one run of pixels.  See include/afcm_hip.h for the semantics kept.
 #pragma once
@@ -228,5 +228,13 @@ int launch_batch(void* a, void* b, float* slice_idx, const void* pool, int64_t p
                  const int32_t* items, int32_t n_items, const double* augment, const double* intensity, int32_t independent_planes,
                  const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value,
                  double max_value, void* stream);
+
+// elastic.hip: the launches of afcm_batch_assemble_elastic; augment_blur.hip has them write the deformed float32 item into its scratch
+// (apply_intensity false: the gather leaves the intensity transforms to the stage after it)
+int launch_elastic(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols, int32_t n_vols,
+                   const int32_t* items, int32_t n_items, const double* augment, const double* intensity, int32_t independent_planes,
+                   const double* elastic, const double* smooth_h, const double* smooth_w, int32_t spline_order, void* workspace,
+                   int64_t workspace_bytes, const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype,
+                   double min_value, double max_value, void* stream, bool apply_intensity);
 
 }  // namespace afcm

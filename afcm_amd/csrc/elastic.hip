@@ -325,24 +325,13 @@ static int check_geometry(int32_t count, int32_t k, int32_t h, int32_t w, int32_
     return AFCM_OK;
 }
 
-}  // namespace afcm
-
-extern "C" int afcm_elastic_plan(int32_t count, int32_t k, int32_t h, int32_t w, int32_t order, int64_t* workspace_bytes, int32_t* launches) {
-    using namespace afcm;
-    AFCM_REQUIRE(workspace_bytes != nullptr, "elastic_plan: null workspace_bytes");
-    if (const int rc = check_geometry(count, k, h, w, order, "elastic_plan")) return rc;
-    *workspace_bytes = layout_of(count, k, h, w, order).bytes;
-    if (launches != nullptr) *launches = order == 3 ? 8 : 6;
-    return AFCM_OK;
-}
-
-extern "C" int afcm_batch_assemble_elastic(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype,
-                                           const int64_t* vols, int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment,
-                                           const double* intensity, int32_t independent_planes, const double* elastic, const double* smooth_h,
-                                           const double* smooth_w, int32_t spline_order, void* workspace, int64_t workspace_bytes,
-                                           const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype,
-                                           double min_value, double max_value, void* stream) {
-    using namespace afcm;
+// The launches of afcm_batch_assemble_elastic.  apply_intensity false (augment_blur.hip: a, b are its float32 scratch, out_dtype AFCM_F32): the
+// intensity rows are checked as ever, but the gather leaves the transforms to the stage after it
+int launch_elastic(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols, int32_t n_vols,
+                   const int32_t* items, int32_t n_items, const double* augment, const double* intensity, int32_t independent_planes,
+                   const double* elastic, const double* smooth_h, const double* smooth_w, int32_t spline_order, void* workspace,
+                   int64_t workspace_bytes, const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype,
+                   double min_value, double max_value, void* stream, bool apply_intensity) {
     AFCM_REQUIRE(elastic != nullptr && smooth_h != nullptr && smooth_w != nullptr && workspace != nullptr,
                  "batch_assemble_elastic: null elastic table, smoothing operator or workspace");
     AFCM_REQUIRE(independent_planes == 0 || independent_planes == 1, "batch_assemble_elastic: independent_planes %d is not 0 or 1", independent_planes);
@@ -383,7 +372,7 @@ extern "C" int afcm_batch_assemble_elastic(void* a, void* b, float* slice_idx, c
         using T = typename decltype(t_tag)::type;
 #define AFCM_GATHER(ORDER)                                                                                                                    \
     hipLaunchKernelGGL((elastic_gather_kernel<T, ORDER>), dim3(blocks), dim3(VOL_THREADS), 0, s, (T*)a, (T*)b, slice_idx, meta, sa, sb, coef, field, \
-                       intensity, (int)independent_planes, k, h, w, groups, total)
+                       apply_intensity ? intensity : nullptr, (int)independent_planes, k, h, w, groups, total)
         if (spline_order == 0) AFCM_GATHER(0);
         else if (spline_order == 1) AFCM_GATHER(1);
         else AFCM_GATHER(3);
@@ -393,4 +382,26 @@ extern "C" int afcm_batch_assemble_elastic(void* a, void* b, float* slice_idx, c
     else if (out_dtype == AFCM_F16) gather(type_tag<f16_t>{});
     else gather(type_tag<bf16_t>{});
     return hip_status(hipGetLastError());
+}
+
+}  // namespace afcm
+
+extern "C" int afcm_elastic_plan(int32_t count, int32_t k, int32_t h, int32_t w, int32_t order, int64_t* workspace_bytes, int32_t* launches) {
+    using namespace afcm;
+    AFCM_REQUIRE(workspace_bytes != nullptr, "elastic_plan: null workspace_bytes");
+    if (const int rc = check_geometry(count, k, h, w, order, "elastic_plan")) return rc;
+    *workspace_bytes = layout_of(count, k, h, w, order).bytes;
+    if (launches != nullptr) *launches = order == 3 ? 8 : 6;
+    return AFCM_OK;
+}
+
+extern "C" int afcm_batch_assemble_elastic(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype,
+                                           const int64_t* vols, int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment,
+                                           const double* intensity, int32_t independent_planes, const double* elastic, const double* smooth_h,
+                                           const double* smooth_w, int32_t spline_order, void* workspace, int64_t workspace_bytes,
+                                           const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype,
+                                           double min_value, double max_value, void* stream) {
+    return afcm::launch_elastic(a, b, slice_idx, pool, pool_elems, src_dtype, vols, n_vols, items, n_items, augment, intensity, independent_planes, elastic,
+                                smooth_h, smooth_w, spline_order, workspace, workspace_bytes, cursor, first, count, k, h, w, out_dtype, min_value, max_value,
+                                stream, true);
 }

@@ -1,6 +1,6 @@
 """assemble_batch / advance_cursor: a training batch from a device-resident pool of volumes (C ABI ``afcm_batch_assemble`` /
-``afcm_batch_assemble_aug`` / ``afcm_batch_assemble_noise`` / ``afcm_batch_assemble_elastic`` / ``afcm_cursor_advance``, include/afcm_hip.h; kernels
-in csrc/batch.hip and csrc/elastic.hip).
+``afcm_batch_assemble_aug`` / ``afcm_batch_assemble_noise`` / ``afcm_batch_assemble_elastic`` / ``afcm_batch_assemble_blur`` /
+``afcm_cursor_advance``, include/afcm_hip.h; kernels in csrc/batch.hip, csrc/elastic.hip and csrc/augment_blur.hip).
 
 ``assemble_batch`` is ``SliceDataset(phase='train').__getitem__`` for ``count`` rows of a device-side item table -- ``A``, ``B`` and ``slice_idx`` in
 one launch, bit-identical to the stacked host items.  The tables live on the device, so the kernel checks every row itself: an invalid row comes out
@@ -20,7 +20,7 @@ def _table(t, what, dtype, cols):
 
 
 def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_value=0., max_value=255., dtype=torch.float32, out=None, cursor=None,
-                   augment=None, intensity=None, independent_planes=False, elastic=None, elastic_ops=None, workspace=None):
+                   augment=None, intensity=None, independent_planes=False, elastic=None, elastic_ops=None, workspace=None, blur=None):
     """``pool``: 1-D DEVICE tensor (uint8 / int16 / float32 / float64) holding every volume; ``vols``: DEVICE int64 [n_vols, 4] (element offset into the
     pool, depth, hs, ws); ``items``: DEVICE int32 [n_items, 4] (vol_a, vol_b, idx, thickness; thickness -1: none, ``slice_num`` 1 only).  Sample ``i`` is
     table row ``(cursor[0] if cursor is not None else 0) + first + i``.  Returns ``A [count, slice_num, H, W]``, ``B [count, 1, H, W]`` of ``dtype``
@@ -39,7 +39,12 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     transforms and before the intensity ones, in a fixed number of launches (``afcm_batch_assemble_elastic``, with or without the other two tables);
     ``elastic_ops = (op_h, op_w, order)``: the DEVICE float64 [H, H] and [W, W] smoothing operators (``augment_elastic.smoothing_operator``) and
     the spline order, 0, 1 or 3; ``workspace``: a DEVICE uint8 tensor of at least ``elastic_workspace_bytes(count, slice_num, H, W, order)`` (a
-    captured graph needs a persistent one), allocated per call when None.  An invalid row is a NaN item."""
+    captured graph needs a persistent one), allocated per call when None.  An invalid row is a NaN item.
+    ``blur``: DEVICE float64 [n_items, 20 (slice_num + 1)], one row beside every item row, per plane ``(flag, sigma, radius, w_0 ... w_16)``
+    (``afcm_amd.augment_blur.blur_rows``): every plane with flag 1 filtered as the reference's ``GaussianBlur3D`` does, after the geometric
+    transforms and the elastic deformation and before the intensity ones, in a fixed number of launches (``afcm_batch_assemble_blur``, with or
+    without the other three tables); ``workspace`` then holds at least ``blur_workspace_bytes(count, slice_num, H, W, order)``, ``order`` the
+    spline order of the elastic table or None without one.  An invalid row is a NaN item."""
     h, w = (int(v) for v in patch_hw)
     first, count = int(first), int(count)
     _lib.require_slice_num(slice_num, 'assemble_batch')
@@ -60,8 +65,8 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
         raise RuntimeError(f'assemble_batch: independent_planes must be a bool, got {independent_planes!r}')
     if independent_planes and intensity is None:
         raise RuntimeError('assemble_batch: independent_planes without an intensity table')
-    if (elastic is None) != (elastic_ops is None) or (elastic is None and workspace is not None):
-        raise RuntimeError('assemble_batch: elastic= (the table) and elastic_ops= (op_h, op_w, order) go together, workspace= only with them')
+    if (elastic is None) != (elastic_ops is None) or (elastic is None and blur is None and workspace is not None):
+        raise RuntimeError('assemble_batch: elastic= (the table) and elastic_ops= (op_h, op_w, order) go together, workspace= only with them or blur=')
     if elastic is not None:
         _table(elastic, 'the elastic table', torch.float64, 4)
         if elastic.shape[0] != items.shape[0]:
@@ -75,6 +80,10 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
                 raise RuntimeError(f'assemble_batch: elastic_ops {name} must be a contiguous torch.float64 [{n}, {n}] for a patch of [{h}, {w}], got {got}')
         if isinstance(order, bool) or order not in (0, 1, 3):
             raise RuntimeError(f'assemble_batch: the spline order must be 0, 1 or 3, got {order!r}')
+    if blur is not None:
+        _table(blur, 'the blur table', torch.float64, 20 * (slice_num + 1))
+        if blur.shape[0] != items.shape[0]:
+            raise RuntimeError(f'assemble_batch: the blur table has {blur.shape[0]} rows, the item table {items.shape[0]}: one row per item row')
     _lib.require_out_dtype(dtype, 'assemble_batch')
     if count < 1 or first < 0 or h < 1 or w < 1:
         raise RuntimeError(f'assemble_batch: {count} items from row {first} at [{h}, {w}]: count and the patch must be positive, first not negative')
@@ -96,22 +105,29 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
                                    f'with strides {tuple(t.stride())}')
     tensors = (pool, vols, items, a, b, slice_idx) + (() if cursor is None else (cursor,)) + (() if augment is None else (augment,)) + \
         (() if intensity is None else (intensity,))
-    if elastic is not None:
-        need = elastic_workspace_bytes(count, slice_num, h, w, order)
+    if elastic is not None or blur is not None:
+        if blur is not None:
+            need = blur_workspace_bytes(count, slice_num, h, w, None if elastic is None else order)
+        else:
+            need = elastic_workspace_bytes(count, slice_num, h, w, order)
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.uint8, device=pool.device)
         elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous() or \
                 workspace.numel() < need:
             got = f'{workspace.dtype} {tuple(workspace.shape)}' if isinstance(workspace, torch.Tensor) else type(workspace).__name__
             raise RuntimeError(f'assemble_batch: the workspace must be a contiguous 1-D uint8 tensor of at least {need} bytes, got {got}')
-        tensors += (elastic, op_h, op_w, workspace)
+        tensors += (workspace,) + (() if elastic is None else (elastic, op_h, op_w)) + (() if blur is None else (blur,))
     _lib.require_gpu(*tensors)
     if len({t.device for t in tensors}) != 1:
         raise RuntimeError(f'assemble_batch: pool, tables, outputs and cursor must be on one device, got {sorted({str(t.device) for t in tensors})}')
     head = (a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), code, vols.data_ptr(), int(vols.shape[0]), items.data_ptr(),
             int(items.shape[0]))
     tail = (_lib.ptr(cursor), first, count, slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
-    if elastic is not None:
+    if blur is not None:
+        more = (None, None, None, -1) if elastic is None else (elastic.data_ptr(), op_h.data_ptr(), op_w.data_ptr(), int(order))
+        rc = _lib.load().afcm_batch_assemble_blur(*head, _lib.ptr(augment), _lib.ptr(intensity), int(independent_planes), *more, blur.data_ptr(),
+                                                  workspace.data_ptr(), workspace.numel(), *tail)
+    elif elastic is not None:
         rc = _lib.load().afcm_batch_assemble_elastic(*head, _lib.ptr(augment), _lib.ptr(intensity), int(independent_planes), elastic.data_ptr(),
                                                      op_h.data_ptr(), op_w.data_ptr(), int(order), workspace.data_ptr(), workspace.numel(), *tail)
     elif intensity is not None:
@@ -129,6 +145,15 @@ def elastic_workspace_bytes(count, slice_num, h, w, order):
     (``afcm_elastic_plan``): the float32 item, the two float64 fields and their half-smoothed copies and, at order 3, the float64 coefficients."""
     need = ctypes.c_int64(0)
     _lib.launched(_lib.load().afcm_elastic_plan(int(count), int(slice_num), int(h), int(w), int(order), ctypes.byref(need), None), 'elastic_plan')
+    return int(need.value)
+
+
+def blur_workspace_bytes(count, slice_num, h, w, order=None):
+    """The bytes ``afcm_batch_assemble_blur`` needs for ``count`` items of ``slice_num`` + 1 planes of [h, w] (``afcm_blur_plan``): the float32 item,
+    the float64 intermediate of the two passes and, with an elastic table of spline order ``order``, ``elastic_workspace_bytes`` for its launches."""
+    need = ctypes.c_int64(0)
+    _lib.launched(_lib.load().afcm_blur_plan(int(count), int(slice_num), int(h), int(w), -1 if order is None else int(order), ctypes.byref(need), None),
+                  'blur_plan')
     return int(need.value)
 
 

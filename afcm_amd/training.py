@@ -12,16 +12,21 @@ flipped, turned and rotated as the reference's training transforms do it, inside
 and parameters of its Gaussian and Poisson noise, generated inside ``afcm_batch_assemble_noise``.  With
 ``DeviceSliceSet(elastic=ElasticConfig(...))`` a third float64 table (afcm_amd/augment_elastic.py) carries the decision, the scale and the key of
 the item's elastic deformation, and every batch goes through ``afcm_batch_assemble_elastic``: between the geometric and the intensity transforms.
+With ``DeviceSliceSet(blur=BlurConfig(...))`` a fourth float64 table (afcm_amd/augment_blur.py) carries every plane's decision, sigma and host-made
+weights of the reference's ``GaussianBlur3D``, and every batch goes through ``afcm_batch_assemble_blur``: after the elastic deformation, before
+the intensity transforms.
 """
+import random
+
 import numpy as np
 import torch
 
 from . import _lib
-from . import augment_elastic, augment_intensity
+from . import augment_blur, augment_elastic, augment_intensity
 from .augment import AugmentConfig, apply_host, augment_rows, checked_rows, identity_rows
 from .data import SliceDataset, open_volumes
 from .intensity import percentile_clip_host, rescale_intensity_host
-from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch, elastic_workspace_bytes
+from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch, blur_workspace_bytes, elastic_workspace_bytes
 from .stylegan3_model import capture_graph, require_capturable
 from .torch_utils.ops.intensity_ops import percentile_clip, percentile_fractions, rescale_intensity
 
@@ -48,11 +53,15 @@ class DeviceSliceSet:
     device table beside the others, ``epoch_elastic`` draws an epoch's rows, ``load_epoch`` uploads them and every batch goes through
     ``afcm_batch_assemble_elastic``.  The set builds the two smoothing operators of its patch size once (``elastic_ops``, host and device) and owns
     the launch's workspace, grown to the largest batch asked for (a captured graph keeps the one it was captured with).  None: no table, the
-    launches above."""
+    launches above.
+    ``blur``: a ``BlurConfig`` (afcm_amd/augment_blur.py; 'train' only, with or without the other three) -- a float64
+    [len(self), 20 (slice_num + 1)] device table beside the others, ``epoch_blur`` draws an epoch's rows, ``load_epoch`` uploads them and every
+    batch goes through ``afcm_batch_assemble_blur``, whose workspace (the elastic launches' included) the set owns in the same way.  None: no
+    table, the launches above."""
 
     def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
                  rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None, clip=None,
-                 intensity=None, elastic=None):
+                 intensity=None, elastic=None, blur=None):
         if phase not in ('train', 'val', 'test'):
             raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
         if cat_inputs:
@@ -80,6 +89,12 @@ class DeviceSliceSet:
             if phase != 'train':
                 raise RuntimeError(f"DeviceSliceSet: augmentation belongs to the 'train' phase, got phase {phase!r}")
         self.elastic = elastic
+        if blur is not None:
+            if not isinstance(blur, augment_blur.BlurConfig):
+                raise RuntimeError(f'DeviceSliceSet: blur must be a BlurConfig or None, got {type(blur).__name__}')
+            if phase != 'train':
+                raise RuntimeError(f"DeviceSliceSet: augmentation belongs to the 'train' phase, got phase {phase!r}")
+        self.blur = blur
         # the smoothing operators of the patch size, once: host (the comparison arm) and device
         self.elastic_ops_host = None if elastic is None else tuple(augment_elastic.smoothing_operator(elastic.sigma, n) for n in patch_shape[1:])
         self.elastic_ops = self.elastic_workspace = None
@@ -130,7 +145,7 @@ class DeviceSliceSet:
         self._idx = np.concatenate([np.arange(d, dtype=np.int64) for d in self.depths])
         self._host_sets, self._host_rescaled = {}, {}
         self.device = None if device is None else torch.device(device)
-        self.pool = self.vols = self.items = self.cursor = self.augment_table = self.intensity_table = self.elastic_table = None
+        self.pool = self.vols = self.items = self.cursor = self.augment_table = self.intensity_table = self.elastic_table = self.blur_table = None
         self.rows = self.position = 0
         if self.device is not None:
             if self.device.type != 'cuda':
@@ -158,6 +173,8 @@ class DeviceSliceSet:
             if self.elastic is not None:
                 self.elastic_table = torch.from_numpy(augment_elastic.identity_rows(len(self))).to(self.device)
                 self.elastic_ops = tuple(torch.from_numpy(op).to(self.device) for op in self.elastic_ops_host) + (self.elastic.spline_order,)
+            if self.blur is not None:
+                self.blur_table = torch.from_numpy(augment_blur.identity_rows(len(self), self.slice_num)).to(self.device)
 
     def __len__(self):
         return int(self._idx.shape[0])
@@ -243,10 +260,30 @@ class DeviceSliceSet:
             return None
         return augment_elastic.identity_rows(n) if elastic is None else augment_elastic.checked_rows(elastic, n, f'DeviceSliceSet.{what}')
 
-    def load_epoch(self, items, augment=None, intensity=None, elastic=None):
+    def epoch_blur(self, seed_or_generator=None, rows=None):
+        """The float64 [rows, 20 (slice_num + 1)] blur table of one epoch (``rows``: ``len(self)`` when None), drawn by ``augment_blur.blur_rows``
+        from the set's ``BlurConfig``.  The reference's class draws from Python's ``random``, so the draws come from a ``random.Random``
+        (``seed_or_generator``: one, or an int seed for one), not from the numpy generator the other tables share."""
+        if self.blur is None:
+            raise RuntimeError('DeviceSliceSet.epoch_blur: this set was built without blur=BlurConfig(...)')
+        rng = seed_or_generator if isinstance(seed_or_generator, random.Random) else random.Random(seed_or_generator)
+        return augment_blur.blur_rows(self.blur, len(self) if rows is None else rows, self.slice_num, rng)
+
+    def _checked_blur(self, blur, n, what):
+        """``_checked_augment`` for the blur table."""
+        if self.blur is None:
+            if blur is not None:
+                raise RuntimeError(f'DeviceSliceSet.{what}: a blur table for a set built without blur=BlurConfig(...)')
+            return None
+        if blur is None:
+            return augment_blur.identity_rows(n, self.slice_num)
+        return augment_blur.checked_rows(blur, n, self.slice_num, f'DeviceSliceSet.{what}')
+
+    def load_epoch(self, items, augment=None, intensity=None, elastic=None, blur=None):
         """Uploads the table into the persistent device table (rows past it are marked invalid) and puts the cursor back to row 0.  A set built
         with ``augment`` takes the epoch's parameter rows (``epoch_augment``) the same way, identity rows when none are given; one built with
-        ``intensity`` its intensity rows (``epoch_intensity``) likewise, one built with ``elastic`` its elastic rows (``epoch_elastic``)."""
+        ``intensity`` its intensity rows (``epoch_intensity``) likewise, one built with ``elastic`` its elastic rows (``epoch_elastic``), one built
+        with ``blur`` its blur rows (``epoch_blur``)."""
         self._need_device('load_epoch')
         items = self._checked_items(items)
         if items.shape[0] > self.items.shape[0]:
@@ -254,6 +291,7 @@ class DeviceSliceSet:
         augment = self._checked_augment(augment, items.shape[0], 'load_epoch')
         intensity = self._checked_intensity(intensity, items.shape[0], 'load_epoch')
         elastic = self._checked_elastic(elastic, items.shape[0], 'load_epoch')
+        blur = self._checked_blur(blur, items.shape[0], 'load_epoch')
         self.items[:items.shape[0]].copy_(torch.from_numpy(items), non_blocking=False)
         self.items[items.shape[0]:].fill_(-1)
         if augment is not None:
@@ -265,6 +303,9 @@ class DeviceSliceSet:
         if elastic is not None:
             self.elastic_table[:items.shape[0]].copy_(torch.from_numpy(elastic), non_blocking=False)
             self.elastic_table[items.shape[0]:].copy_(torch.from_numpy(augment_elastic.identity_rows(len(self) - items.shape[0])))
+        if blur is not None:
+            self.blur_table[:items.shape[0]].copy_(torch.from_numpy(blur), non_blocking=False)
+            self.blur_table[items.shape[0]:].copy_(torch.from_numpy(augment_blur.identity_rows(len(self) - items.shape[0], self.slice_num)))
         self.rows = int(items.shape[0])
         self.rewind()
 
@@ -284,11 +325,19 @@ class DeviceSliceSet:
         if not use_cursor and (count < 1 or first < 0 or first + count > self.rows):
             raise RuntimeError(f'DeviceSliceSet.batch: rows [{first}, {first + count}) are not inside the loaded epoch of {self.rows} (load_epoch first)')
         more = {}
-        if self.elastic is not None:
-            need = elastic_workspace_bytes(count, self.slice_num, *self.patch_shape[1:], self.elastic.spline_order)
+        if self.elastic is not None or self.blur is not None:
+            order = None if self.elastic is None else self.elastic.spline_order
+            if self.blur is not None:                                                        # the blur launches' workspace holds the elastic ones'
+                need = blur_workspace_bytes(count, self.slice_num, *self.patch_shape[1:], order)
+            else:
+                need = elastic_workspace_bytes(count, self.slice_num, *self.patch_shape[1:], order)
             if self.elastic_workspace is None or self.elastic_workspace.numel() < need:   # a larger batch than any before: a new one; a graph keeps its own
                 self.elastic_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-            more = dict(elastic=self.elastic_table, elastic_ops=self.elastic_ops, workspace=self.elastic_workspace)
+            more = dict(workspace=self.elastic_workspace)
+            if self.elastic is not None:
+                more.update(elastic=self.elastic_table, elastic_ops=self.elastic_ops)
+            if self.blur is not None:
+                more.update(blur=self.blur_table)
         return assemble_batch(self.pool, self.vols, self.items, first, count, self.patch_shape[1:], slice_num=self.slice_num, min_value=self.min_value,
                               max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None, augment=self.augment_table,
                               intensity=self.intensity_table, independent_planes=self.intensity is not None and self.intensity.independent_planes, **more)
@@ -313,14 +362,17 @@ class DeviceSliceSet:
                                             for p, v in self.volumes[subject].items()}
         return self._host_rescaled[subject]
 
-    def host_batch(self, items, first, count, device=None, augment=None, intensity=None, elastic=None):
+    def host_batch(self, items, first, count, device=None, augment=None, intensity=None, elastic=None, blur=None):
         """The same batch through ``SliceDataset(phase='train', thickness=[t])`` items, stacked and uploaded: the comparison arm of tests and
         benchmark.  ``augment``: the parameter table that goes with ``items`` (a set built with ``augment`` only); ``augment.apply_host`` applies
         row ``first + j`` to ``A`` and ``B`` of item ``first + j``.  ``intensity``: the intensity table that goes with ``items`` (a set built with
         ``intensity`` only), applied after it by ``augment_intensity.apply_host``.  ``elastic``: the elastic table that goes with ``items`` (a set
-        built with ``elastic`` only), applied between the two by ``augment_elastic.apply_host``.  A row the kernel would refuse raises here."""
+        built with ``elastic`` only), applied between the two by ``augment_elastic.apply_host``.  ``blur``: the blur table that goes with
+        ``items`` (a set built with ``blur`` only), applied between the elastic and the intensity arms by ``augment_blur.apply_host``.  A row the
+        kernel would refuse raises here."""
         items = self._checked_items(items)
         elastic = None if elastic is None else self._checked_elastic(elastic, items.shape[0], 'host_batch')
+        blur = None if blur is None else self._checked_blur(blur, items.shape[0], 'host_batch')
         augment = None if augment is None else self._checked_augment(augment, items.shape[0], 'host_batch')
         intensity = None if intensity is None else self._checked_intensity(intensity, items.shape[0], 'host_batch')
         m = len(self.paths)
@@ -343,6 +395,9 @@ class DeviceSliceSet:
                 item['A'], item['B'] = apply_host(item['A'], augment[first + j]), apply_host(item['B'], augment[first + j])
             if elastic is not None:                                                      # all planes of the item, the target included: one deformation
                 both = augment_elastic.apply_host(torch.cat([item['A'], item['B']]), elastic[first + j], self.elastic, self.elastic_ops_host)
+                item['A'], item['B'] = both[:-1], both[-1:]
+            if blur is not None:                                                         # every plane its own record: those of A, then B
+                both = augment_blur.apply_host(torch.cat([item['A'], item['B']]), blur[first + j])
                 item['A'], item['B'] = both[:-1], both[-1:]
             if intensity is not None:
                 independent = self.intensity.independent_planes
@@ -374,7 +429,7 @@ def _fed_step(step, schedule, batch_size, batch, gen_z, cur_nimg=None):
 
 
 def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None, ramp=None, where='device', gen_z=None, augment=None,
-                intensity=None, elastic=None):
+                intensity=None, elastic=None, blur=None):
     """The inner loop of the reference's train.py:45-77 over the epoch table ``items`` (``DeviceSliceSet.epoch_items``): per batch
     ``total_iters += batch_size``, ``step.set_input(A, B, gen_c=slice_idx)``, ``step.optimize_parameters(cur_nimg=total_iters)`` and, when the step
     has an EMA copy and ``ema_kimgs`` is given, ``step.update_ema(batch_size, total_iters, ema_kimgs, ramp)``.  The last batch is partial, as the
@@ -382,7 +437,8 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     ``where='host'``: from ``SliceDataset`` items (``DeviceSliceSet.host_batch``), the same bits.  Both arms draw ``gen_z`` in the same order
     (``gen_z``: a fixed [batch_size, z_dim] tensor instead of a draw per batch).  ``augment``: the epoch's parameter table
     (``DeviceSliceSet.epoch_augment``) for a set built with ``augment``, ``intensity``: the epoch's intensity table (``epoch_intensity``) for one built with ``intensity``, ``elastic``: the epoch's elastic table
-    (``epoch_elastic``) for one built with ``elastic`` (the host arm is ``augment_elastic.apply_host``); both arms apply them.  Works with ``StyleGAN3GeneratorStep`` and
+    (``epoch_elastic``) for one built with ``elastic`` (the host arm is ``augment_elastic.apply_host``), ``blur``: the epoch's blur table (``epoch_blur``) for one built with ``blur`` (the host arm is
+    ``augment_blur.apply_host``); both arms apply them.  Works with ``StyleGAN3GeneratorStep`` and
     ``StyleGAN3Step`` alike.
     Returns the new ``total_iters``."""
     if where not in ('device', 'host'):
@@ -396,13 +452,14 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     augment = dataset._checked_augment(augment, n, 'train_epoch')
     intensity = dataset._checked_intensity(intensity, n, 'train_epoch')
     elastic = dataset._checked_elastic(elastic, n, 'train_epoch')
+    blur = dataset._checked_blur(blur, n, 'train_epoch')
     if where == 'device':
-        dataset.load_epoch(items, augment, intensity, elastic)
+        dataset.load_epoch(items, augment, intensity, elastic, blur)
     schedule = getattr(step, 'schedule', None) if where == 'device' else None
     for first in range(0, n, batch_size):
         count = min(batch_size, n - first)
         batch = (lambda: dataset.batch(first, count)) if where == 'device' else (
-            lambda: dataset.host_batch(items, first, count, device=device, augment=augment, intensity=intensity, elastic=elastic))
+            lambda: dataset.host_batch(items, first, count, device=device, augment=augment, intensity=intensity, elastic=elastic, blur=blur))
         total_iters += batch_size
         _fed_step(step, schedule, batch_size, batch, None if gen_z is None else gen_z[:count], cur_nimg=total_iters)
         if schedule is None and ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
@@ -429,7 +486,8 @@ class TrainingGraph:
     is captured with ``afcm_batch_assemble_aug``: the parameter table is persistent as the item table is, and the cursor moves through both; one built with
     ``intensity`` with ``afcm_batch_assemble_noise``, its table persistent in the same way; one built with ``elastic`` with the launches of
     ``afcm_batch_assemble_elastic`` -- a fixed number, each skipping on the device the items whose flag is 0 -- and the graph keeps the workspace
-    it was captured with."""
+    it was captured with; one built with ``blur`` with the launches of ``afcm_batch_assemble_blur``, fixed in number as well, the workspace kept
+    likewise."""
 
     def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None, undo_warmup=False):
         require_capturable(step, 'TrainingGraph')
@@ -484,8 +542,8 @@ class TrainingGraph:
         self.graph = capture_graph(lambda: _fed_step(step, schedule, batch_size, cursor_batch, self.gen_z), warmup, next_rows, leave_no_trace)
         self.elastic_workspace = dataset.elastic_workspace    # the captured launches point into it, whatever the set allocates later
 
-    def load_epoch(self, items, augment=None, intensity=None, elastic=None):
-        self.dataset.load_epoch(items, augment, intensity, elastic)
+    def load_epoch(self, items, augment=None, intensity=None, elastic=None, blur=None):
+        self.dataset.load_epoch(items, augment, intensity, elastic, blur)
 
     def rewind(self):
         self.dataset.rewind()
@@ -504,7 +562,8 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
     """The outer loop of the reference's train.py:38-45 for a step built with a ``DeviceSchedule``.  ``epochs``: an iterable of epoch numbers
     (``range(epoch_count, n_epochs + n_epochs_decay + 1)``).  Per epoch: ``step.set_lr(lr_schedule.lr_at(k))`` for G and D, k = 1 for the first
     (``update_learning_rate()`` at the top of every epoch); ``dataset.epoch_items(rng)``, for a set built with ``augment`` ``epoch_augment(rng)``
-    right after it, for one built with ``intensity`` ``epoch_intensity(rng)`` after that, for one built with ``elastic`` ``epoch_elastic(rng)`` last, and ``load_epoch``; then replays of ONE ``TrainingGraph``
+    right after it, for one built with ``intensity`` ``epoch_intensity(rng)`` after that, for one built with ``elastic`` ``epoch_elastic(rng)`` after that, for one built with ``blur`` ``epoch_blur`` last -- from a ``random.Random``
+    seeded by one extra draw of ``rng``, ``rng.integers(0, 2 ** 63)``, taken only when ``blur`` is configured -- and ``load_epoch``; then replays of ONE ``TrainingGraph``
     built in the first epoch (``graph=False``: eager steps, the same kernels) until fewer than ``batch_size`` rows remain; ``on_epoch(epoch, step)``
     -- validation and checkpoints are the caller's, through ``validation.validate`` and ``step.save_networks``.  ``rng``: a seed or a
     ``numpy.random.Generator``; an int seeds one generator for the whole run.  ``gen_z``: one fixed [batch_size, z_dim] latent batch for every step
@@ -525,7 +584,9 @@ def train_epochs(step, dataset, batch_size, epochs, lr_schedule, rng, graph=True
         items = dataset.epoch_items(rng)
         augment = dataset.epoch_augment(rng) if dataset.augment is not None else None
         intensity = dataset.epoch_intensity(rng) if dataset.intensity is not None else None
-        dataset.load_epoch(items, augment, intensity, dataset.epoch_elastic(rng) if dataset.elastic is not None else None)
+        elastic = dataset.epoch_elastic(rng) if dataset.elastic is not None else None
+        blur = dataset.epoch_blur(random.Random(int(rng.integers(0, 2 ** 63)))) if dataset.blur is not None else None
+        dataset.load_epoch(items, augment, intensity, elastic, blur)
         if dataset.rows < batch_size:
             raise RuntimeError(f'train_epochs: an epoch of {dataset.rows} rows is shorter than a batch of {batch_size}')
         if graph and runner is None:

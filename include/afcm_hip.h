@@ -757,6 +757,44 @@ int afcm_batch_assemble_elastic(void* a, void* b, float* slice_idx, const void* 
                                 int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Training batches with a Gaussian blur: the reference's GaussianBlur3D (data/augment/transforms.py:716-726; configs/defaults.py:80-82, sigma
+ * [0.1, 2], execution_probability 0.5) on every [1, h, w] plane of the item, every plane with its own decision and sigma (the reference draws per
+ * plane).  Its filter is skimage.filters.gaussian(x, sigma), by skimage's documentation scipy.ndimage.gaussian_filter(x, sigma, mode='nearest',
+ * truncate=4.0) on a float array; the statement below equals that scipy call bit for bit (parity with skimage's own function is not pinned).
+ * Position in the chain: after the geometric transforms (augment, may be null) and the elastic deformation (elastic, may be null; with it
+ * smooth_h, smooth_w and spline_order as afcm_batch_assemble_elastic takes them), before the intensity transforms (intensity, may be null).
+ * blur: DEVICE float64 [n_items][20 (k + 1)], row r of sample i the same r as the item row; 20 doubles per plane, the k planes of A, then B:
+ * (flag, sigma, radius, w_0 ... w_16).  The weights are made by the HOST (afcm_amd/augment_blur.py: gaussian_weights): radius = int(4 sigma + 0.5),
+ * phi_x = exp(-0.5 / (sigma sigma) x^2) for x = -radius ... radius, over their sum, w_j = phi at +j; the kernels evaluate no exponential and do
+ * not read sigma beyond its check.
+ * p: the float32 plane the launch without the blur and intensity tables produces.  All arithmetic is float64, every product and every addition
+ * rounded on its own, three passes in axis order -- depth (a line of one element), y, x -- each per output element i of a line v[0 ... n):
+ *   t = v[i] w_0;  t = t + (v[clamp(i - j, 0, n - 1)] + v[clamp(i + j, 0, n - 1)]) w_j for j = radius, radius - 1, ..., 1
+ * so the depth pass is t = p w_0; t = t + (p + p) w_j.  The result is rounded once to float32; the intensity transforms, where a table is given,
+ * then act on that float32 value as afcm_batch_assemble_noise states; then one rounding to out_dtype.  The reference filters the float64 plane
+ * BEFORE its float32 cast; here the float32 item is widened back: a blurred pixel may differ from the reference's arithmetic by one float32 unit
+ * in the last place.  afcm_amd/augment_blur.py evaluates the same operations in numpy and gets the same bits.  No atomics.
+ * A plane record is valid when flag is 0 or 1, sigma is finite and > 0, radius is a whole number in [0, 16] and w_0 ... w_16 are finite; a row
+ * when all its records are.  An item with an invalid row of any table reads nothing from the pool and is NaN throughout, label included.  A plane
+ * whose flag is 0 has the bits of the launch without the table.
+ * Launches on `stream`, a fixed number per call whatever the flags are (afcm_blur_plan: 4, or 3 + those of afcm_elastic_plan with an elastic
+ * table), no allocation, no synchronise: the float32 item into the workspace (afcm_batch_assemble / _aug's kernel, or the launches of
+ * afcm_batch_assemble_elastic with the workspace as their output), the rows' check, the depth and y pass (32 x 64 output tiles, the rows and their
+ * halo staged in LDS, float64 out), the x pass with the rest of the chain (16 x 64 output tiles).  afcm_blur_tiles gives those four extents.
+ * workspace: DEVICE, on a multiple of 256 bytes, at least the workspace_bytes afcm_blur_plan gives for (count, k, h, w, elastic_order), where
+ * elastic_order is the spline order of the elastic table or -1 without one; no initialisation needed, nothing is kept between calls.
+ * AFCM_E_INVALID as afcm_batch_assemble_elastic where an elastic table is given and as afcm_batch_assemble_noise otherwise; also a null blur table
+ * or workspace, a workspace that is too small or misaligned, count above 32767, h or w above 32768.
+ * ---------------------------------------------------------------------------------------- */
+int afcm_blur_plan(int32_t count, int32_t k, int32_t h, int32_t w, int32_t elastic_order, int64_t* workspace_bytes, int32_t* launches);
+void afcm_blur_tiles(int32_t* rows_tile_h, int32_t* rows_tile_w, int32_t* cols_tile_h, int32_t* cols_tile_w);
+int afcm_batch_assemble_blur(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                             int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment, const double* intensity,
+                             int32_t independent_planes, const double* elastic, const double* smooth_h, const double* smooth_w, int32_t spline_order,
+                             const double* blur, void* workspace, int64_t workspace_bytes, const int64_t* cursor, int32_t first, int32_t count,
+                             int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value, double max_value, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * The training loop's time-dependent scalars on the device (r11), so that ONE captured graph stays right for a whole run.
  * The schedule block is a DEVICE array of 8 doubles:
  *   [0] total_iters  images seen: the reference's total_iters / cur_nimg (train.py:50-53), exact in a double

@@ -8,6 +8,9 @@ against the fixed-input one.  Two steps, each its own process (run each under it
                                                            # probabilities) beside the plain and the augmented launch; the host arm
     python tools/bench_train_feed.py feed --elastic        # afcm_batch_assemble_elastic (no item, every item, the reference's probability 0.1;
                                                            # orders 3, 1, 0) beside the plain launch; the host arm
+    python tools/bench_train_feed.py feed --blur           # afcm_batch_assemble_blur (no plane, every plane at radius 8, the reference's
+                                                           # probability 0.5, the same with the elastic table) beside the plain and the elastic
+                                                           # launch; the host arm.  --only ARM: that arm's launches alone, for a kernel trace
 
 (a) alternates ``DeviceSliceSet.host_batch`` (SliceDataset items in numpy, stacked, uploaded) and ``DeviceSliceSet.batch`` (one launch) over the same
 rows of a synthetic uint8 set after a warm-up of each, the alternation repeated; wall time by a host clock ended by a synchronise.  (b) times
@@ -372,6 +375,106 @@ def feed_elastic(args):
     return 0 if equal else 1
 
 
+def feed_blur(args):
+    """``feed --blur``: the blur launches (``afcm_batch_assemble_blur``: 4, or 11 with an order-3 elastic table) beside the plain launch and the
+    elastic launches, device events over the whole call, the arms alternated inside every repeat -- no plane executing (the cost every batch
+    pays: the scratch round trip, the rows' check and a y pass that exits early), every plane executing at radius 8 (sigma 2, the upper end of the
+    reference's range), the reference's execution probability 0.5 with sigma in [0.1, 2], and the same after the elastic deformation at its own
+    reference settings; and the host arm -- ``augment_blur.apply_host`` -- by a host clock.  ``--only ARM`` launches that one arm 20 times and
+    returns: what a kernel trace of one arm needs."""
+    import torch
+    from afcm_amd import _lib
+    import numpy as np
+    from afcm_amd.augment_blur import BlurConfig, identity_rows, plane_record
+    from afcm_amd.augment_elastic import ElasticConfig
+    from afcm_amd.torch_utils.ops.batch_ops import blur_workspace_bytes
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_train_feed.py needs a GPU: a time taken without one says nothing')
+    dev = torch.device('cuda:0')
+    ds = synthetic_set(args.subjects, args.depth, args.res, dev, elastic=ElasticConfig(), blur=BlurConfig())
+    items = ds.epoch_items(0)
+    n = len(items)
+    reference = ds.epoch_blur(1)
+    tables = {'blur_none': identity_rows(n, 4), 'blur_every_radius8': np.tile(plane_record(2.0), (n, 5)), 'blur_reference_0.5': reference}
+    tables = {name: torch.from_numpy(rows).to(dev) for name, rows in tables.items()}
+    warp = torch.from_numpy(ds.epoch_elastic(2)).to(dev)
+    ds.load_epoch(items, None, None, None, reference)
+    batches = min(args.batches, n // args.batch)
+    lib, launches = _lib.load(), {}
+    op_h, op_w, order = ds.elastic_ops
+    work = torch.empty(blur_workspace_bytes(args.batch, 4, args.res, args.res, order), dtype=torch.uint8, device=dev)
+    for out_name, out_dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
+        a = torch.empty((args.batch, 4, args.res, args.res), dtype=out_dtype, device=dev)
+        b = torch.empty((args.batch, 1, args.res, args.res), dtype=out_dtype, device=dev)
+        c = torch.empty((args.batch, 1), dtype=torch.float32, device=dev)
+        out_bytes = a.numel() * a.element_size() + b.numel() * b.element_size()
+        head = (a.data_ptr(), b.data_ptr(), c.data_ptr(), ds.pool.data_ptr(), ds.pool.numel(), _lib.SRC_U8, ds.vols.data_ptr(), int(ds.vols.shape[0]),
+                ds.items.data_ptr(), int(ds.items.shape[0]))
+        tail = (None, 0, args.batch, 4, args.res, args.res, _lib.dtype_code(a), 0., 255., _lib.stream_ptr(a))
+        with_warp = (warp.data_ptr(), op_h.data_ptr(), op_w.data_ptr(), order)
+
+        def plain():
+            assert lib.afcm_batch_assemble(*head, *tail) == 0
+
+        def elastic():
+            assert lib.afcm_batch_assemble_elastic(*head, None, None, 0, *with_warp, work.data_ptr(), work.numel(), *tail) == 0
+
+        def blur(table, warped=False):
+            def launch():
+                assert lib.afcm_batch_assemble_blur(*head, None, None, 0, *(with_warp if warped else (None, None, None, -1)), table.data_ptr(),
+                                                    work.data_ptr(), work.numel(), *tail) == 0
+            return launch
+
+        arms = dict({'plain': plain, 'elastic_reference_0.1': elastic}, **{name: blur(table) for name, table in tables.items()})
+        arms['blur_reference_0.5+elastic_0.1'] = blur(tables['blur_reference_0.5'], True)
+        if args.only is not None:
+            for _ in range(20):
+                arms[args.only]()
+            torch.cuda.synchronize()
+            print(f'{args.only}: 20 calls, fp32 outputs')
+            return 0
+        us = {name: [] for name in arms}
+        for _ in range(args.repeats):
+            for name, fn in arms.items():
+                us[name].append(events_us(fn, launches=50))
+        for name, v in us.items():
+            launches[f'{name}_{out_name}'] = dict(per_repeat_us=v, mean_us=sum(v) / len(v), spread_us=spread(v),
+                                                  ns_per_kib=sum(v) / len(v) * 1e3 / (out_bytes / 1024))
+
+    def clock(rows):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for j in range(batches):
+            out = ds.host_batch(items, j * args.batch, args.batch, blur=rows)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / batches, out
+
+    host = {'host_plain': None, 'host_reference_0.5': reference}
+    stats, last = {name: [] for name in host}, {}
+    for name, rows in host.items():
+        clock(rows)
+    for _ in range(args.repeats):
+        for name, rows in host.items():
+            ms, last[name] = clock(rows)
+            stats[name].append(ms)
+    device_last = ds.batch((batches - 1) * args.batch, args.batch)
+    equal = all(torch.equal(x, y) for x, y in zip(last['host_reference_0.5'], device_last))
+    executed = float(reference[:, ::20].mean())
+    print(f'training batches of {args.batch} x (4 + 1) planes at {args.res}^2 from {args.subjects} uint8 subjects of ({args.depth}, {args.res}, {args.res}) with '
+          f'the per-plane Gaussian blur, sigma in [0.1, 2] ({100 * executed:.1f} % of the planes execute in the 0.5 table); elastic: sigma 50, alpha 2000, '
+          f'order 3; {args.repeats} repeats, the arms alternated inside each')
+    for name, s in launches.items():
+        print(f'{name:36s} us per call {"  ".join(f"{x:8.2f}" for x in s["per_repeat_us"])}   mean {s["mean_us"]:8.2f}   spread {s["spread_us"]:.2f}   '
+              f'{s["ns_per_kib"]:.3f} ns per KiB of output')
+    arms = {}
+    for name, v in stats.items():
+        arms[name] = dict(per_repeat_ms=v, mean_ms=sum(v) / len(v), spread_ms=spread(v))
+        print(f'{name:36s} ms/batch per repeat {"  ".join(f"{x:8.3f}" for x in v)}   mean {arms[name]["mean_ms"]:8.3f}   spread {arms[name]["spread_ms"]:.3f}')
+    print(f'the host arm\'s and the device\'s last blurred batch are {"bit-identical" if equal else "DIFFERENT"}')
+    print(json.dumps(dict(bench='train_feed_blur', res=args.res, batch=args.batch, launches=launches, arms=arms, equal=equal)))
+    return 0 if equal else 1
+
+
 def step(args):
     import torch
     from afcm_amd import layer_schedule as sched
@@ -441,12 +544,16 @@ def main():
     ap.add_argument('--augment', action='store_true', help='feed: time the augmented launch and the augmenting host arm instead')
     ap.add_argument('--intensity', action='store_true', help='feed: time the noise launch and its host arm instead')
     ap.add_argument('--elastic', action='store_true', help='feed: time the elastic launches and their host arm instead')
+    ap.add_argument('--blur', action='store_true', help='feed: time the blur launches and their host arm instead')
+    ap.add_argument('--only', default=None, help='feed --blur: launch this one arm 20 times and return (for a kernel trace)')
     args = ap.parse_args()
-    if (args.augment or args.intensity or args.elastic) and args.what != 'feed':
-        raise SystemExit('--augment, --intensity and --elastic belong to the feed step')
-    if args.augment + args.intensity + args.elastic > 1:
-        raise SystemExit('--augment, --intensity or --elastic, one at a time')
-    feeds = feed_elastic if args.elastic else (feed_intensity if args.intensity else (feed_augment if args.augment else feed))
+    if (args.augment or args.intensity or args.elastic or args.blur) and args.what != 'feed':
+        raise SystemExit('--augment, --intensity, --elastic and --blur belong to the feed step')
+    if args.augment + args.intensity + args.elastic + args.blur > 1:
+        raise SystemExit('--augment, --intensity, --elastic or --blur, one at a time')
+    if args.only is not None and not args.blur:
+        raise SystemExit('--only belongs to feed --blur')
+    feeds = feed_blur if args.blur else feed_elastic if args.elastic else (feed_intensity if args.intensity else (feed_augment if args.augment else feed))
     return {'feed': feeds, 'step': step}[args.what](args)
 
 
