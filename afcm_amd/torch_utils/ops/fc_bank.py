@@ -22,8 +22,11 @@ _MAPIN_WS = {}
 
 
 def supported(x, weight, activation):
+    # (csrc/fc_bank.hip afcm_fc_act_fwd: 16-byte loads of x and w rows -- a contiguous view that starts off the 16-byte grid stays where it
+    # is under .contiguous(), so the gate has to look at the addresses)
     return (ENABLED and activation in _ACTS and x.ndim == 2 and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32
-            and 0 < x.shape[0] <= 64 and weight.shape[1] % 16 == 0 and weight.shape[0] % 16 == 0)
+            and 0 < x.shape[0] <= 64 and weight.shape[1] % 16 == 0 and weight.shape[0] % 16 == 0
+            and x.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0)
 
 
 class _FcAct(torch.autograd.Function):
@@ -51,6 +54,8 @@ class _FcAct(torch.autograd.Function):
         alpha, beta, act, has_b = ctx.cfg
         lib = _lib.load()
         gy = gy.contiguous()
+        if gy.data_ptr() % 16 != 0:
+            gy = gy.clone()                                     # (the kernel reads gy rows with 16-byte loads; a fresh buffer is aligned)
         n, cin = x.shape
         cout = int(w.shape[0])
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None

@@ -4,7 +4,7 @@ declines raises, _lib.launched); where it says no, either the op itself must ref
 runs and is held to the same bar.  Thresholds, from the code:
   affine_bank   K = kw + kg <= 1536, K % 16, kw % 4, kg % 4, 16-byte aligned rows (csrc/affine_bank.hip bank_supported); 16 batch rows
                 per pass (kNB), later passes accumulate dW
-  fc_act        n <= 64, cin % 16, cout % 16 backward; NT = 1 / 2 / 4 at n <= 16 / 32 / 64; 1024-thread form at cin >= 2048, n <= 32
+  fc_act        n <= 64, cin % 16, cout % 16 backward, 16-byte aligned x and weight; NT = 1 / 2 / 4 at n <= 16 / 32 / 64; 1024-thread form at cin >= 2048, n <= 32
                 (csrc/fc_bank.hip afcm_fc_act_fwd / _bwd)
   mapping_input one workgroup per sample, the last one (a ticket) reduces and re-arms the ticket (csrc/fc_bank.hip mapping_input_bwd_kernel)
   modulation    weight rows cin k^2 <= 1024 / <= 4608 / longer; style rows of at most 16384 channels (csrc/modulation.hip)
@@ -152,6 +152,41 @@ def test_fc_act_thread_classes_vs_float64(n, cin, monkeypatch):
 def test_fc_fallback_outside_the_gate_vs_float64(n, cin, cout, act, monkeypatch):
     """cout % 16, more than 64 rows, cin % 16: the gate says no and the GEMM composition holds the same bar."""
     _fc_vs_float64(n, cin, cout, act, False, monkeypatch)
+
+
+@pytest.mark.parametrize('n,cin,cout,act', [(8, 64, 48, 'lrelu'), (16, 32, 16, 'linear')], ids=str)
+def test_fc_fallback_for_a_view_off_the_16_byte_grid_vs_float64(n, cin, cout, act, monkeypatch):
+    """x = buf[1:].view(n, cin): contiguous, so .contiguous() leaves it where it is, 4 bytes past a 16-byte boundary.  The kernel's
+    16-byte loads cannot take it (afcm_fc_act_fwd refuses the pointers), so the gate must say no and the GEMM composition run, held to
+    the kernel's bars.  The same input on the 16-byte grid takes the kernel; there a cotangent off the grid is copied, not refused."""
+    from afcm_amd.networks_stylegan3 import FullyConnectedLayer
+    from afcm_amd.torch_utils.ops import fc_bank
+    torch.manual_seed(n + cin + cout)
+    fc = FullyConnectedLayer(cin, cout, activation=act, lr_multiplier=0.37, bias_init=0.5).cuda()
+    xa = torch.randn(n, cin, device='cuda')
+    x = torch.empty(n * cin + 1, device='cuda')[1:].view(n, cin).copy_(xa).requires_grad_(True)
+    r = torch.empty(n * cout + 1, device='cuda')[1:].view(n, cout).copy_(torch.randn(n, cout, device='cuda'))
+    assert x.is_contiguous() and x.data_ptr() % 16 == 4 and x.contiguous().data_ptr() == x.data_ptr() and r.data_ptr() % 16 == 4
+    calls = []
+    real = fc_bank.fc_act
+    monkeypatch.setattr(fc_bank, 'fc_act', lambda *a, **k: calls.append(1) or real(*a, **k))
+    y = fc(x)                                                                      # (raised before the gate looked at addresses)
+    got = torch.autograd.grad(y, [x, fc.weight, fc.bias], r)
+    assert len(calls) == 0
+    assert fc_bank.supported(xa, fc.weight, act) and not fc_bank.supported(x, fc.weight, act)
+    xa.requires_grad_(True)
+    ya = fc(xa)
+    gota = torch.autograd.grad(ya, [xa, fc.weight, fc.bias], r)                    # the kernel, its cotangent off the grid
+    assert len(calls) == 1
+    xd, wd, bd = (t.detach().double().cpu().requires_grad_(True) for t in (x, fc.weight, fc.bias))
+    yd = xd @ (wd * fc.weight_gain).t() + bd * fc.bias_gain
+    if act == 'lrelu':
+        yd = torch.nn.functional.leaky_relu(yd, 0.2) * np.sqrt(2)
+    ref = torch.autograd.grad(yd, [xd, wd, bd], r.double().cpu())
+    for route, yy, gg in (('fallback', y, got), ('kernel', ya, gota)):
+        _close(yy, yd, 2e-6, f'y ({route})')
+        for nm, a, b in zip(('dx', 'dw', 'db'), gg, ref):
+            _close(a, b, 3e-6, f'{nm} ({route})')
 
 
 # ---- mapping input stage ----------------------------------------------------------------------------------------------------------------------
