@@ -11,6 +11,9 @@ and write it in place.  Rules of the layout:
 * columns >= W of a row are padding.  No kernel may depend on what they hold, except that a kernel that WRITES a pitched tensor
   fills them with finite values (the weight gradient multiplies the head of dy's padding by zeros, include/afcm_hip.h).
 * a tensor that is neither dense nor of exactly this form is made contiguous (``rows``).
+* the base address of a tensor handed to a kernel lies on the kernels' grid: ``BASE_ALIGN`` bytes.  A contiguous view may sit at
+  any element offset of its storage (``buf[1:].view(...)``: 2 bytes past an allocation for a 16-bit dtype) and ``.contiguous()``
+  leaves it there, so ``rows`` / ``dense`` move such a tensor to a fresh allocation (``clone``), and ``pitch_of`` answers None.
 """
 import torch
 
@@ -19,6 +22,11 @@ import torch
 ROW_BYTES = 64          # rows padded to multiples of this (>= 16)
 MAX_OVERHEAD = 0.10     # ... unless that pads a row by more than this fraction
 ENABLED = True          # False = dense tensors everywhere
+# Base alignment (bytes) of every activation tensor a kernel reads: the 16-bit conv, weight-gradient, stride-2 and filtered_lrelu
+# kernels fetch dword pairs / 16-byte granules of 16-bit pixels from 4-byte aligned addresses (csrc/conv2d.hip "raw buffer loads of
+# 8 bytes", csrc/conv2d_wgrad.hip "from a 4-byte aligned address", csrc/filtered_lrelu.hip "aligned 16-bit pairs"); with the even
+# widths and pitches their entry points require, every row then starts on this grid too.  fp32 tensors are on it by construction.
+BASE_ALIGN = 4
 
 
 def pitch_for(w, dtype):
@@ -42,15 +50,16 @@ def empty(shape, dtype, device, pitched=True):
 
 
 def pitch_of(t):
-    """Row pitch (elements) if ``t`` is dense or a row-pitched view as made by ``empty``; None for any other layout."""
-    if t.ndim != 4:
+    """Row pitch (elements) if ``t`` is dense or a row-pitched view as made by ``empty``, its base on the kernels' grid; None for
+    any other layout."""
+    if t.ndim != 4 or t.data_ptr() % BASE_ALIGN:
         return None
     if t.is_contiguous():
         return t.shape[3]
     n, c, h, w = t.shape
     s = t.stride()
     ld = s[2]
-    if s[3] != 1 or ld < w or s[1] != h * ld or s[0] != c * h * ld or (ld & 1) or (t.data_ptr() & 3):
+    if s[3] != 1 or ld < w or s[1] != h * ld or s[0] != c * h * ld or (ld & 1):
         return None
     return ld
 
@@ -59,14 +68,18 @@ def rows(t):
     """(tensor, row pitch): ``t`` itself when a pitch-aware kernel can address it, else a contiguous copy."""
     ld = pitch_of(t)
     if ld is None:
-        t = t.contiguous()
+        t = dense(t)
         ld = t.shape[3]
     return t, ld
 
 
-def dense(t):
-    """For kernels that take dense tensors only."""
-    return t if t.is_contiguous() else t.contiguous()
+def dense(t, align=BASE_ALIGN):
+    """For kernels that take dense tensors only: ``t`` itself when it is contiguous with its base on a multiple of ``align`` bytes
+    (the kernels' grid, or the 16 bytes of an entry point that takes whole vectors), else a contiguous copy in a fresh allocation.
+    Differentiable, like ``.contiguous()``."""
+    if not t.is_contiguous():
+        t = t.contiguous()
+    return t.clone() if t.data_ptr() % align else t
 
 
 def whole_buffer(t):

@@ -114,22 +114,17 @@ def plane_dot(a, b=None):
     # the 4-byte base alignment and an even pitch), an even width for 2-byte elements, rows of at least 16 bytes.  Anything else --
     # an expanded stride-0 gradient, an odd-width plane, a view at an odd element offset -- takes the dense kernel on a copy.
     if (not (a.is_contiguous() and (b is None or b.is_contiguous())) and lda is not None and ldb is not None
-            and a.shape[3] * a.element_size() >= 16 and (a.element_size() == 4 or a.shape[3] % 2 == 0)
-            and a.data_ptr() % 4 == 0 and (b is None or b.data_ptr() % 4 == 0)):      # (pitch_of takes a dense tensor at any offset)
+            and a.shape[3] * a.element_size() >= 16 and (a.element_size() == 4 or a.shape[3] % 2 == 0)):
         n, c, h, w = a.shape
         out = torch.empty([n, c], dtype=torch.float32, device=a.device)
         _lib.launched(lib.afcm_plane_dot_ld(out.data_ptr(), a.data_ptr(), _lib.ptr(b), _lib.dtype_code(a), n * c, h, w, lda, ldb, _lib.stream_ptr(a)),
                       'plane_dot')
         return out
-    a = a.contiguous()
-    if a.data_ptr() % 16:                 # a view at an odd storage offset: the kernel wants 16-byte aligned bases
-        a = a.clone()
+    a = _rows.dense(a, 16)                # a view at an odd storage offset: the kernel wants 16-byte aligned bases
     n, c, h, w = a.shape
     if b is not None:
-        b = b.contiguous()
+        b = _rows.dense(b, 16)
         assert b.shape == a.shape and b.dtype == a.dtype
-        if b.data_ptr() % 16:
-            b = b.clone()
     out = torch.empty([n, c], dtype=torch.float32, device=a.device)
     _lib.launched(lib.afcm_plane_dot(out.data_ptr(), a.data_ptr(), _lib.ptr(b), _lib.dtype_code(a), n * c, h * w, _lib.stream_ptr(a)),
                   'plane_dot')
@@ -145,7 +140,7 @@ def plane_dot_gated(a, b, flags, out_scale, gz, next_scale=None, gskip=None):
     lda, ldb = _rows.pitch_of(a), _rows.pitch_of(b)
     n, c, h, w = a.shape
     ok = (lda is not None and ldb is not None and w * a.element_size() >= 16 and (a.element_size() == 4 or w % 2 == 0)
-          and a.data_ptr() % 4 == 0 and b.data_ptr() % 4 == 0 and flags.dtype == torch.int32 and flags.is_contiguous()
+          and flags.dtype == torch.int32 and flags.is_contiguous()
           and tuple(flags.shape[:2]) == (n, c))
     if not ok:
         return plane_dot(a, b)
@@ -248,7 +243,7 @@ def split16(x, scale=None, nparts=2, dtype=torch.float16, bound=None):
     """[nparts, N, C, H, W] of `dtype`: g * scale[n, c] * x[n, c] as a sum of `nparts` 16-bit tensors (C ABI afcm_split16); every
     part is dense, ``.stride(0)`` is the part stride.  ``bound``: the word of ``amax_bits`` (g: its power of two) or None (g = 1)."""
     lib = _lib.load()
-    x = x.contiguous()
+    x = _rows.dense(x, 16)                # (afcm_split16 reads x in 16-byte vectors)
     assert x.dtype == torch.float32 and x.ndim == 4 and nparts in (2, 3) and dtype in (torch.float16, torch.bfloat16)
     n, c, h, w = x.shape
     total = x.numel()
@@ -269,7 +264,7 @@ def plane_dot_parts(parts, b, bound=None):
     its split16 parts (factor g from ``bound``)."""
     lib = _lib.load()
     nparts, n, c, h, w = parts.shape
-    b = b.contiguous()
+    b = _rows.dense(b, 16)                # (afcm_plane_dot_parts reads b in 16-byte vectors)
     assert b.dtype == torch.float32 and tuple(b.shape) == (n, c, h, w) and parts.stride(1) == c * h * w
     out = torch.empty([n, c], dtype=torch.float32, device=b.device)
     _lib.launched(lib.afcm_plane_dot_parts(out.data_ptr(), parts.data_ptr(), parts.stride(0), nparts, b.data_ptr(), _lib._DTYPES[parts.dtype], n * c, h * w,
@@ -449,7 +444,7 @@ class _ScaledConv2d(torch.autograd.Function):
             raise RuntimeError('x is empty')
         _lib.dtype_code(x)
         cout, cin, ks, _ = w.shape
-        x = x.contiguous()
+        x = _rows.dense(x)                # (for callers of .apply itself -- the backward nodes below; after scaled_conv2d: a pointer test)
         # prescaled: the producer of x already applied in_scale (fused into its epilogue) and owns the gradient of in_scale
         # a backward that will need the data gradient gets its (transposed, flipped) weight image from the same launch
         ctx.wpt = None
@@ -504,7 +499,7 @@ class _ScaledConv2d(torch.autograd.Function):
         if ctx.prescaled:
             in_scale = None
         cout, cin, ks, _ = w.shape
-        dy = dy.contiguous()
+        dy = _rows.dense(dy)
         dx = dw = d_in = d_out = None
         if ctx.split is not None:
             # fp32 on the 16-bit matrix pipe: dy's parts (the demodulation factor applied while splitting) feed both gradients; here
@@ -564,7 +559,7 @@ class _ConvWgrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dy, x, ks, pad):
-        dy, x = dy.contiguous(), x.contiguous()
+        dy, x = _rows.dense(dy), _rows.dense(x)
         cout, cin = int(dy.shape[1]), int(x.shape[1])
         ctx.save_for_backward(dy, x)
         ctx.cfg = (ks, pad)
@@ -609,7 +604,7 @@ class _StridedConv2d(torch.autograd.Function):
         lib = _lib.load()
         n, cin, h, wd = x.shape
         cout = int(w.shape[0])
-        x = x.contiguous()
+        x = _rows.dense(x)                # (for callers of .apply itself; after strided_conv2d: a pointer test)
         code = _lib._DTYPES[x.dtype]
         bk = lib.afcm_conv2d_block_k(code)
         rows_pad = (cout + 127) // 128 * 128                       # the stride-2 kernel runs 128-row blocks only
@@ -659,13 +654,13 @@ def strided_conv2d_supported(x, w, padding):
 
 def strided_conv2d(x, w, padding=0):
     """3x3 correlation at stride 2 of 16-bit activations (see _StridedConv2d); check ``strided_conv2d_supported`` first."""
-    return _StridedConv2d.apply(x.contiguous(), w.contiguous(), int(padding))
+    return _StridedConv2d.apply(_rows.dense(x), w.contiguous(), int(padding))
 
 
 def scaled_conv2d(x, w, in_scale=None, out_scale=None, padding=0, prescaled=False, link_in=None):
-    # contiguity is established out here, under autograd, so that the node saves tensors that are still part of the graph
-    # (a second-order backward differentiates through them)
-    return _ScaledConv2d.apply(x.contiguous(), w.contiguous(), in_scale, out_scale, int(padding), bool(prescaled), link_in)
+    # contiguity (and the base alignment the kernels need: _rows.dense) is established out here, under autograd, so that the node
+    # saves tensors that are still part of the graph (a second-order backward differentiates through them)
+    return _ScaledConv2d.apply(_rows.dense(x), w.contiguous(), in_scale, out_scale, int(padding), bool(prescaled), link_in)
 
 
 def modulation_coefficients(w, s, demodulate=True, input_gain=None):

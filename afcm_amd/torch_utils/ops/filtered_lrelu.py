@@ -185,6 +185,7 @@ def _run(x, fu, fd, b, si, cfg, write_signs, want_plane_sum=False, oscale=None, 
     elif si is not None:
         if si.dtype != torch.uint8 or si.ndim != 4 or not si.is_contiguous() or si.shape[:2] != x.shape[:2]:
             raise RuntimeError('signs must be a contiguous uint8 tensor with the same batch & channels as x')
+        si = _rows.dense(si)                             # (the kernels read the codes in dwords: a view at an odd byte offset is copied)
         a.sh, a.swb = si.shape[2], si.shape[3]
         a.signs = si.data_ptr()
     a.x, a.y = x.data_ptr(), y.data_ptr()

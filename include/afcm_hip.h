@@ -121,7 +121,10 @@ typedef struct afcm_filtered_lrelu_args {
 int afcm_filtered_lrelu_shapes(afcm_filtered_lrelu_args* a);
 /* Fused argument sets: the separable 12 / 24-tap cases (up 2 / down 2, up 2 / down 4, up 4 / down 2), and the radial ones, where
  * one filter is 12 x 12 (fuh / fdh = 12) and the other separable: fu 12 or 24 taps with fd 12 x 12 (up 2 or 4, down 2), and fu 12 x 12
- * with fd 12 or 24 taps (up 2, down 2 or 4).  Their sign tensors use layout 0.  Every other 2-D argument set returns AFCM_E_NOKERNEL. */
+ * with fd 12 or 24 taps (up 2, down 2 or 4).  Their sign tensors use layout 0.  Every other 2-D argument set returns AFCM_E_NOKERNEL.
+ * Base pointers (not checked here: the caller keeps them): x, y and skip on 4-byte boundaries -- the 16-bit kernels move aligned pairs and
+ * 16-byte pieces of pixels from dword addresses, which with the even widths and pitches required above puts every row on one --, signs on
+ * a 4-byte boundary (the codes are read and written in dwords), b at any element, fu / fd / oscale / oscale2 fp32. */
 int afcm_filtered_lrelu(const afcm_filtered_lrelu_args* a, void* stream);
 
 /* Matrix-core path (16-bit dtypes, the separable 12/24-tap cases of the generator): the FIR passes run as banded
@@ -135,7 +138,7 @@ int afcm_filtered_lrelu_prepare(const afcm_filtered_lrelu_args* a, void* stream)
 /* In-place gain -> leaky ReLU -> clamp with sign write/read, used by the generic fallback.
  * Replaces plugin `filtered_lrelu_act_(x, si, sx, sy, gain, slope, clamp, writeSigns) -> so`
  *   SG3OPS/filtered_lrelu.cpp:213-290, kernel SG3OPS/filtered_lrelu.cu:1105-1211.
- * signs: uint8 [N, C, h, swb] with swb = ceil16(w)/4 in WRITE mode. */
+ * signs: uint8 [N, C, h, swb] with swb = ceil16(w)/4 in WRITE mode, on a 4-byte boundary (one dword of codes per thread); x at any element. */
 int afcm_filtered_lrelu_act(void* x, uint8_t* signs, int32_t dtype, int32_t n, int32_t c, int32_t h, int32_t w,
                             int32_t sh, int32_t swb, int32_t sx, int32_t sy, float gain, float slope, float clamp,
                             int32_t sign_mode, void* stream);
@@ -146,6 +149,8 @@ int afcm_filtered_lrelu_act(void* x, uint8_t* signs, int32_t dtype, int32_t n, i
  *   SG3OPS/upfirdn2d.cpp:16-98, kernels SG3OPS/upfirdn2d.cu:29-375.
  * f is a device float32 [fh, fw] array (a separable filter is two calls, as in
  * SG3OPS/upfirdn2d.py:244-245).  y: [N, C, yh, yw] with yw = (xw*upx + padx0 + padx1 - fw + downx) / downx.
+ * x and y may sit at any element offset: the 16-bit rows kernel (16-byte loads) is taken only when both lie on 4-byte boundaries, the other
+ * kernels read element by element (same taps in the same order: the result does not depend on the choice).
  * ---------------------------------------------------------------------------------------- */
 int afcm_upfirdn2d(void* y, const void* x, const float* f, int32_t dtype, int32_t n, int32_t c, int32_t xh, int32_t xw,
                    int32_t yh, int32_t yw, int32_t fh, int32_t fw, int32_t upx, int32_t upy, int32_t downx, int32_t downy,
@@ -209,7 +214,10 @@ int afcm_conv2d(void* y, const void* x, const void* wpacked, const float* oscale
  * a row meaningful; 0 = dense).  MI355X layout of the 16-bit activation stream: rows start on 64-byte boundaries.
  * Pitches are taken by the 16-bit 3x3 kernel only.  Columns >= w of x are never used; columns >= Q of y are padding: the kernel
  * writes finite values up to the next multiple of 8 past Q (the tail of a row's last 8-pixel granule) and leaves the rest of the
- * padding UNWRITTEN. */
+ * padding UNWRITTEN.
+ * Base pointers (not checked here: the caller keeps them): x and y on 4-byte boundaries -- a 16-bit image is fetched in 8-byte buffer loads
+ * at dword offsets from its base, which is why widths and pitches are even --, wpacked on 16 bytes (32 as afcm_conv2d_pack_weights writes
+ * it), oscale / obias fp32. */
 int afcm_conv2d_ld(void* y, const void* x, const void* wpacked, const float* oscale, const float* obias, int32_t dtype, int32_t n,
                    int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t rows_pad, int32_t x_pitch,
                    int32_t y_pitch, void* stream);
@@ -233,7 +241,10 @@ int afcm_conv2d_wgrad(float* dw, float* workspace, const void* dy, const void* x
                       int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, void* stream);
 /* The same with row-pitched operands (0 = dense); 16-bit, 3x3 pad 2 or 1x1 pad 0 only.  Columns >= w of x are never used; of dy,
  * the columns up to the next multiple of 8 past Q must hold FINITE values (they multiply zeros): afcm_conv2d_ld writes exactly those
- * columns, afcm_filtered_lrelu writes the whole pitch. */
+ * columns, afcm_filtered_lrelu writes the whole pitch.
+ * Base pointers (not checked here: the caller keeps them): dy and x on 4-byte boundaries (a lane fetches 4-byte pieces or, in the granule
+ * kernel, 16 bytes = 8 pixels from a dword address; widths and pitches are even); dw and workspace fp32, the 16-byte reduction is taken
+ * only where both allow it. */
 int afcm_conv2d_wgrad_ld(float* dw, float* workspace, const void* dy, const void* x, int32_t dtype, int32_t n, int32_t cin,
                          int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t dy_pitch, int32_t x_pitch, void* stream);
 /* afcm_conv2d_wgrad_ld that ALSO returns dots[n][cin] = sum_{o, tap} wq[o][i][tap] * dW_n[o][i][tap] (r06), dW_n = image n's share of the weight
@@ -241,7 +252,8 @@ int afcm_conv2d_wgrad_ld(float* dw, float* workspace, const void* dy, const void
  * dx = conv^T(wq, dy) -- for a conv whose input carries a per-plane style factor s (modulated_conv2d, NET:41-63) the gradient of s times s,
  * which the host otherwise takes from a pass over x and dx (afcm_plane_dot_ld).  The K range is split over workgroups WITHIN images; available
  * for the 16-bit granule kernel (3x3 pad 2, 1x1 pad 0) when the split count of afcm_conv2d_wgrad_splits() is a multiple of n <= 64, else
- * AFCM_E_NOKERNEL (nothing launched: call afcm_conv2d_wgrad_ld and afcm_plane_dot_ld).  Same workspace as afcm_conv2d_wgrad_ld. */
+ * AFCM_E_NOKERNEL (nothing launched: call afcm_conv2d_wgrad_ld and afcm_plane_dot_ld).  Same workspace and the same base alignment of dy
+ * and x (4 bytes) as afcm_conv2d_wgrad_ld. */
 int afcm_conv2d_wgrad_dots_ld(float* dw, float* dots, float* workspace, const void* dy, const void* x, const float* wref, int32_t dtype, int32_t n,
                               int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t ks, int32_t pad, int32_t dy_pitch, int32_t x_pitch,
                               void* stream);
@@ -263,7 +275,7 @@ int afcm_scale_planes(void* y, const void* x, const float* scale, int32_t dtype_
                       int32_t hw, void* stream);
 
 /* out[plane] = sum_i a[plane,i] * b[plane,i]  (b == NULL: plain sum); fp32 accumulation.  Used for the style /
- * demodulation / bias gradients. */
+ * demodulation / bias gradients.  a and b on 16-byte boundaries (AFCM_E_INVALID otherwise). */
 int afcm_plane_dot(float* out, const void* a, const void* b, int32_t dtype, int64_t planes, int32_t hw, void* stream);
 /* The same over planes of h rows x w columns with row pitches (elements; 0 = dense); padding columns are never read.  Rows of at
  * least one 16-byte vector (w >= 16 / element size; w equal to it included), starting on 4-byte boundaries, h * max(pitch) < 2^27. */
@@ -442,7 +454,7 @@ int afcm_conv2d_pack_bank(const afcm_pack_entry* entries, int32_t count, int32_t
  *   bound), on the device: no host round trip between the magnitude pass and the split.
  * afcm_split16: parts[k] (k < nparts in {2, 3}) = part k of g * scale[plane] * x[plane, :] (scale NULL: 1; bound NULL: g = 1, the
  *   bfloat16 case), dtype AFCM_F16 or AFCM_BF16, each a dense tensor of x's shape, part_stride ELEMENTS apart (>= planes * hw, a
- *   multiple of 4).
+ *   multiple of 4).  x on a 16-byte, parts on an 8-byte boundary (AFCM_E_INVALID otherwise); afcm_amax_bits takes x at any fp32 element.
  * afcm_conv2d_pack_split: the weight image of a split conv -- channel block t of [terms * cin16] holds part (term_wparts >> 4 t) & 15 of
  *   g * w ([cout][cin][3][3] fp32; g from `bound`, the weights' afcm_amax_bits word, or 1), in the layout of afcm_conv2d_pack_weights
  *   (mode 0: forward, rows = cout; mode 1: data gradient, transposed and flipped, rows = cin and cin16 is cout rounded up to 16):
@@ -450,10 +462,11 @@ int afcm_conv2d_pack_bank(const afcm_pack_entry* entries, int32_t count, int32_t
  * afcm_conv2d_split: y[n][cout][P][Q] fp32 = oscale[n,o] / (g_a g_b) * sum_t conv(W_t, part_{x(t)}) + obias[o], 3x3, stride 1,
  *   0 <= pad <= 2, w even.  x_parts as written by afcm_split16 on the [n][cin][h][w] tensor (it must hold every part a term names); term
  *   t (t < terms <= 8) reads part (term_parts >> 4 t) & 15 and the channel block t of wpacked (afcm_conv2d_pack_split).  bound_a /
- *   bound_b: the two operands' bound words or NULL (g = 1).
+ *   bound_b: the two operands' bound words or NULL (g = 1).  x_parts on a 4-byte boundary (afcm_conv2d_ld's rule; afcm_split16 writes it on 8).
  * afcm_unscale: t[i] /= g_a g_b in place (the weight gradient summed from split parts of dy and x: afcm_conv2d_wgrad_ld per term).
  * afcm_plane_dot_parts: out[plane] = <sum_k parts[k][plane, :], b[plane, :]> / g, b fp32 -- afcm_plane_dot for a tensor that only exists as
- *   its split parts (the style gradient <x, dx> when the backward keeps x's parts instead of x).
+ *   its split parts (the style gradient <x, dx> when the backward keeps x's parts instead of x).  parts on an 8-byte, b on a 16-byte
+ *   boundary (AFCM_E_INVALID otherwise).
  * ---------------------------------------------------------------------------------------- */
 int afcm_amax_bits(uint32_t* out, const float* x, int64_t planes, int32_t hw, const float* scale, void* stream);
 int afcm_split16(void* parts, const float* x, const float* scale, const uint32_t* bound, int32_t dtype, int64_t planes, int32_t hw,
@@ -473,7 +486,8 @@ int afcm_conv2d_split(float* y, const void* x_parts, const void* wpacked, const 
  * [n][cout][(h + 2 pad - 3) / 2 + 1][(w + 2 pad - 3) / 2 + 1] = the even rows / columns of afcm_conv2d's result (same 16-bit operands, fp32 accumulation; the two
  * kernels sum their K-chunks in a different order -- 16 channels here, 32 in the stride-1 kernel since r05 -- so results agree within 1 ulp
  * of the 16-bit output, not bit for bit: tests/test_gpu_conv.py holds both to a float64 strided conv), at a quarter of its MFMAs and without the full-resolution intermediate.  Forward only (the gradients are stride-1 convolutions with the
- * zero-stuffed dy: afcm_conv2d / afcm_conv2d_wgrad).
+ * zero-stuffed dy: afcm_conv2d / afcm_conv2d_wgrad).  x on a 4-byte boundary (8-byte buffer loads at dword offsets, as in afcm_conv2d_ld; not
+ * checked here), wpacked on 16 bytes.
  * ---------------------------------------------------------------------------------------- */
 int afcm_conv2d_stride2(void* y, const void* x, const void* wpacked, int32_t dtype, int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w,
                         int32_t pad, int32_t rows_pad, void* stream);
@@ -505,6 +519,7 @@ int afcm_axpy_planes(void* y, const void* a, const void* b, const float* scale, 
  *   afcm_fc_act_fwd:  y = act(alpha * x w^T + beta * b)
  *   afcm_fc_act_bwd:  with gp = gy * act'(y) (from the saved output y, as bias_act.cu:68-73): dx = alpha * gp w, dw = alpha * gp^T x,
  *                     db = beta * colsum(gp); any of dx / dw / db may be NULL (not wanted).
+ *   x, w, y (forward) and gy, y (backward) on 16-byte boundaries: rows are read in 16-byte vectors (AFCM_E_INVALID otherwise).
  * afcm_mapping_input_fwd / _bwd: the mapping network's input stage (NET:143-150): x0 [n][zdim + wdim] = cat(normalize(z),
  * normalize(embed(c))) with normalize(v) = v * rsqrt(mean(v^2) + 1e-8) and embed = the linear FC c_dim -> w_dim (weight ew [wdim][cdim],
  * bias eb, gains alpha / beta); cdim = 0: x0 = normalize(z) only.  The backward returns the embedding layer's weight / bias gradients
