@@ -15,6 +15,7 @@ SRC_U8, SRC_I16, SRC_F32, SRC_F64 = 0, 1, 2, 3
 SCHEDULE_SLOTS = 8
 EMA_LERP, EMA_COPY = 0, 1
 GROUP_2B, GROUP_4B = 2, 4
+NORM_PERCENTILE, NORM_STANDARDIZE, NORM_FIXED = 1, 2, 3
 
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 OUT_DTYPES = tuple(_DTYPES)
@@ -178,6 +179,11 @@ SIGNATURES = {
     'afcm_trainlog_cols': (C.c_int32, []),
     'afcm_grad_stats': (C.c_int, [_vp, _i32, _i64, _f32, _vp, _vp]),
     'afcm_trainlog_append': (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    'afcm_norm_plan': (C.c_int, [_i32, _i32, C.POINTER(_i32)]),
+    'afcm_plane_norm_stats': (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp] + [_i32] * 6 + [_f64, _f64, _f64, _vp]),
+    'afcm_slice_norm_stats': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64] + [_i32] * 7 + [_f64, _f64, _f64, _vp]),
+    'afcm_batch_assemble_norm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp] + [_i32] * 6 + [_f64, _f64, _vp]),
+    'afcm_slice_assemble_norm': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _i32] + [_i32] * 6 + [_f64, _f64, _vp]),
 }
 
 

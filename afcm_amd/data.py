@@ -17,6 +17,7 @@ import random
 import numpy as np
 import torch
 
+from .normalise import checked_config, normalise_host
 from .predictor import patch_indices
 
 
@@ -72,11 +73,14 @@ class SliceDataset(torch.utils.data.Dataset):
     ``raw_internal_path_in`` / ``raw_internal_path_out``: modalities of A / B; ``thickness``: candidate slice thicknesses (a random
     one per item when training, the first otherwise); ``slice_num``: 1 (the slice itself) or 4 (thick slices at -1, 0, +1, +2
     thicknesses around the target's own thick slice; positions outside the volume are zero planes BEFORE normalisation, i.e. they
-    come out as the background value -1)."""
+    come out as the background value -1).  ``normalise``: a ``NormaliseConfig`` (afcm_amd/normalise.py) -- every plane, a zero plane included,
+    goes through ``normalise_host`` in place of the fixed ``Normalize``: the reference's ``PercentileNormalizer`` or ``Standardize``."""
 
     def __init__(self, source, phase='train', patch_shape=(1, 256, 256), stride_shape=(1, 32, 32), raw_internal_path_in=('raw',),
-                 raw_internal_path_out=('raw',), rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0):
+                 raw_internal_path_out=('raw',), rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0,
+                 normalise=None):
         assert phase in ('train', 'val', 'test')
+        self.normalise = checked_config(normalise, 'SliceDataset')
         self.phase, self.rand_output, self.cat_inputs = phase, rand_output, cat_inputs
         self.raw_internal_path_in, self.raw_internal_path_out = list(raw_internal_path_in), list(raw_internal_path_out)
         self.thickness, self.slice_num = list(thickness), slice_num
@@ -93,6 +97,8 @@ class SliceDataset(torch.utils.data.Dataset):
         """normalised float32 tensor [1, H, W] of one slice position (None: a zero plane, cmsr_dataset.py:138-139)."""
         v = self.raw[modality]
         m = v[where] if where is not None else np.zeros(v[0:1].shape)
+        if self.normalise is not None:
+            return torch.from_numpy(normalise_host(m, self.normalise, self.min_value, self.max_value)[0].astype(np.float32))
         return torch.from_numpy(normalize(m, self.min_value, self.max_value).astype(np.float32))
 
     def __getitem__(self, idx):

@@ -11,6 +11,8 @@ import ctypes
 import torch
 
 from ... import _lib
+from ...normalise import checked_config, refuse_with
+from .normalise_ops import plane_norm_stats
 
 
 def _table(t, what, dtype, cols):
@@ -20,7 +22,8 @@ def _table(t, what, dtype, cols):
 
 
 def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_value=0., max_value=255., dtype=torch.float32, out=None, cursor=None,
-                   augment=None, intensity=None, independent_planes=False, elastic=None, elastic_ops=None, workspace=None, blur=None):
+                   augment=None, intensity=None, independent_planes=False, elastic=None, elastic_ops=None, workspace=None, blur=None,
+                   normalise=None, norm_coef=None):
     """``pool``: 1-D DEVICE tensor (uint8 / int16 / float32 / float64) holding every volume; ``vols``: DEVICE int64 [n_vols, 4] (element offset into the
     pool, depth, hs, ws); ``items``: DEVICE int32 [n_items, 4] (vol_a, vol_b, idx, thickness; thickness -1: none, ``slice_num`` 1 only).  Sample ``i`` is
     table row ``(cursor[0] if cursor is not None else 0) + first + i``.  Returns ``A [count, slice_num, H, W]``, ``B [count, 1, H, W]`` of ``dtype``
@@ -44,7 +47,12 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     (``afcm_amd.augment_blur.blur_rows``): every plane with flag 1 filtered as the reference's ``GaussianBlur3D`` does, after the geometric
     transforms and the elastic deformation and before the intensity ones, in a fixed number of launches (``afcm_batch_assemble_blur``, with or
     without the other three tables); ``workspace`` then holds at least ``blur_workspace_bytes(count, slice_num, H, W, order)``, ``order`` the
-    spline order of the elastic table or None without one.  An invalid row is a NaN item."""
+    spline order of the elastic table or None without one.  An invalid row is a NaN item.
+    ``normalise``: a ``NormaliseConfig`` (afcm_amd/normalise.py) -- every plane of every item goes through the reference's ``PercentileNormalizer``
+    or ``Standardize`` in place of the fixed ``Normalize`` (followed by it with ``then_normalize``), in two launches: ``afcm_plane_norm_stats`` writes
+    the planes' coefficients, ``afcm_batch_assemble_norm`` applies them, with or without ``augment``.  ``norm_coef``: a DEVICE float64
+    [n >= count, slice_num + 1, 4] the coefficients are written to (a captured graph needs a persistent one), allocated per call when None.
+    ``normalise`` excludes ``intensity``, ``elastic`` and ``blur``."""
     h, w = (int(v) for v in patch_hw)
     first, count = int(first), int(count)
     _lib.require_slice_num(slice_num, 'assemble_batch')
@@ -61,6 +69,10 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
         _table(intensity, 'the intensity table', torch.float64, 36)
         if intensity.shape[0] != items.shape[0]:
             raise RuntimeError(f'assemble_batch: the intensity table has {intensity.shape[0]} rows, the item table {items.shape[0]}: one row per item row')
+    if checked_config(normalise, 'assemble_batch') is not None:
+        refuse_with('assemble_batch', intensity=intensity, elastic=elastic, blur=blur)
+    elif norm_coef is not None:
+        raise RuntimeError('assemble_batch: norm_coef= only with normalise=')
     if not isinstance(independent_planes, bool):
         raise RuntimeError(f'assemble_batch: independent_planes must be a bool, got {independent_planes!r}')
     if independent_planes and intensity is None:
@@ -123,7 +135,10 @@ def assemble_batch(pool, vols, items, first, count, patch_hw, slice_num=4, min_v
     head = (a.data_ptr(), b.data_ptr(), slice_idx.data_ptr(), pool.data_ptr(), pool.numel(), code, vols.data_ptr(), int(vols.shape[0]), items.data_ptr(),
             int(items.shape[0]))
     tail = (_lib.ptr(cursor), first, count, slice_num, h, w, _lib.dtype_code(a), float(min_value), float(max_value), _lib.stream_ptr(pool))
-    if blur is not None:
+    if normalise is not None:
+        coef = plane_norm_stats(pool, vols, items, first, count, (h, w), slice_num, normalise, cursor=cursor, out=norm_coef)
+        rc = _lib.load().afcm_batch_assemble_norm(*head, _lib.ptr(augment), coef.data_ptr(), int(normalise.then_normalize), *tail)
+    elif blur is not None:
         more = (None, None, None, -1) if elastic is None else (elastic.data_ptr(), op_h.data_ptr(), op_w.data_ptr(), int(order))
         rc = _lib.load().afcm_batch_assemble_blur(*head, _lib.ptr(augment), _lib.ptr(intensity), int(independent_planes), *more, blur.data_ptr(),
                                                   workspace.data_ptr(), workspace.numel(), *tail)

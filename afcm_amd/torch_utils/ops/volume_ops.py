@@ -8,6 +8,8 @@ atomics and bit-identical to the host code they restate.
 import torch
 
 from ... import _lib
+from ...normalise import checked_config
+from .normalise_ops import slice_norm_stats
 
 
 def _triple(v, what):
@@ -18,11 +20,14 @@ def _triple(v, what):
 
 
 def assemble_slices(volume, first, count, patch_shape, thickness=None, slice_num=4, min_value=0.0, max_value=255.0, stride_shape=(1, 1, 1),
-                    dtype=torch.float32):
+                    dtype=torch.float32, normalise=None):
     """``volume`` [D, Hs, Ws] (uint8 / int16 / float32 / float64, rows contiguous, any stride in z) -> ``A [count, slice_num, H, W]`` of ``dtype`` and
     ``slice_idx [count, 1]`` float32 for the target slices ``[first, first + count)``, with ``patch_shape = (1, H, W)``: centre crop / constant pad to
     (H, W), the thick slices at -1, 0, +1, +2 ``thickness`` around the target's own (``slice_num`` 4) or the slice itself (1), ``data.normalize``.
-    Only the shipped loader geometry exists: patch depth 1, z stride 1, a ``thickness`` with ``slice_num`` 4."""
+    Only the shipped loader geometry exists: patch depth 1, z stride 1, a ``thickness`` with ``slice_num`` 4.
+    ``normalise``: a ``NormaliseConfig`` (afcm_amd/normalise.py) -- every plane goes through the reference's ``PercentileNormalizer`` or
+    ``Standardize`` in place of the fixed ``Normalize`` (followed by it with ``then_normalize``), in two launches: ``afcm_slice_norm_stats`` writes the
+    planes' coefficients, ``afcm_slice_assemble_norm`` applies them."""
     pd, h, w = _triple(patch_shape, 'assemble_slices: patch_shape')
     if pd != 1 or int(stride_shape[0]) != 1:
         raise RuntimeError(f'assemble_slices: patch depth {pd} with z stride {int(stride_shape[0])}: only one slice per patch and z stride 1 are supported')
@@ -40,6 +45,14 @@ def assemble_slices(volume, first, count, patch_shape, thickness=None, slice_num
     first, count = int(first), int(count)
     a = torch.empty([max(count, 0), slice_num, h, w], dtype=dtype, device=volume.device)
     slice_idx = torch.empty([max(count, 0), 1], dtype=torch.float32, device=volume.device)
+    if checked_config(normalise, 'assemble_slices') is not None:
+        coef = slice_norm_stats(volume, first, count, (h, w), thickness, slice_num, normalise)
+        rc = _lib.load().afcm_slice_assemble_norm(a.data_ptr(), slice_idx.data_ptr(), volume.data_ptr(), code, _lib.dtype_code(a), depth, hs, ws,
+                                                  volume.stride(0), coef.data_ptr(), int(normalise.then_normalize), first, count, slice_num,
+                                                  -1 if thickness is None else int(thickness), h, w, float(min_value), float(max_value),
+                                                  _lib.stream_ptr(volume))
+        _lib.launched(rc, 'slice_assemble_norm')
+        return a, slice_idx
     rc = _lib.load().afcm_slice_assemble(a.data_ptr(), slice_idx.data_ptr(), volume.data_ptr(), code, _lib.dtype_code(a), depth, hs, ws,
                                          volume.stride(0), first, count, slice_num, -1 if thickness is None else int(thickness), h, w,
                                          float(min_value), float(max_value), _lib.stream_ptr(volume))

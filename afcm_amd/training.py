@@ -15,6 +15,9 @@ the item's elastic deformation, and every batch goes through ``afcm_batch_assemb
 With ``DeviceSliceSet(blur=BlurConfig(...))`` a fourth float64 table (afcm_amd/augment_blur.py) carries every plane's decision, sigma and host-made
 weights of the reference's ``GaussianBlur3D``, and every batch goes through ``afcm_batch_assemble_blur``: after the elastic deformation, before
 the intensity transforms.
+With ``DeviceSliceSet(normalise=NormaliseConfig(...))`` (afcm_amd/normalise.py) every plane goes through the reference's ``PercentileNormalizer`` or
+``Standardize`` instead of the fixed ``Normalize``: ``afcm_plane_norm_stats`` writes each plane's coefficients into a buffer the set owns and
+``afcm_batch_assemble_norm`` applies them, with or without the geometric table.
 """
 import random
 
@@ -26,6 +29,7 @@ from . import augment_blur, augment_elastic, augment_intensity
 from .augment import AugmentConfig, apply_host, augment_rows, checked_rows, identity_rows
 from .data import SliceDataset, open_volumes
 from .intensity import percentile_clip_host, rescale_intensity_host
+from .normalise import checked_config, refuse_with
 from .torch_utils.ops.batch_ops import advance_cursor, assemble_batch, blur_workspace_bytes, elastic_workspace_bytes
 from .stylegan3_model import capture_graph, require_capturable
 from .torch_utils.ops.intensity_ops import percentile_clip, percentile_fractions, rescale_intensity
@@ -57,11 +61,18 @@ class DeviceSliceSet:
     ``blur``: a ``BlurConfig`` (afcm_amd/augment_blur.py; 'train' only, with or without the other three) -- a float64
     [len(self), 20 (slice_num + 1)] device table beside the others, ``epoch_blur`` draws an epoch's rows, ``load_epoch`` uploads them and every
     batch goes through ``afcm_batch_assemble_blur``, whose workspace (the elastic launches' included) the set owns in the same way.  None: no
-    table, the launches above."""
+    table, the launches above.
+    ``normalise``: a ``NormaliseConfig`` (afcm_amd/normalise.py; any phase, with or without ``augment``, not with the other three) -- every plane
+    of every item is normalised by its own percentiles or moments: two launches per batch, ``afcm_plane_norm_stats`` into the set's persistent
+    float64 [batch, slice_num + 1, 4] coefficient buffer (``norm_coef``, grown to the largest batch asked for; a captured graph keeps the one it
+    was captured with), then ``afcm_batch_assemble_norm``.  None: the launches above, exactly."""
 
     def __init__(self, sources, phase='train', patch_shape=(1, 256, 256), raw_internal_path_in=('raw',), raw_internal_path_out=('raw',),
                  rand_output=False, cat_inputs=False, thickness=(), slice_num=4, min_value=0.0, max_value=255.0, device='cuda', rescale=None, augment=None, clip=None,
-                 intensity=None, elastic=None, blur=None):
+                 intensity=None, elastic=None, blur=None, normalise=None):
+        if checked_config(normalise, 'DeviceSliceSet') is not None:
+            refuse_with('DeviceSliceSet', intensity=intensity, elastic=elastic, blur=blur)
+        self.normalise, self.norm_coef = normalise, None
         if phase not in ('train', 'val', 'test'):
             raise RuntimeError(f"DeviceSliceSet: phase must be 'train', 'val' or 'test', got {phase!r}")
         if cat_inputs:
@@ -338,6 +349,10 @@ class DeviceSliceSet:
                 more.update(elastic=self.elastic_table, elastic_ops=self.elastic_ops)
             if self.blur is not None:
                 more.update(blur=self.blur_table)
+        if self.normalise is not None:
+            if self.norm_coef is None or self.norm_coef.shape[0] < count:                 # a larger batch than any before: a new one; a graph keeps its own
+                self.norm_coef = torch.empty((count, self.slice_num + 1, 4), dtype=torch.float64, device=self.device)
+            more = dict(normalise=self.normalise, norm_coef=self.norm_coef)
         return assemble_batch(self.pool, self.vols, self.items, first, count, self.patch_shape[1:], slice_num=self.slice_num, min_value=self.min_value,
                               max_value=self.max_value, dtype=dtype, out=out, cursor=self.cursor if use_cursor else None, augment=self.augment_table,
                               intensity=self.intensity_table, independent_planes=self.intensity is not None and self.intensity.independent_planes, **more)
@@ -362,14 +377,17 @@ class DeviceSliceSet:
                                             for p, v in self.volumes[subject].items()}
         return self._host_rescaled[subject]
 
-    def host_batch(self, items, first, count, device=None, augment=None, intensity=None, elastic=None, blur=None):
+    def host_batch(self, items, first, count, device=None, augment=None, intensity=None, elastic=None, blur=None, normalise=None):
         """The same batch through ``SliceDataset(phase='train', thickness=[t])`` items, stacked and uploaded: the comparison arm of tests and
         benchmark.  ``augment``: the parameter table that goes with ``items`` (a set built with ``augment`` only); ``augment.apply_host`` applies
         row ``first + j`` to ``A`` and ``B`` of item ``first + j``.  ``intensity``: the intensity table that goes with ``items`` (a set built with
         ``intensity`` only), applied after it by ``augment_intensity.apply_host``.  ``elastic``: the elastic table that goes with ``items`` (a set
         built with ``elastic`` only), applied between the two by ``augment_elastic.apply_host``.  ``blur``: the blur table that goes with
         ``items`` (a set built with ``blur`` only), applied between the elastic and the intensity arms by ``augment_blur.apply_host``.  A row the
-        kernel would refuse raises here."""
+        kernel would refuse raises here.  ``normalise``: a ``NormaliseConfig`` -- the items come from ``SliceDataset(normalise=)``, every plane
+        through ``normalise_host`` before the geometric transforms; not with ``intensity``, ``elastic`` or ``blur``."""
+        if checked_config(normalise, 'DeviceSliceSet.host_batch') is not None:
+            refuse_with('DeviceSliceSet.host_batch', intensity=intensity, elastic=elastic, blur=blur)
         items = self._checked_items(items)
         elastic = None if elastic is None else self._checked_elastic(elastic, items.shape[0], 'host_batch')
         blur = None if blur is None else self._checked_blur(blur, items.shape[0], 'host_batch')
@@ -381,11 +399,12 @@ class DeviceSliceSet:
             subject, column_b = divmod(vol_b, m)
             if not (0 <= vol_b < m * len(self.volumes)) or vol_a != subject * m + self.paths.index(self.raw_internal_path_in[0]):
                 raise RuntimeError(f'DeviceSliceSet.host_batch: row ({vol_a}, {vol_b}, {idx}, {t}) does not pair the input and an output of one subject')
-            key = (subject, column_b)
+            key = (subject, column_b, normalise)
             if key not in self._host_sets:
                 self._host_sets[key] = SliceDataset(self._host_volumes(subject), phase='train', patch_shape=self.patch_shape, stride_shape=(1, 1, 1),
                                                     raw_internal_path_in=self.raw_internal_path_in[:1], raw_internal_path_out=[self.paths[column_b]],
-                                                    slice_num=self.slice_num, min_value=self.min_value, max_value=self.max_value)
+                                                    slice_num=self.slice_num, min_value=self.min_value, max_value=self.max_value,
+                                                    normalise=normalise)
             ds = self._host_sets[key]
             ds.thickness = [] if t == -1 else [t]
             if not 0 <= idx < len(ds):
@@ -438,7 +457,7 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     (``gen_z``: a fixed [batch_size, z_dim] tensor instead of a draw per batch).  ``augment``: the epoch's parameter table
     (``DeviceSliceSet.epoch_augment``) for a set built with ``augment``, ``intensity``: the epoch's intensity table (``epoch_intensity``) for one built with ``intensity``, ``elastic``: the epoch's elastic table
     (``epoch_elastic``) for one built with ``elastic`` (the host arm is ``augment_elastic.apply_host``), ``blur``: the epoch's blur table (``epoch_blur``) for one built with ``blur`` (the host arm is
-    ``augment_blur.apply_host``); both arms apply them.  Works with ``StyleGAN3GeneratorStep`` and
+    ``augment_blur.apply_host``); both arms apply them.  A set built with ``normalise`` feeds both arms through its normaliser.  Works with ``StyleGAN3GeneratorStep`` and
     ``StyleGAN3Step`` alike.
     Returns the new ``total_iters``."""
     if where not in ('device', 'host'):
@@ -459,7 +478,8 @@ def train_epoch(step, dataset, batch_size, items, total_iters=0, ema_kimgs=None,
     for first in range(0, n, batch_size):
         count = min(batch_size, n - first)
         batch = (lambda: dataset.batch(first, count)) if where == 'device' else (
-            lambda: dataset.host_batch(items, first, count, device=device, augment=augment, intensity=intensity, elastic=elastic, blur=blur))
+            lambda: dataset.host_batch(items, first, count, device=device, augment=augment, intensity=intensity, elastic=elastic, blur=blur,
+                                       normalise=dataset.normalise))
         total_iters += batch_size
         _fed_step(step, schedule, batch_size, batch, None if gen_z is None else gen_z[:count], cur_nimg=total_iters)
         if schedule is None and ema_kimgs is not None and getattr(step, 'netG_ema', None) is not None:
@@ -487,7 +507,7 @@ class TrainingGraph:
     ``intensity`` with ``afcm_batch_assemble_noise``, its table persistent in the same way; one built with ``elastic`` with the launches of
     ``afcm_batch_assemble_elastic`` -- a fixed number, each skipping on the device the items whose flag is 0 -- and the graph keeps the workspace
     it was captured with; one built with ``blur`` with the launches of ``afcm_batch_assemble_blur``, fixed in number as well, the workspace kept
-    likewise."""
+    likewise; one built with ``normalise`` with ``afcm_plane_norm_stats`` and ``afcm_batch_assemble_norm``, the coefficient buffer kept likewise."""
 
     def __init__(self, step, dataset, batch_size, warmup=3, fixed_z=False, dtype=torch.float32, gen_z=None, undo_warmup=False):
         require_capturable(step, 'TrainingGraph')
@@ -541,6 +561,7 @@ class TrainingGraph:
 
         self.graph = capture_graph(lambda: _fed_step(step, schedule, batch_size, cursor_batch, self.gen_z), warmup, next_rows, leave_no_trace)
         self.elastic_workspace = dataset.elastic_workspace    # the captured launches point into it, whatever the set allocates later
+        self.norm_coef = dataset.norm_coef                    # likewise the coefficients of a set built with normalise
 
     def load_epoch(self, items, augment=None, intensity=None, elastic=None, blur=None):
         self.dataset.load_epoch(items, augment, intensity, elastic, blur)

@@ -151,7 +151,7 @@ def _input_head(real_A):
 
 @torch.no_grad()
 def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4, patch_hw, batch_size, patch_halo=(0, 8, 8), heads=('prediction',),
-                   where='device', min_value=0., max_value=255., rescale=None, clip=None, share_encoder=False):
+                   where='device', min_value=0., max_value=255., rescale=None, clip=None, share_encoder=False, normalise=None):
     """One subject through the EMA generator: ``source`` (a mapping {internal path: array [D, Hs, Ws]} or an HDF5 file name) -> {head: [C, D, H, W]}
     with ``heads`` out of 'prediction' (``fake_B``) and 'input' (the thick slice each target falls into).  ``step`` needs
     ``set_test_input(real_A, slice_idx)``, ``test()``, ``real_A`` and ``fake_B`` [B, C, H, W] (``StyleGAN3GeneratorStep`` built with ``ema=True``).
@@ -167,7 +167,10 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     ``share_encoder=True`` (``where='device'`` only): with four-slice inputs the ``thickness`` consecutive targets of one thick slice carry the same
     ``A`` bit for bit, so the step is told which rows of a batch are equal (``set_test_input(a, slice_idx, groups, leaders)``) and runs the
     generator's encoder once per group instead of once per sample.  The batch partition does not change; a group that straddles a batch boundary
-    is encoded once in each batch.  With ``slice_num`` 1 or no thickness every sample is its own group."""
+    is encoded once in each batch.  With ``slice_num`` 1 or no thickness every sample is its own group.
+    ``normalise``: a ``NormaliseConfig`` (afcm_amd/normalise.py) -- a model trained under the reference's ``PercentileNormalizer`` or ``Standardize``
+    needs it at inference: every input plane is normalised by its own percentiles or moments, by ``assemble_slices(normalise=)`` on the device and
+    by ``SliceDataset(normalise=)`` on the host, the same bits."""
     if where not in ('device', 'host'):
         raise ValueError(f"where must be 'device' or 'host', got {where!r}")
     if share_encoder and where != 'device':
@@ -198,7 +201,8 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
         if clip is not None:
             source = {path: percentile_clip_host(open_volumes(source, [path])[path], clip)[0]}
         ds = SliceDataset(source, phase='test', patch_shape=patch_shape, stride_shape=stride_shape, raw_internal_path_in=[path], raw_internal_path_out=[path],
-                          thickness=[] if thickness is None else [thickness], slice_num=slice_num, min_value=min_value, max_value=max_value)
+                          thickness=[] if thickness is None else [thickness], slice_num=slice_num, min_value=min_value, max_value=max_value,
+                          normalise=normalise)
         volume_shape = tuple(ds.raw[path].shape)
         predictors, maps = {}, {}
         for first in range(0, len(ds), batch_size):
@@ -228,7 +232,7 @@ def predict_volume(step, source, *, raw_internal_path_in, thickness, slice_num=4
     shared = GroupTables(plan, batch_size, thickness if slice_num == 4 else None, device) if share_encoder else None
     for first in range(0, len(plan), batch_size):
         a, slice_idx = assemble_slices(volume, first, min(batch_size, len(plan) - first), patch_shape, thickness=thickness, slice_num=slice_num,
-                                       min_value=min_value, max_value=max_value, stride_shape=stride_shape)
+                                       min_value=min_value, max_value=max_value, stride_shape=stride_shape, normalise=normalise)
         if shared is None:
             step.set_test_input(a, slice_idx)
         else:
@@ -273,7 +277,7 @@ def evaluate_volume(step, source, target, *, from_network_range=True, with_3d=Fa
     ``with_3d=True`` adds ``evaluate_3D`` (volume PSNR and the 7^3-window SSIM evaluate.py:81 reports first) as ``'3d'``: the layer sums of
     ``afcm_volume_ssim`` travel in that same copy, behind the three tables.  ``rescale=(q_lo, q_hi)`` (a ``predict_volume`` keyword) takes a raw
     scanner volume as the source and rescales it on the device after the upload, still without a host read; ``clip=(p_min, p_max)`` does the same
-    with the percentile clip.
+    with the percentile clip; ``normalise=NormaliseConfig(...)`` normalises every input plane by its own statistics, as in ``predict_volume``.
     Returns {'slice': (psnr, ssim, mae), 'one': (psnr, ssim, mae), 'prediction': [C, D, H, W] device tensor} and, on request, '3d': (psnr, ssim, mae)."""
     if predict_kwargs.get('where', 'device') != 'device':
         raise ValueError("evaluate_volume runs on the device; for host arrays use predict_volume(where='host') and afcm_amd.evaluation")

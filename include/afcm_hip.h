@@ -988,6 +988,53 @@ int afcm_grad_stats(const afcm_adam_entry* table, int32_t n, int64_t total_chunk
 int afcm_trainlog_append(double* log, int32_t capacity, int64_t* head, const double* block, const float* step_G, const float* step_D,
                          const float* losses, const double* partials_G, int64_t chunks_G, const double* partials_D, int64_t chunks_D, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Per-plane normalisers (additions to v13): the reference's PercentileNormalizer and Standardize (data/augment/transforms.py:552-601,
+ * channelwise False; the first two entries of configs/defaults.py for both phases) inside the two loaders.  They come before every geometric
+ * transform, and their coefficients are a statistic of each [1, h, w] item plane m: the plane after the centred crop / zero pad, padded zeros
+ * counted, a thick-slice position outside the volume a plane of zeros.  Two launches: the statistics, then the assembly.
+ *
+ * afcm_plane_norm_stats (the items of afcm_batch_assemble's pool and tables: k planes of a, then b) and afcm_slice_norm_stats (the slices of
+ * afcm_slice_assemble: k planes) write coef [count][planes][4] DEVICE float64 = (sub, div, stat0, stat1) per plane, one 256-thread workgroup
+ * each.  All arithmetic is float64 whatever the source type, every operation rounded on its own.
+ *   AFCM_NORM_PERCENTILE  p0, p1 = pmin / 100, pmax / 100.  lo, hi = numpy's `linear` percentiles: with n = h w and v = q (n - 1), the order
+ *                         statistics at floor(v) and min(floor(v) + 1, n - 1) (-0.0 taken as +0.0) combined by numpy's _lerp with g = v - floor(v):
+ *                         g >= 0.5 ? b - (b - a) (1 - g) : a + (b - a) g.  sub = lo, div = (hi - lo) + eps, stats lo, hi.  The order statistics
+ *                         come from an exact radix select, 8 bits per pass, most significant first (u8 one pass, i16 two, f32 four, f64 eight),
+ *                         in LDS histograms.  One NaN in the plane makes all four NaN, as numpy's percentile does.
+ *   AFCM_NORM_STANDARDIZE mean = sum / n, std = sqrt(ss / n), ss the sum of (m - mean)^2.  Both sums in ONE order: thread t adds pixels t, t + 256,
+ *                         ... of the row-major plane in ascending order onto +0.0, then the tree s[t] += s[t + o] for o = 128, 64, ..., 1.
+ *                         sub = mean, div = std < eps ? eps : std (numpy.clip: a NaN stays), stats mean, std.
+ *   AFCM_NORM_FIXED       p0, p1 = the given mean and std: sub = p0, div = p1 < eps ? eps : p1; nothing is read.
+ * A plane outside the volume reads nothing: lo = hi = 0, or mean = std = 0.  An invalid item row (afcm_batch_assemble's checks) reads nothing
+ * and gives four NaNs.  No global atomics (integer LDS adds only), no allocation, no host read: bit-identical from launch to launch, on
+ * `stream`, capturable.  afcm_norm_plan: plan[0..3] = threads per workgroup, times the plane is read, bits per digit, ranks selected.
+ *
+ * afcm_batch_assemble_norm is afcm_batch_assemble_aug (augment may be NULL: afcm_batch_assemble) and afcm_slice_assemble_norm is
+ * afcm_slice_assemble -- thread shape, row checks, gather, labels and stores -- with the value of a pixel m of plane p of sample i
+ *   v = (m - sub) / div  from coef[i][p],  then, with then_normalize, clip(2 * ((v - min) / (max - min)) - 1, -1, 1) (a NaN stays),
+ * in float64 for EVERY source type, then one rounding to float32 and one more to a 16-bit out_dtype.  A nearest-neighbour gather commutes
+ * with a pointwise map, so coefficients taken from the un-augmented plane are the reference's order of operations.  min_value / max_value
+ * are read only with then_normalize but checked always.
+ * AFCM_E_INVALID: as the launches they extend; also a null or misaligned coef, an unknown mode, percentile fractions outside
+ * 0 <= p0 <= p1 <= 1, a NaN eps, then_normalize not 0 or 1, a plane of more than 2^30 pixels.
+ * ---------------------------------------------------------------------------------------- */
+enum { AFCM_NORM_PERCENTILE = 1, AFCM_NORM_STANDARDIZE = 2, AFCM_NORM_FIXED = 3 };
+int afcm_norm_plan(int32_t src_dtype, int32_t mode, int32_t* plan);
+int afcm_plane_norm_stats(double* coef, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols, int32_t n_vols,
+                          const int32_t* items, int32_t n_items, const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w,
+                          int32_t mode, double p0, double p1, double eps, void* stream);
+int afcm_slice_norm_stats(double* coef, const void* src, int32_t src_dtype, int32_t depth, int32_t hs, int32_t ws, int64_t src_stride_z, int32_t first,
+                          int32_t count, int32_t k, int32_t thickness, int32_t h, int32_t w, int32_t mode, double p0, double p1, double eps,
+                          void* stream);
+int afcm_batch_assemble_norm(void* a, void* b, float* slice_idx, const void* pool, int64_t pool_elems, int32_t src_dtype, const int64_t* vols,
+                             int32_t n_vols, const int32_t* items, int32_t n_items, const double* augment, const double* coef, int32_t then_normalize,
+                             const int64_t* cursor, int32_t first, int32_t count, int32_t k, int32_t h, int32_t w, int32_t out_dtype, double min_value,
+                             double max_value, void* stream);
+int afcm_slice_assemble_norm(void* a, float* slice_idx, const void* src, int32_t src_dtype, int32_t out_dtype, int32_t depth, int32_t hs, int32_t ws,
+                             int64_t src_stride_z, const double* coef, int32_t then_normalize, int32_t first, int32_t count, int32_t k, int32_t thickness,
+                             int32_t h, int32_t w, double min_value, double max_value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

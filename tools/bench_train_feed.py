@@ -11,6 +11,9 @@ against the fixed-input one.  Two steps, each its own process (run each under it
     python tools/bench_train_feed.py feed --blur           # afcm_batch_assemble_blur (no plane, every plane at radius 8, the reference's
                                                            # probability 0.5, the same with the elastic table) beside the plain and the elastic
                                                            # launch; the host arm.  --only ARM: that arm's launches alone, for a kernel trace
+    python tools/bench_train_feed.py feed --normalise percentile|standardize
+                                                           # afcm_plane_norm_stats alone, the normalised batch (statistics +
+                                                           # afcm_batch_assemble_norm) beside the plain launch; the host arm
 
 (a) alternates ``DeviceSliceSet.host_batch`` (SliceDataset items in numpy, stacked, uploaded) and ``DeviceSliceSet.batch`` (one launch) over the same
 rows of a synthetic uint8 set after a warm-up of each, the alternation repeated; wall time by a host clock ended by a synchronise.  (b) times
@@ -531,6 +534,49 @@ def step(args):
     return 0
 
 
+def feed_normalise(args):
+    """``feed --normalise percentile|standardize``: the statistics launch alone (``afcm_plane_norm_stats``, one workgroup per plane), the fed
+    batch (statistics + ``afcm_batch_assemble_norm``) beside the plain launch, device events with the arms alternated inside every repeat; and
+    the host arm -- stacked ``SliceDataset(normalise=)`` items -- by a host clock."""
+    import torch
+    from afcm_amd.normalise import NormaliseConfig
+    from afcm_amd.torch_utils.ops.normalise_ops import norm_plan, plane_norm_stats
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_train_feed.py needs a GPU: a time taken without one says nothing')
+    dev = torch.device('cuda:0')
+    config = NormaliseConfig(percentile=(1, 99.6)) if args.normalise == 'percentile' else NormaliseConfig(standardize=True)
+    ds = synthetic_set(args.subjects, args.depth, args.res, dev, normalise=config)
+    plain = synthetic_set(args.subjects, args.depth, args.res, dev)
+    items = ds.epoch_items(0)
+    ds.load_epoch(items)
+    plain.load_epoch(items)
+    hw = (args.res, args.res)
+    coef = torch.empty((args.batch, 5, 4), dtype=torch.float64, device=dev)
+    fns = {'stats_alone': lambda: plane_norm_stats(ds.pool, ds.vols, ds.items, 0, args.batch, hw, 4, config, out=coef),
+           'plain_batch': lambda: plain.batch(0, args.batch),
+           'normalised_batch': lambda: ds.batch(0, args.batch)}
+    us = {name: [] for name in fns}
+    for _ in range(args.repeats):
+        for name, fn in fns.items():
+            us[name].append(events_us(fn))
+    print(f'{args.normalise}: batches of {args.batch} x (4 + 1) planes at {args.res}^2 from uint8 sources, {args.batch * 5} statistics workgroups, '
+          f'plan {norm_plan(torch.uint8, config)}; 200 launches per figure, {args.repeats} repeats, the arms alternated')
+    stats = {}
+    for name, v in us.items():
+        stats[name] = dict(per_repeat_us=v, mean_us=sum(v) / len(v), spread_us=spread(v))
+        print(f'{name:18s} us per call {"  ".join(f"{x:8.2f}" for x in v)}   mean {stats[name]["mean_us"]:8.2f}   spread {stats[name]["spread_us"]:.2f}')
+    want = ds.host_batch(items, 0, args.batch, normalise=config)
+    t0 = time.perf_counter()
+    for j in range(min(args.batches, 2)):
+        ds.host_batch(items, j * args.batch, args.batch, normalise=config)
+    torch.cuda.synchronize()
+    host_ms = (time.perf_counter() - t0) * 1e3 / min(args.batches, 2)
+    equal = all(torch.equal(a, b) for a, b in zip(ds.batch(0, args.batch), want))
+    print(f'host arm {host_ms:.1f} ms per batch; the two arms\' batches are {"bit-identical" if equal else "DIFFERENT"}')
+    print(json.dumps(dict(bench='train_feed_normalise', mode=args.normalise, res=args.res, batch=args.batch, launches=stats, host_ms=host_ms, equal=equal)))
+    return 0 if equal else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('what', choices=['feed', 'step'])
@@ -546,7 +592,13 @@ def main():
     ap.add_argument('--elastic', action='store_true', help='feed: time the elastic launches and their host arm instead')
     ap.add_argument('--blur', action='store_true', help='feed: time the blur launches and their host arm instead')
     ap.add_argument('--only', default=None, help='feed --blur: launch this one arm 20 times and return (for a kernel trace)')
+    ap.add_argument('--normalise', choices=['percentile', 'standardize'], default=None,
+                    help='feed: time the per-plane statistics launch, the normalised batch and its host arm instead')
     args = ap.parse_args()
+    if args.normalise is not None:
+        if args.what != 'feed' or args.augment or args.intensity or args.elastic or args.blur:
+            raise SystemExit('--normalise belongs to the feed step, on its own')
+        return feed_normalise(args)
     if (args.augment or args.intensity or args.elastic or args.blur) and args.what != 'feed':
         raise SystemExit('--augment, --intensity, --elastic and --blur belong to the feed step')
     if args.augment + args.intensity + args.elastic + args.blur > 1:
