@@ -184,6 +184,9 @@ SIGNATURES = {
     'afcm_slice_norm_stats': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64] + [_i32] * 7 + [_f64, _f64, _f64, _vp]),
     'afcm_batch_assemble_norm': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp] + [_i32] * 6 + [_f64, _f64, _vp]),
     'afcm_slice_assemble_norm': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _vp, _i32] + [_i32] * 6 + [_f64, _f64, _vp]),
+    'afcm_modconv_epilogue_workspace_bytes': (C.c_int64, [_i32] * 4),
+    'afcm_modconv_epilogue_fwd': (C.c_int, [_vp] * 6 + [_i32] * 6 + [_f64, _f64, _f64, _vp]),
+    'afcm_modconv_epilogue_bwd': (C.c_int, [_vp] * 10 + [_i32] * 6 + [_f64, _f64, _f64, _vp]),
 }
 
 

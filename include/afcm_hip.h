@@ -1035,6 +1035,31 @@ int afcm_slice_assemble_norm(void* a, float* slice_idx, const void* src, int32_t
                              int64_t src_stride_z, const double* coef, int32_t then_normalize, int32_t first, int32_t count, int32_t k, int32_t thickness,
                              int32_t h, int32_t w, double min_value, double max_value, void* stream);
 
+/* ----------------------------------------------------------------------------------------
+ * Epilogue of the CoModGAN modulated convolution (additions to v13: no existing entry point or struct changes, so the number stays;
+ * csrc/modconv_epilogue.hip, afcm_amd/networks_comodgan.py).  All tensors contiguous float32.  u = 1 or 2, with (H, W) = (h, w) the
+ * LOW resolution:
+ *   t [n, u u o, h, w]  the convolution's result; for u = 2 channel (py 2 + px) o + c holds output phase (py, px) of channel c
+ *   dcoefs [n, o], bias [o], noise NULL | [u h, u w] (noise_per_sample 0) | [n, 1, u h, u w] (1), noise_strength one DEVICE float (NULL with noise)
+ *   y [n, o, u h, u w]:  y[., c, u i + py, u j + px] = clamp(lrelu(t[., (py u + px) o + c, i, j] dcoefs + noise noise_strength + bias) gain, +-clamp)
+ * evaluated in float64 and rounded once; lrelu(v) = v > 0 ? v : alpha v; clamp < 0: none, otherwise the clamp rounded to float32.
+ * afcm_modconv_epilogue_bwd (first order), with g = dy (y > 0 ? 1 : alpha) gain and g = 0 where |y| >= clamp (the slope alpha at y == 0,
+ * no gradient at the clamp: bias_act's conventions):  d_t = g dcoefs in t's layout, d_dcoefs [n, o] = sum g t, d_bias [o] = sum g,
+ * d_noise_strength (one float; NULL with noise) = sum g noise.  The sums are float64 in one fixed order (stated in the source file), without
+ * atomics: bit-identical from launch to launch.  workspace: afcm_modconv_epilogue_workspace_bytes(n, o, h, w) bytes, 8-byte aligned,
+ * written before it is read.  No allocation, no host read, on `stream`, capturable.
+ * Tensors that are all 16-byte aligned, with w a multiple of 4 / u, are read and written in 16-byte pieces; any other take 4-byte reads.
+ * AFCM_E_INVALID (nothing launched): a null or misaligned pointer (y and dy: 4 u bytes), noise without its strength or the reverse, u not
+ * 1 or 2, an empty tensor, a plane of 2^31 pixels or more, a gain that is not positive and finite, a NaN slope or clamp.
+ * ---------------------------------------------------------------------------------------- */
+int64_t afcm_modconv_epilogue_workspace_bytes(int32_t n, int32_t o, int32_t h, int32_t w);
+int afcm_modconv_epilogue_fwd(float* y, const float* t, const float* dcoefs, const float* bias, const float* noise, const float* noise_strength,
+                              int32_t noise_per_sample, int32_t n, int32_t o, int32_t h, int32_t w, int32_t u, double alpha, double gain,
+                              double clamp, void* stream);
+int afcm_modconv_epilogue_bwd(float* d_t, float* d_dcoefs, float* d_bias, float* d_noise_strength, double* workspace, const float* dy,
+                              const float* y, const float* t, const float* dcoefs, const float* noise, int32_t noise_per_sample, int32_t n,
+                              int32_t o, int32_t h, int32_t w, int32_t u, double alpha, double gain, double clamp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
