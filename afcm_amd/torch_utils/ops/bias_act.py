@@ -4,6 +4,11 @@ Drop-in for the reference's ``bias_act(x, b=None, dim=1, act='linear', alpha=Non
 clamp=None, impl='cuda')`` (SG3OPS/bias_act.py:52-86).  ``impl='cuda'`` on a ROCm tensor runs the HIP
 kernel ``afcm_bias_act``; first- and second-order gradients re-enter the same kernel in its
 grad=1 / grad=2 modes (the plugin contract of SG3OPS/bias_act.py:142-203).
+
+One departure from that contract: 'linear' with a clamp keeps its output for the backward.  The plugin's wrapper saves y only for the
+activations whose derivative reads it (``'y' in spec.ref``), so behind a clamped 'linear' -- the CoModGAN ToRGB layer -- its kernel finds
+no saved output and lets the gradient through where the forward clamped; the reference's own ``_bias_act_ref`` (and the derivative of
+clamp) gives 0 there, and that is what the reference goldens hold (tests/golden/K3_comod32.npz).
 """
 import collections
 import math
@@ -90,7 +95,8 @@ class _BiasAct(torch.autograd.Function):
         if act != 'linear' or gain != 1 or clamp >= 0 or b is not None:
             y = _launch(x, b, None, None, None, 0, dim, spec, alpha, gain, clamp)
         need_x = 'x' in spec.ref or spec.has_2nd_grad
-        ctx.save_for_backward(x if need_x else None, b if need_x else None, y if 'y' in spec.ref else None)
+        need_y = 'y' in spec.ref or (act == 'linear' and clamp >= 0)           # the clamp's mask is read from the saved output
+        ctx.save_for_backward(x if need_x else None, b if need_x else None, y if need_y else None)
         ctx.cfg = (dim, act, alpha, gain, clamp)
         return y
 

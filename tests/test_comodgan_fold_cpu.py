@@ -57,6 +57,8 @@ GOLDEN_CONFIGS = {
                        synthesis_kwargs=dict(channel_base=512, channel_max=16, cond_mod=True, skip_resolution=64)),
     'K2_comod128': dict(z_dim=32, c_dim=1, w_dim=32, img_resolution=128, img_channels_in=4, img_channels_out=1, mapping_kwargs=dict(num_layers=2),
                         synthesis_kwargs=dict(channel_base=1024, channel_max=12, conv_clamp=256, skip_resolution=32)),
+    'K3_comod32': dict(z_dim=32, c_dim=2, w_dim=32, img_resolution=32, img_channels_in=2, img_channels_out=1, mapping_kwargs=dict(num_layers=2),
+                       synthesis_kwargs=dict(channel_base=256, channel_max=8, cond_mod=False, conv_clamp=2, skip_resolution=8)),
 }
 
 

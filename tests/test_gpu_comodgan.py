@@ -1,6 +1,6 @@
 """The CoModGAN generator (afcm_amd/networks_comodgan.py) on the GPU: against the reference's own outputs and gradients (tests/golden/K1, K2:
 tools/gen_golden_comodgan.py) under the bounds tests/test_gpu_generator.py applies to the fp32 stylegan3 generator, the fused arm against the
-unfused one, the noise modes, and the generator inside the package's training step, captured graph, validation and volume loops.
+unfused one (also under the float64-oracle criterion of tests/comodgan_ref.py), the noise modes, and the generator inside the package's training step, captured graph, validation and volume loops.
 
 Every figure is printed before it is asserted."""
 import numpy as np
@@ -16,6 +16,8 @@ CONFIGS = {
                        synthesis_kwargs=dict(channel_base=512, channel_max=16, cond_mod=True, skip_resolution=64, dropout_rate=0)),
     'K2_comod128': dict(z_dim=32, c_dim=1, w_dim=32, img_resolution=128, img_channels_in=4, img_channels_out=1, mapping_kwargs=dict(num_layers=2),
                         synthesis_kwargs=dict(channel_base=1024, channel_max=12, conv_clamp=256, skip_resolution=32, dropout_rate=0)),
+    'K3_comod32': dict(z_dim=32, c_dim=2, w_dim=32, img_resolution=32, img_channels_in=2, img_channels_out=1, mapping_kwargs=dict(num_layers=2),
+                       synthesis_kwargs=dict(channel_base=256, channel_max=8, cond_mod=False, conv_clamp=2, skip_resolution=8, dropout_rate=0)),
 }
 _CACHE = {}
 
@@ -100,6 +102,15 @@ def test_fused_arm_equals_unfused_arm(name, monkeypatch):
     worst = max((float((gf[k] - gu[k]).double().norm() / gu[k].double().norm().clamp_min(1e-30)), k) for k in gu)
     print(f'{name}: fused vs unfused worst gradient relative L2 {worst[0]:.3e} ({worst[1]})')
     assert worst[0] <= 1e-2
+    # the criterion of tests/comodgan_ref.py between the two arms: each arm's gradient against the other's, the yardstick Y from the float64
+    # and float32 oracle on the golden's own state and inputs (nothing in it comes from either arm)
+    import comodgan_ref as R
+    bounds = R.golden_bounds(_golden(name)[0], CONFIGS[name])
+    ratios = {k: max(R.err(gf[k], gu[k]), R.err(gu[k], gf[k])) / bounds[k] for k in gu}
+    worst = max((v, k) for k, v in ratios.items())
+    print(f'{name}: fused vs unfused worst gradient err / max(Y, median Y) {worst[0]:.3f} ({worst[1]}), MARGIN {R.MARGIN}')
+    bad = {k: round(v, 3) for k, v in ratios.items() if not v <= R.MARGIN}
+    assert not bad, bad
 
 
 def test_noise_modes():
